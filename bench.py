@@ -2,7 +2,8 @@
 """Benchmark of the style-transfer inner loop on MI355X (BASELINE.json: iterations/sec @1024px VGG19; images/hour at
 1/2/4/8 GPUs).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 1024] [--optimizer adam] [--precision fp32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 1024] [--optimizer adam] [--precision fp32] [--dump-outputs DIR]
+    python bench.py --full                                                  # + roofline, worker_level, CPU oracle / parity, other configs
     python bench.py --size 2048 --optimizer lbfgs --precision bf16          # BASELINE configs[2]
     python bench.py --examples                                              # BASELINE configs[0]: the example pair at 256 px, 50 Adam iterations
     python bench.py --gpus 8 --tiled 2x4 --size 8192                        # BASELINE configs[4] (tile-sharded image)
@@ -19,8 +20,11 @@ aggregate it/s over all ranks and scaling is weak.  The ranks come either from t
 sets RANK / LOCAL_RANK / WORLD_SIZE) or, when those are absent and --gpus N > 1, from this script itself: it starts N
 fresh child processes (one per GPU) BEFORE anything touches the GPU and relays rank 0's line.
 
-Rank 0 prints ONE JSON line.  `value` comes from the median of R back-to-back timed blocks of exactly K steps (each
-bracketed by barrier + device sync, max over ranks); all blocks are listed under `timing`.  `roofline` is for the
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times ONE block of exactly K steps (bracketed by barrier + device
+sync, max over ranks), writes its outputs when --dump-outputs DIR is given and prints the line; `value` and `ms_per_step` come
+from that block.  Everything else below is measured only with --full: R = 5 back-to-back blocks by default (`value` = the
+median block; all blocks are listed under `timing`), the profiled leg, `worker_level`, the CPU oracle and the short legs of the
+other BASELINE configs (`extra_configs`).  `roofline` is for the
 dominant kernel class (the conv3x3 launches on the matrix cores): `achieved` counts the FLOPs the MFMA pipe executes
 (Winograd launches perform 4/9 of the direct-convolution FLOPs), so `frac` is a true fraction of the MFMA peak; the
 algorithmic (direct-convolution) figure is kept beside it.  `cpu_baseline` (kind "port") and `parity` come
@@ -28,6 +32,10 @@ from the CPU oracle run on this host on the same inputs, N = 1 only: the objecti
 sign census) and the ITERATE after the oracle's timed step(s) (`parity.image_mse`, 0..255 units).  `worker_level` is the rate
 including one `Iterate` per step, which `value` excludes: D2H + pickle on one thread / with the sender thread / pipelined, and the
 worker's zero-copy form (the GPU copies the iterate into a pre-formatted pickle in pinned memory; the transport gets that buffer).
+
+--dump-outputs DIR writes, after the timed steps, the iterate of the last one as a caller of ``StyleTransfer.step()`` receives it
+(HxWx3 float32 RGB, unclipped) to DIR/image.npy; an image over DUMP_BYTES is written as a fixed seeded sample, DIR/image_sample.npy.
+The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 
 import argparse
@@ -58,6 +66,7 @@ WEIGHTS = {'content': {'conv4_2': 0.08},
 PARAMS = {'p': 50, 'p_power': 6, 'tv': 5, 'tv_power': 2}
 ITERS_PER_IMAGE = 500
 STEP_SIZES = {'adam': 10, 'lbfgs': 1}
+DUMP_BYTES = 48 << 20              # --dump-outputs: larger iterates are written as a sample of this many bytes
 
 
 def images(size):
@@ -112,6 +121,18 @@ def make_job(inputs, optimizer, device, precision='fp32', conv_algo=1):
     job.reset()
     assert job.start()
     return job
+
+
+def dump_outputs(job, out_dir):
+    """The current iterate as step() hands it out (deprocess of the device-resident x, the same float32 arithmetic as the
+    engine's deprocess kernel), to out_dir/image.npy, or a seeded sample of it when it is larger than DUMP_BYTES."""
+    image = np.ascontiguousarray(job.model.deprocess(job.input), np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    if image.nbytes <= DUMP_BYTES:
+        np.save(os.path.join(out_dir, 'image.npy'), image)
+    else:
+        idx = np.sort(np.random.RandomState(0).randint(0, image.size, DUMP_BYTES // 4))
+        np.save(os.path.join(out_dir, 'image_sample.npy'), image.reshape(-1)[idx])
 
 
 class StubJob:
@@ -504,7 +525,7 @@ def profiled_leg(job, steps):
 
 
 def extra_config_leg(label, inputs, optimizer, precision, steps, blocks, warmup, device, conv_algo=1):
-    """One more BASELINE config measured in the default run, reported under `extra_configs` (never `value`): the same
+    """One more BASELINE config measured in the --full run, reported under `extra_configs` (never `value`): the same
     timed-region contract (warm-up, then `blocks` blocks of exactly `steps` device-resident steps, median), plus the conv class's
     fraction of its MFMA peak from a short profiled leg."""
     from style_transfer2_amd import distributed as st2_dist
@@ -549,7 +570,7 @@ def extra_config_leg(label, inputs, optimizer, precision, steps, blocks, warmup,
 
 
 def extra_configs(args, device):
-    """BASELINE configs[2], [0] and (memory permitting) [4]-on-one-GPU as short legs of the default N = 1 run, so that the driver's one
+    """BASELINE configs[2], [0] and (memory permitting) [4]-on-one-GPU as short legs of the --full N = 1 run, so that one
     command sees every config; each failure is recorded as {'error': ...} and never disturbs the headline line."""
     out = {}
     t_all = time.perf_counter()
@@ -680,7 +701,13 @@ def main(argv=None):
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=30)
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--repeats', type=int, default=5, help='timed blocks of --steps steps (value = the median block)')
+    ap.add_argument('--repeats', type=int, default=None,
+                    help='timed blocks of --steps steps (value = the median block); default 1, with --full 5')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beyond the headline: 5 timed blocks, the profiled leg (roofline, per-kernel '
+                         'times), worker_level, the CPU oracle (cpu_baseline, parity) and the short legs of the other configs')
+    ap.add_argument('--dump-outputs', metavar='DIR', default='',
+                    help='after the timed steps, write the iterate of the last one to DIR/image.npy (float32; a seeded sample when large)')
     ap.add_argument('--size', type=int, default=1024)
     ap.add_argument('--optimizer', default='adam', choices=['adam', 'lbfgs'])
     ap.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'],
@@ -689,20 +716,24 @@ def main(argv=None):
                     help='st_set_conv_algo: 1 (default, the headline arithmetic) Winograd on the fp32 matrix cores, 0 direct kernel only, '
                          '2 Winograd with split operands on the bf16 matrix cores (fp32 results; reported as a custom workload)')
     ap.add_argument('--examples', action='store_true',
-                    help='BASELINE configs[0]: the example pair fitted to 256 px by jobs.resize_to_fit, noise init, 50 Adam iterations, CPU oracle beside it')
+                    help='BASELINE configs[0]: the example pair fitted to 256 px by jobs.resize_to_fit, noise init, 50 Adam iterations (with --full: CPU oracle beside it)')
     ap.add_argument('--examples-iters', type=int, default=EXAMPLES_ITERS, help=argparse.SUPPRESS)       # (the GPU test shortens the job)
     ap.add_argument('--tiled', default='', help='RxC: ONE image of --size tile-sharded over R*C GPUs (BASELINE configs[4])')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-worker-level', action='store_true')
-    ap.add_argument('--no-extra-configs', action='store_true', help='skip the short legs of BASELINE configs[2], [0] and [4]-on-one-GPU (default run, N = 1 only)')
+    ap.add_argument('--no-extra-configs', action='store_true', help='skip the short legs of BASELINE configs[2], [0] and [4]-on-one-GPU (--full run, N = 1 only)')
     ap.add_argument('--cpu-size', type=int, default=0, help='image size of the CPU sample (default: --size)')
     ap.add_argument('--engine', default='hip', choices=['hip', 'stub'], help=argparse.SUPPRESS)
     ap.add_argument('--rehearse-one-gpu', action='store_true',
                     help='every rank uses device 0 and the ranks meet over gloo (RCCL refuses two ranks on one device): checks the '
                          '--gpus fan-out on a one-GPU box; the ranks share the card, so the rate is NOT a measurement')
     args = ap.parse_args(argv)
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     if args.gpus < 1 or args.steps < 1 or args.repeats < 1:
         ap.error('--gpus, --steps and --repeats must be positive')
+    if args.dump_outputs and (args.tiled or args.engine == 'stub'):
+        ap.error('--dump-outputs needs the single-image HIP job (not --tiled, not the stub engine)')
 
     # ---- ranks: from the launcher, or started here (nothing above this line has touched the GPU)
     if 'WORLD_SIZE' not in os.environ:
@@ -749,7 +780,7 @@ def main(argv=None):
         inputs = job_inputs(args)
         job = make_job(inputs, args.optimizer, local_rank, args.precision, args.conv_algo)
         sync = job.engine.sync
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline and args.engine == 'hip'
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.engine == 'hip'
     cpu_size = args.cpu_size or args.size
     cpu_iters = args.examples_iters if args.examples else 2          # (two oracle iterations, timed one by one: a spread)
     dev_steps = cpu_iters + (1 if (args.optimizer == 'lbfgs' and cpu_iters == 1) else 0)      # (the oracle leg's untimed first L-BFGS step)
@@ -759,9 +790,11 @@ def main(argv=None):
     for r in range(args.repeats):
         blocks.append(st2_dist.timed_region(group, job.step_async, args.steps, args.warmup if r == 0 else 0, sync))
     elapsed = statistics.median(blocks)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(job, args.dump_outputs)
 
     prof, prof_steps = {}, 0
-    if args.engine == 'hip':
+    if args.full and args.engine == 'hip':
         # per-kernel-class HIP-event timing of the same steps (separate leg so `value` carries no event overhead)
         prof_steps = max(3, min(10, args.steps))
         prof = profiled_leg(job, prof_steps)
@@ -821,7 +854,7 @@ def main(argv=None):
             if split:                    # --conv-algo 2: the split kernel's launches against the bf16 peak; the line above is what stayed on the fp32 pipe
                 out['roofline_f32_pipe_rest'] = out['roofline']
                 out['roofline'] = split
-        if world == 1 and args.engine == 'hip' and not args.no_worker_level:
+        if args.full and world == 1 and args.engine == 'hip' and not args.no_worker_level:
             out['worker_level'] = worker_level(job, max(3, min(20, args.steps)))
         if want_cpu:
             cpu_inputs = inputs if cpu_size == args.size else images(cpu_size) + (WEIGHTS, PARAMS)
@@ -830,7 +863,7 @@ def main(argv=None):
             if args.examples:
                 out['config']['resize_to_fit_matches_reference_fixture'] = example_inputs()[3]
         default_headline = (args.size, args.optimizer, args.precision, args.conv_algo) == (1024, 'adam', 'fp32', 1) and not args.examples
-        if world == 1 and args.engine == 'hip' and default_headline and not args.no_extra_configs:
+        if args.full and world == 1 and args.engine == 'hip' and default_headline and not args.no_extra_configs:
             job.engine.close()                   # the headline job's HBM goes back before the other configs run
             out['extra_configs'] = extra_configs(args, local_rank)
         json_out.write(json.dumps(out) + '\n')

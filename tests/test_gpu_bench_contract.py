@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -24,7 +25,7 @@ def run_bench(*extra):
 
 
 def test_bench_line_has_the_contract_keys():
-    d = run_bench('--cpu-size', '64')
+    d = run_bench('--full', '--cpu-size', '64')
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
               'vs_baseline', 'dtype', 'data', 'config', 'roofline', 'cpu_baseline'):
         assert k in d, k
@@ -49,15 +50,36 @@ def test_bench_line_has_the_contract_keys():
     assert w['sync_iterate_it_s'] > 0 and w['async_iterate_it_s'] > 0 and w['iterate_MB'] == pytest.approx(256 * 256 * 3 * 4 / 1e6, rel=0.05)
 
 
+def test_plain_run_times_exactly_steps_and_dumps_the_iterate(tmp_path):
+    """Without --full: one block of exactly --steps timed steps and the headline keys only; --dump-outputs writes the iterate of
+    the last step, and a second run with the same arguments (same seeded inputs) writes the same iterate."""
+    dumps = []
+    for i in range(2):
+        out_dir = tmp_path / ('run%d' % i)
+        d = run_bench('--dump-outputs', str(out_dir))
+        assert d['steps'] == 4 and d['warmup'] == 2 and d['timing']['blocks'] == 1 and len(d['timing']['block_ms']) == 1
+        assert d['ms_per_step'] == pytest.approx(d['timing']['block_ms'][0] / 4, rel=1e-3)
+        assert abs(d['value'] - 1e3 / d['ms_per_step']) <= 1e-6 * d['value'] and d['unit'] == 'it/s' and d['dtype'] == 'f32'
+        for k in ('roofline', 'kernel_ms_per_step', 'worker_level', 'cpu_baseline', 'parity', 'extra_configs'):
+            assert k not in d, k
+        assert sorted(os.listdir(out_dir)) == ['image.npy']
+        img = np.load(out_dir / 'image.npy')
+        assert img.shape == (256, 256, 3) and img.dtype == np.float32 and np.isfinite(img).all()
+        dumps.append(img)
+    init = np.random.RandomState(3).randint(0, 256, (256, 256, 3)).astype(np.float32)      # bench.images(256)[2]
+    assert np.abs(dumps[0] - init).max() > 1                  # six Adam steps of size 10 moved it
+    assert np.abs(dumps[0] - dumps[1]).max() <= 1e-3
+
+
 def test_bench_parity_leg_at_the_benched_size():
-    d = run_bench('--size', '128', '--no-worker-level')
+    d = run_bench('--full', '--size', '128', '--no-worker-level')
     p = d['parity']
     assert p['loss_rel'] <= 1e-4 and p['grad_rel_l2'] <= 5e-3 and p['grad_cosine'] >= 0.9999
     assert p['relu_sign_flips'] <= 50 and p['activations'] > 1e6
 
 
 def test_bench_bf16_and_lbfgs_variants_run():
-    d = run_bench('--precision', 'bf16', '--optimizer', 'lbfgs', '--no-cpu-baseline', '--repeats', '2')
+    d = run_bench('--full', '--precision', 'bf16', '--optimizer', 'lbfgs', '--no-cpu-baseline', '--repeats', '2')
     assert 'bf16' in d['dtype'] and 'cpu_baseline' not in d and d['timing']['blocks'] == 2
     assert d['roofline']['peak'] == pytest.approx(2516.6)
 

@@ -121,7 +121,7 @@ def test_stylize_cli_and_bench_examples_mode(tmp_path):
     assert out.returncode == 0, out.stderr[-1500:]
     from PIL import Image
     assert Image.open(tmp_path / 'o.png').size == (128, 96)
-    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--examples', '--examples-iters', '8', '--steps', '10', '--warmup', '2', '--repeats', '2',
+    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--full', '--examples', '--examples-iters', '8', '--steps', '10', '--warmup', '2', '--repeats', '2',
                           '--no-worker-level'], capture_output=True, text=True, timeout=900, cwd=REPO)
     assert out.returncode == 0, out.stderr[-1500:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][-1])

@@ -120,11 +120,8 @@ def test_prototxt_roundtrip_and_refusals():
         prototxt.parse(no_relu)
 
 
-def test_prototxt_reader_on_the_reference_model_file():
-    """The reference's own models/vgg19.prototxt (present in the build container only) parses to the built-in VGG19."""
+def test_prototxt_reader_on_the_reference_model_file(golden_dir):
+    """The reference's own models/vgg19.prototxt (stored unmodified as tests/golden/vgg19.prototxt) parses to the built-in VGG19."""
     import os
     from style_transfer2_amd import prototxt
-    path = '/root/reference/models/vgg19.prototxt'
-    if not os.path.exists(path):
-        pytest.skip('the reference tree is not on this machine')
-    assert prototxt.read(path) == VGG19_TOPOLOGY
+    assert prototxt.read(os.path.join(golden_dir, 'vgg19.prototxt')) == VGG19_TOPOLOGY

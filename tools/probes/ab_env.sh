@@ -4,7 +4,7 @@
 for rep in 1 2; do
   for setting in "$@"; do
     echo "== $setting"
-    env $setting python bench.py --steps 20 --repeats 3 --no-cpu-baseline --no-worker-level --no-extra-configs $BENCH_ARGS 2>/dev/null | python -c "
+    env $setting python bench.py --full --steps 20 --repeats 3 --no-cpu-baseline --no-worker-level --no-extra-configs $BENCH_ARGS 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); k = d['kernel_ms_per_step']
 print('%.2f it/s  %.4f ms/step  ' % (d['value'], d['ms_per_step']) + '  '.join('%s %.4f' % (n, k[n]) for n in sorted(k)))"

@@ -3,7 +3,7 @@
 # Usage: tools/probes/gram_style_sweep.sh > gpurun_out/gram_style_sweep.txt
 run() {
   echo "== $1"
-  env $1 python bench.py --steps 20 --repeats 3 --no-cpu-baseline --no-worker-level --no-extra-configs 2>/dev/null | python -c "
+  env $1 python bench.py --full --steps 20 --repeats 3 --no-cpu-baseline --no-worker-level --no-extra-configs 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); k = d['kernel_ms_per_step']
 print('%.2f it/s  gram_partial %.4f  gram_reduce %.4f  style_grad %.4f  (ms per step)' % (d['value'], k['gram_partial_mfma_f32'], k['gram_reduce'], k['style_grad_mfma_f32']))"
