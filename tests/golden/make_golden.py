@@ -68,6 +68,27 @@ def golden_image_norms():
     save('image_norms.npz', **out)
 
 
+# (1b) tv_norm / p_norm at tiny and one-pixel-thin images (the sizes where a wrapped or clipped neighbour goes wrong) --------
+EDGE_NORM_SHAPES = (('1x1', (1, 3, 1, 1)), ('1x9', (1, 3, 1, 9)), ('9x1', (1, 3, 9, 1)), ('2x2', (1, 3, 2, 2)), ('1x257', (1, 3, 1, 257)))
+
+
+def golden_image_norms_edges():
+    out = {}
+    rng = np.random.RandomState(12)
+    for tag, shape in EDGE_NORM_SHAPES:
+        x = (rng.randn(*shape) * 50).astype(F32)
+        out['x_' + tag] = x
+        for beta in (2, 1.5):
+            v, g = ref_utils.tv_norm(x / 255, beta)
+            out['tv_%s_%s_value' % (tag, beta)] = np.asarray(v)
+            out['tv_%s_%s_grad' % (tag, beta)] = g
+        for p in (2, 6):
+            v, g = ref_utils.p_norm(x / 255, p)
+            out['p_%s_%s_value' % (tag, p)] = np.asarray(v)
+            out['p_%s_%s_grad' % (tag, p)] = g
+    save('image_norms_edges.npz', **out)
+
+
 # (2) gram_matrix ------------------------------------------------------------------------------
 def golden_gram():
     rng = np.random.RandomState(12)
@@ -277,6 +298,7 @@ def golden_config1_inputs():
 
 if __name__ == '__main__':
     golden_image_norms()
+    golden_image_norms_edges()
     golden_gram()
     golden_descent()
     golden_transfer()

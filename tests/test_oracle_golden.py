@@ -27,6 +27,21 @@ def test_tv_and_p_terms_match_reference():
             assert v == g['p_%s_%s_value' % (tag, p)]
 
 
+def test_tv_and_p_terms_match_reference_at_tiny_and_thin_sizes():
+    """The same pin at 1x1, 1x9, 9x1, 2x2 and 1x257: every neighbour of the TV term wraps (np.roll) or is the pixel itself."""
+    g = load('image_norms_edges.npz')
+    for tag in ('1x1', '1x9', '9x1', '2x2', '1x257'):
+        x = g['x_' + tag]
+        for beta in (2, 1.5):
+            v, grad = oracle.tv_term(x / 255, beta)
+            assert np.array_equal(grad, g['tv_%s_%s_grad' % (tag, beta)]), (tag, beta)
+            assert v == g['tv_%s_%s_value' % (tag, beta)], (tag, beta)
+        for p in (2, 6):
+            v, grad = oracle.p_term(x / 255, p)
+            assert np.array_equal(grad, g['p_%s_%s_grad' % (tag, p)]), (tag, p)
+            assert v == g['p_%s_%s_value' % (tag, p)], (tag, p)
+
+
 def test_gram_matches_reference():
     g = load('gram.npz')
     assert np.array_equal(oracle.gram(g['feat']), g['gram'])
