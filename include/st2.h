@@ -27,11 +27,13 @@ typedef struct st_ctx st_ctx;
 
 enum { ST_OK = 0, ST_ERR_ARG = 1, ST_ERR_STATE = 2, ST_ERR_HIP = 3 };
 enum { ST_OPT_NONE = 0, ST_OPT_ADAM = 1, ST_OPT_LBFGS = 2 };
-enum { ST_LAYER_CONV = 0, ST_LAYER_POOL = 1 };
+enum { ST_LAYER_CONV = 0, ST_LAYER_POOL = 1, ST_LAYER_AVEPOOL = 2 };
 
-/* One layer of a VGG-shaped topology: Conv3x3(pad 1)+ReLU, or MaxPool 2x2/2 (Caffe ceil mode). */
+/* One layer of a VGG-shaped topology: Conv3x3(pad 1)+ReLU (ST_LAYER_CONV), MaxPool 2x2/2 (ST_LAYER_POOL) or AvePool 2x2/2
+ * (ST_LAYER_AVEPOOL: Caffe `pool: AVE`, the divisor is the window clipped to the blob, 4, 2 or 1), both pools in Caffe ceil mode.
+ * st_create refuses any other kind with ST_ERR_ARG; tile-sharded mode (st_tile_configure) refuses a net with an average pool. */
 typedef struct st_layer_desc {
-    int kind;            /* ST_LAYER_CONV | ST_LAYER_POOL */
+    int kind;            /* ST_LAYER_CONV | ST_LAYER_POOL | ST_LAYER_AVEPOOL */
     const char* name;    /* blob/layer name, e.g. "conv1_1" */
     int cin, cout;       /* conv only */
 } st_layer_desc;

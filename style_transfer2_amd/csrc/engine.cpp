@@ -22,7 +22,7 @@ const char* const kProfNames[P_COUNT] = {"conv3x3_fwd_mfma_f32", "conv3x3_dgrad_
                                           "image_pass", "finalize", "vector_ops", "misc", "conv3x3_fwd_wino_f32", "conv3x3_dgrad_wino_f32",
                                           "conv3x3_fwd_mfma_bf16", "conv3x3_dgrad_mfma_bf16", "tile_comm",
                                           "gram_partial_mfma_bf16", "style_grad_mfma_bf16", "conv3x3_fwd_wino_split_bf16x6", "conv3x3_dgrad_wino_split_bf16x6",
-                                          "style_grad_fused_in_conv_dgrad_bf16"};
+                                          "style_grad_fused_in_conv_dgrad_bf16", "avepool_fwd", "avepool_bwd"};
 
 static const struct { int kind; const char* name; int cin, cout; } kVgg19[] = {
     {0, "conv1_1", 3, 64}, {0, "conv1_2", 64, 64}, {1, "pool1", 0, 0},
@@ -202,7 +202,8 @@ int forward_range(st_ctx* c, ActSet& a, const float* x, int last, bool lean)
                 double bytes = px * (2.0 * L.cin + 4.0 * L.cout + (next16 ? 2.0 * L.cout : 0.0));
                 if (lean && !blob_needs32(c, a, i) && i < last) {
                     const bool next_pool = !c->topo[i].is_conv;
-                    if (next_pool && !blob_active(c, i) && conv16_can_pool(p)) {       // (a weighted blob gets an injected diff: classic pool backward)
+                    // (a weighted blob gets an injected diff: classic pool backward; an average pool always runs stand-alone on the fp32 blob)
+                    if (next_pool && !c->topo[i].ave && !blob_active(c, i) && conv16_can_pool(p)) {
                         // the pool rides on this launch: pooled bf16 copy for the conv after it, arg-max map for the backward
                         const int pb = i + 1, pc = a.C[pb];
                         const size_t phw = (size_t)a.h[pb] * a.w[pb];
@@ -237,8 +238,9 @@ int forward_range(st_ctx* c, ActSet& a, const float* x, int last, bool lean)
                   ProfScope ps(c, wsplit ? P_CONV_FWD_WSPLIT : wino ? P_CONV_FWD_WINO : P_CONV_FWD, 2.0 * 9 * L.cin * L.cout * px, 4.0 * px * (L.cin + L.cout));
                   if (wino) {
                       p.wpack = wsplit ? reinterpret_cast<const float*>(L.us_fwd) : L.u_fwd; ST_TRY(wino_scratch(c, p, wsplit));
-                      // the max-pool that follows rides on this launch's epilogue (the pooled blob is written beside the conv blob)
-                      if (i < last && !c->topo[i].is_conv && !c->bf16 && (wsplit ? conv_wino_split_can_pool(p.K, p.M, p.H, p.W) : conv_wino_can_pool(p.K, p.M, p.H, p.W))) {
+                      // the max-pool that follows rides on this launch's epilogue (the pooled blob is written beside the conv blob);
+                      // an average pool does not (avepool_fwd reads the fp32 blob)
+                      if (i < last && !c->topo[i].is_conv && !c->topo[i].ave && !c->bf16 && (wsplit ? conv_wino_split_can_pool(p.K, p.M, p.H, p.W) : conv_wino_can_pool(p.K, p.M, p.H, p.W))) {
                           p.pool_out = a.data[i + 1]; pooled_by_conv = i + 1; a.has32[i + 1] = 1;
                           // ... and a one-byte arg-max map for the pool's backward (maxpool_bwd_amap_k: neither blob is read again)
                           const char* ae = getenv("ST2_POOL_AMAP");          // =0: the classic pool backward (read per forward: the tests compare both)
@@ -270,6 +272,19 @@ int forward_range(st_ctx* c, ActSet& a, const float* x, int last, bool lean)
             }
         } else if (i == pooled_by_conv) {
             // written by the producing conv's epilogue
+        } else if (L.ave) {
+            // average pool: stand-alone pass over the fp32 blob below, writing the fp32 pooled blob where something reads fp32
+            // (lean rules: a weighted blob, the last blob, a consumer that is not a bf16 conv) and the bf16 copy a bf16 conv reads
+            const int C = a.C[i - 1];
+            const size_t hw = (size_t)a.h[i] * a.w[i];
+            if (!a.has32[i - 1]) return fail(ST_ERR_STATE, "internal: the input blob of average pool %s is not materialised", L.name.c_str());
+            const bool feeds16 = c->bf16 && i < last && c->topo[i].is_conv && conv16_ok(c, C);
+            const bool want32 = !lean || !feeds16 || blob_active(c, i) || i == last;
+            if (feeds16 && !a.data16[i]) ST_TRY(dmalloc16(&a.data16[i], act16_elems(C, hw)));
+            a.has32[i] = want32;
+            const double n_in = (double)C * a.h[i - 1] * a.w[i - 1];
+            ProfScope ps(c, P_AVEPOOL_FWD, 0, 4.0 * n_in + (want32 ? 4.0 * C * hw : 0.0) + (feeds16 ? 2.0 * act16_elems(C, hw) : 0.0));
+            HIP_TRY(launch_avepool_fwd(a.data[i - 1], want32 ? a.data[i] : nullptr, feeds16 ? a.data16[i] : nullptr, C, a.h[i - 1], a.w[i - 1], c->stream));
         } else {
             const double n_in = (double)a.C[i - 1] * a.h[i - 1] * a.w[i - 1];
             a.has32[i] = 1;
@@ -426,6 +441,19 @@ int backward_chain(st_ctx* c, int top, const float* top_diff, const std::vector<
                 else HIP_TRY(launch_conv3x3(p, c->stream));
                 cur = dst;
             }
+        } else if (L.ave) {
+            // average pool: dx = mask(dy / window size) + inject in one pass; the bf16 copy for a bf16 dgrad conv below comes out of
+            // the same pass (no pack_act16), the fp32 diff where the consumer below reads fp32 (or every diff is materialised)
+            if (!cur) return fail(ST_ERR_STATE, "internal: fp32 diff missing above %s", L.name.c_str());
+            if (mask_src && !a.has32[below]) return fail(ST_ERR_STATE, "internal: pool input blob %d missing", below);
+            const bool to16 = c->bf16 && below >= 1 && conv_takes16(below);
+            const bool to32 = !(lean && to16);
+            const double n_in = (double)a.C[below] * a.h[below] * a.w[below];
+            ProfScope ps(c, P_AVEPOOL_BWD, 0, 4.0 * (double)a.C[below] * a.h[i] * a.w[i] +
+                         n_in * (4.0 * ((mask_src ? 1 : 0) + (inject ? 1 : 0) + (to32 ? 1 : 0)) + (to16 ? 2.0 : 0.0)));
+            HIP_TRY(launch_avepool_bwd(cur, mask_src, inject, to32 ? dst : nullptr, to16 ? dst16 : nullptr, a.C[below], a.h[below], a.w[below], c->stream));
+            cur16 = to16 ? dst16 : nullptr;
+            cur = to32 ? dst : nullptr;
         } else if (lean && a.amap_ok[i] && !inject && below >= 1 && conv_takes16(below)) {
             // pool fused into its producing conv: route the bf16 diff through the arg-max map (ReLU mask of the conv blob included)
             const int C = a.C[below];
@@ -613,7 +641,11 @@ int st_create(st_ctx** out, int device_id, const st_layer_desc* layers, int n_la
     } else {
         int cprev = 3;
         for (int i = 0; i < n_layers; ++i) {
-            Layer L; L.is_conv = layers[i].kind == ST_LAYER_CONV; L.name = layers[i].name ? layers[i].name : "";
+            const int kind = layers[i].kind;
+            if (kind != ST_LAYER_CONV && kind != ST_LAYER_POOL && kind != ST_LAYER_AVEPOOL) {
+                delete c; return fail(ST_ERR_ARG, "layer %d (%s): unknown kind %d", i, layers[i].name ? layers[i].name : "", kind);
+            }
+            Layer L; L.is_conv = kind == ST_LAYER_CONV; L.ave = kind == ST_LAYER_AVEPOOL; L.name = layers[i].name ? layers[i].name : "";
             if (L.is_conv) {
                 L.cin = layers[i].cin; L.cout = layers[i].cout;
                 if (L.cin != cprev || L.cout <= 0) { delete c; return fail(ST_ERR_ARG, "layer %s: cin %d does not follow %d", L.name.c_str(), L.cin, cprev); }

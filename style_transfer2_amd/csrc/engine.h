@@ -35,13 +35,15 @@ int fail(int code, const char* fmt, ...);
 // --------------------------------------------------------------------------------------- profiling
 enum ProfClass { P_CONV_FWD, P_CONV_DGRAD, P_POOL_FWD, P_POOL_BWD, P_GRAM, P_GRAM_REDUCE, P_STYLE_GRAD,
                  P_LAYER_ELEM, P_IMAGE_PASS, P_FINALIZE, P_VECTOR, P_MISC, P_CONV_FWD_WINO, P_CONV_DGRAD_WINO,
-                 P_CONV_FWD_BF16, P_CONV_DGRAD_BF16, P_COMM, P_GRAM_BF16, P_STYLE_GRAD_BF16, P_CONV_FWD_WSPLIT, P_CONV_DGRAD_WSPLIT, P_STYLE_FUSED_BF16, P_COUNT };
+                 P_CONV_FWD_BF16, P_CONV_DGRAD_BF16, P_COMM, P_GRAM_BF16, P_STYLE_GRAD_BF16, P_CONV_FWD_WSPLIT, P_CONV_DGRAD_WSPLIT, P_STYLE_FUSED_BF16,
+                 P_AVEPOOL_FWD, P_AVEPOOL_BWD, P_COUNT };
 extern const char* const kProfNames[P_COUNT];
 struct ProfRec { int cls; hipEvent_t a, b; double flops, bytes; };
 
 // ------------------------------------------------------------------------------------------- types
 struct Layer {
     bool is_conv = false;
+    bool ave = false;                                            // pool layer: average (ST_LAYER_AVEPOOL) instead of max pooling
     std::string name;
     int cin = 0, cout = 0;
     float *w_fwd = nullptr, *w_bwd = nullptr, *w_raw = nullptr, *w_raw_r = nullptr, *bias = nullptr;   // w_raw_r: w_raw rounded to bf16 values

@@ -85,6 +85,9 @@ extern "C" {
 int st_tile_configure(st_ctx* c, int gH, int gW, int wy0, int wx0, int ty0, int tx0, int ty1, int tx1)
 {
     if (c) c->epoch++;       // anything but st_step may change what a step launches: captured step graphs are stale
+    if (c)
+        for (const Layer& L : c->topo)
+            if (L.ave) return fail(ST_ERR_ARG, "tile-sharded mode does not run average pools (layer %s); use a single-context job", L.name.c_str());
     if (!c || !c->x[0]) return fail(ST_ERR_STATE, "set the window image first (st_set_input)");
     if (wy0 < 0 || wx0 < 0 || wy0 + c->H > gH || wx0 + c->W > gW || ty0 < wy0 || tx0 < wx0 ||
         ty1 > wy0 + c->H || tx1 > wx0 + c->W || ty1 <= ty0 || tx1 <= tx0)

@@ -3,6 +3,7 @@
 // reference's NumPy expressions (one IEEE operation per NumPy operation, same order).
 //
 //   max pool fwd/bwd            models/vgg19.prototxt:45-55 ...  (Caffe ceil mode, first max)
+//   average pool fwd/bwd        prototxt `pool: AVE`             (Caffe ceil mode, clipped-window divisor)
 //   content / deep-dream terms  worker.py:249-256, 271-277
 //   TV + p-norm + combine + Adam  utils.py:285-304, worker.py:279-297, optimizers.py:20-27
 //   pre / deprocess             worker.py:63-71
@@ -196,6 +197,215 @@ hipError_t launch_maxpool_bwd(const float* dy, const float* x, float* dx, const 
         return hipGetLastError();
     }
     maxpool_bwd_k<<<reduce_grid(total, 256, 65536), 256, 0, s>>>(dy, x, dx, inject, apply_mask, C, H, W, Ho, Wo);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------- average pool
+// Caffe PoolingLayer AVE, kernel 2, stride 2, pad 0 (ceil mode): top = (((0 + x00) + x01) + x10) + x11 over the in-image elements of
+// the window, divided by the clipped window size (4, 2 or 1 -- exactly a multiplication by 0.25, 0.5, 1; this file does not contract);
+// backward: every bottom element of a window receives top_diff / size.  A thread owns 8 channels (one channel block of the bf16
+// layout [ceil(C/8)][h*w][8] the bf16 convs read), so both outputs are written from registers; the bf16 copy is the fp32 result
+// rounded as pack_act16_k rounds it, channels beyond C are zero.
+typedef __bf16 ap_bf16x8 __attribute__((ext_vector_type(8)));
+
+__device__ __forceinline__ float ave_window_scale(int r0, int c0, int H, int W)
+{
+    const int n = (min(r0 + 2, H) - r0) * (min(c0 + 2, W) - c0);
+    return n == 4 ? 0.25f : n == 2 ? 0.5f : 1.0f;
+}
+
+// general build: one thread = one pooled pixel x 8 channels, windows clipped at the border
+__global__ __launch_bounds__(256) void avepool_fwd_k(const float* __restrict__ in, float* __restrict__ out,
+                                                     unsigned short* __restrict__ out16, int C, int H, int W, int Ho, int Wo)
+{
+    const size_t hwo = (size_t)Ho * Wo, total = (size_t)((C + 7) / 8) * hwo;
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+        const size_t p = idx % hwo, cb = idx / hwo;
+        const int py = (int)(p / Wo), px = (int)(p % Wo);
+        const int r0 = 2 * py, c0 = 2 * px;
+        const bool r1ok = r0 + 1 < H, c1ok = c0 + 1 < W;
+        const float scale = ave_window_scale(r0, c0, H, W);
+        ap_bf16x8 v;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int c = (int)cb * 8 + j;
+            float t = 0.f;
+            if (c < C) {
+                const float* q = in + (size_t)c * H * W + (size_t)r0 * W + c0;
+                t += q[0];
+                if (c1ok) t += q[1];
+                if (r1ok) t += q[W];
+                if (r1ok && c1ok) t += q[W + 1];
+                t = t * scale;
+                if (out) out[(size_t)c * hwo + p] = t;
+            }
+            v[j] = (__bf16)t;
+        }
+        if (out16) *reinterpret_cast<ap_bf16x8*>(out16 + idx * 8) = v;
+    }
+}
+
+// H even, W % 4 == 0 (every window full): one thread = two adjacent pooled pixels x 8 channels, 16-byte loads of the 2 x 4 input
+// patch per channel (256 bytes in flight per thread), 8-byte fp32 and 2 x 16-byte bf16 stores
+__global__ __launch_bounds__(256) void avepool_fwd_v4_k(const float* __restrict__ in, float* __restrict__ out,
+                                                        unsigned short* __restrict__ out16, int C, int W4, int Ho, size_t n_patches)
+{
+    const size_t rowp = (size_t)Ho * W4;                      // patches per channel plane
+    const size_t hw = (size_t)Ho * W4 * 8, hwo = (size_t)Ho * W4 * 2;
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < n_patches; idx += (size_t)gridDim.x * 256) {
+        const size_t pp = idx % rowp, cb = idx / rowp;
+        const size_t py = pp / W4, q = pp % W4;
+        float4 r0[8], r1[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int c = (int)cb * 8 + j;
+            if (c < C) {
+                const float* base = in + (size_t)c * hw + (2 * py) * (size_t)W4 * 4 + q * 4;
+                r0[j] = *reinterpret_cast<const float4*>(base);
+                r1[j] = *reinterpret_cast<const float4*>(base + (size_t)W4 * 4);
+            } else {
+                r0[j] = r1[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        }
+        ap_bf16x8 v0, v1;
+        const size_t po = py * (size_t)W4 * 2 + q * 2;        // first of the two pooled pixels in the plane
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int c = (int)cb * 8 + j;
+            float2 o;
+            o.x = ((((0.f + r0[j].x) + r0[j].y) + r1[j].x) + r1[j].y) * 0.25f;
+            o.y = ((((0.f + r0[j].z) + r0[j].w) + r1[j].z) + r1[j].w) * 0.25f;
+            if (c >= C) o = make_float2(0.f, 0.f);
+            else if (out) *reinterpret_cast<float2*>(out + (size_t)c * hwo + po) = o;
+            v0[j] = (__bf16)o.x; v1[j] = (__bf16)o.y;
+        }
+        if (out16) {
+            unsigned short* d = out16 + (cb * hwo + po) * 8;
+            *reinterpret_cast<ap_bf16x8*>(d) = v0;
+            *reinterpret_cast<ap_bf16x8*>(d + 8) = v1;
+        }
+    }
+}
+
+hipError_t launch_avepool_fwd(const float* in, float* out, unsigned short* out16, int C, int H, int W, hipStream_t s)
+{
+    if (!out && !out16) return hipErrorInvalidValue;
+    const int Ho = pooled_size(H), Wo = pooled_size(W);
+    const int CB = (C + 7) / 8;
+    if (H % 2 == 0 && W % 4 == 0) {
+        const size_t n_patches = (size_t)CB * Ho * (W / 4);
+        avepool_fwd_v4_k<<<reduce_grid(n_patches, 256, 65536), 256, 0, s>>>(in, out, out16, C, W / 4, Ho, n_patches);
+        return hipGetLastError();
+    }
+    const size_t total = (size_t)CB * Ho * Wo;
+    avepool_fwd_k<<<reduce_grid(total, 256, 65536), 256, 0, s>>>(in, out, out16, C, H, W, Ho, Wo);
+    return hipGetLastError();
+}
+
+// general build: one thread = one bottom pixel x 8 channels
+__global__ __launch_bounds__(256) void avepool_bwd_k(const float* __restrict__ dy, const float* __restrict__ x,
+                                                     const float* __restrict__ inject, float* __restrict__ dx,
+                                                     unsigned short* __restrict__ dx16, int C, int H, int W, int Ho, int Wo)
+{
+    const size_t hw = (size_t)H * W, hwo = (size_t)Ho * Wo, total = (size_t)((C + 7) / 8) * hw;
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+        const size_t p = idx % hw, cb = idx / hw;
+        const int r = (int)(p / W), col = (int)(p % W);
+        const int py = r >> 1, px = col >> 1;
+        const float scale = ave_window_scale(2 * py, 2 * px, H, W);
+        ap_bf16x8 v;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int c = (int)cb * 8 + j;
+            float t = 0.f;
+            if (c < C) {
+                const size_t o = (size_t)c * hw + p;
+                t = dy[(size_t)c * hwo + (size_t)py * Wo + px] * scale;
+                if (x) t = x[o] > 0.f ? t : 0.f;
+                if (inject) t += inject[o];
+                if (dx) dx[o] = t;
+            }
+            v[j] = (__bf16)t;
+        }
+        if (dx16) *reinterpret_cast<ap_bf16x8*>(dx16 + idx * 8) = v;
+    }
+}
+
+// H even, W % 4 == 0: one thread = a 2 x 4 bottom patch (two pooled pixels) x 8 channels, 16-byte loads / stores of the mask source,
+// the injected diff and the fp32 output; the bf16 copy goes out as eight 16-byte pixel vectors
+__global__ __launch_bounds__(256) void avepool_bwd_v4_k(const float* __restrict__ dy, const float* __restrict__ x,
+                                                        const float* __restrict__ inject, float* __restrict__ dx,
+                                                        unsigned short* __restrict__ dx16, int C, int W4, int Ho, size_t n_patches)
+{
+    const size_t rowp = (size_t)Ho * W4;
+    const size_t W = (size_t)W4 * 4, hw = (size_t)Ho * 2 * W, hwo = (size_t)Ho * W4 * 2;
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < n_patches; idx += (size_t)gridDim.x * 256) {
+        const size_t pp = idx % rowp, cb = idx / rowp;
+        const size_t py = pp / W4, q = pp % W4;
+        const size_t o0 = 2 * py * W + q * 4, o1 = o0 + W;          // in-plane offsets of the patch's two rows
+        const size_t po = py * (size_t)W4 * 2 + q * 2;
+        float4 d0[8], d1[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int c = (int)cb * 8 + j;
+            if (c < C) {
+                const size_t pl = (size_t)c * hw;
+                const float2 g = *reinterpret_cast<const float2*>(dy + (size_t)c * hwo + po);
+                const float gx = g.x * 0.25f, gy = g.y * 0.25f;
+                d0[j] = make_float4(gx, gx, gy, gy); d1[j] = d0[j];
+                if (x) {
+                    const float4 m0 = *reinterpret_cast<const float4*>(x + pl + o0);
+                    const float4 m1 = *reinterpret_cast<const float4*>(x + pl + o1);
+                    d0[j].x = m0.x > 0.f ? d0[j].x : 0.f; d0[j].y = m0.y > 0.f ? d0[j].y : 0.f;
+                    d0[j].z = m0.z > 0.f ? d0[j].z : 0.f; d0[j].w = m0.w > 0.f ? d0[j].w : 0.f;
+                    d1[j].x = m1.x > 0.f ? d1[j].x : 0.f; d1[j].y = m1.y > 0.f ? d1[j].y : 0.f;
+                    d1[j].z = m1.z > 0.f ? d1[j].z : 0.f; d1[j].w = m1.w > 0.f ? d1[j].w : 0.f;
+                }
+                if (inject) {
+                    const float4 i0 = *reinterpret_cast<const float4*>(inject + pl + o0);
+                    const float4 i1 = *reinterpret_cast<const float4*>(inject + pl + o1);
+                    d0[j].x += i0.x; d0[j].y += i0.y; d0[j].z += i0.z; d0[j].w += i0.w;
+                    d1[j].x += i1.x; d1[j].y += i1.y; d1[j].z += i1.z; d1[j].w += i1.w;
+                }
+                if (dx) {
+                    *reinterpret_cast<float4*>(dx + pl + o0) = d0[j];
+                    *reinterpret_cast<float4*>(dx + pl + o1) = d1[j];
+                }
+            } else {
+                d0[j] = d1[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        }
+        if (dx16) {
+            ap_bf16x8 v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                v[0][j] = (__bf16)d0[j].x; v[1][j] = (__bf16)d0[j].y; v[2][j] = (__bf16)d0[j].z; v[3][j] = (__bf16)d0[j].w;
+                v[4][j] = (__bf16)d1[j].x; v[5][j] = (__bf16)d1[j].y; v[6][j] = (__bf16)d1[j].z; v[7][j] = (__bf16)d1[j].w;
+            }
+            unsigned short* r0 = dx16 + (cb * hw + o0) * 8;
+            unsigned short* r1 = dx16 + (cb * hw + o1) * 8;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                *reinterpret_cast<ap_bf16x8*>(r0 + k * 8) = v[k];
+                *reinterpret_cast<ap_bf16x8*>(r1 + k * 8) = v[4 + k];
+            }
+        }
+    }
+}
+
+hipError_t launch_avepool_bwd(const float* dy, const float* x, const float* inject, float* dx, unsigned short* dx16,
+                              int C, int H, int W, hipStream_t s)
+{
+    if (!dx && !dx16) return hipErrorInvalidValue;
+    const int Ho = pooled_size(H), Wo = pooled_size(W);
+    const int CB = (C + 7) / 8;
+    if (H % 2 == 0 && W % 4 == 0) {
+        const size_t n_patches = (size_t)CB * Ho * (W / 4);
+        avepool_bwd_v4_k<<<reduce_grid(n_patches, 256, 65536), 256, 0, s>>>(dy, x, inject, dx, dx16, C, W / 4, Ho, n_patches);
+        return hipGetLastError();
+    }
+    const size_t total = (size_t)CB * H * W;
+    avepool_bwd_k<<<reduce_grid(total, 256, 65536), 256, 0, s>>>(dy, x, inject, dx, dx16, C, H, W, Ho, Wo);
     return hipGetLastError();
 }
 

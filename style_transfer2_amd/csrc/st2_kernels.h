@@ -159,6 +159,17 @@ hipError_t launch_maxpool_bwd(const float* dy, const float* x, float* dx, const 
                               int apply_mask, int C, int H, int W, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
+// average pool 2x2 stride 2, Caffe ceil mode (prototxt `pool: AVE`): divisor = the clipped window size (4, 2 or 1).
+// Either output may be null (not both): `out` fp32 [C][Ho][Wo], `out16` the bf16 channel-blocked copy [ceil(C/8)][Ho*Wo][8]
+// (pack_act16 of `out`, bit for bit).
+// ------------------------------------------------------------------------------------------
+hipError_t launch_avepool_fwd(const float* in, float* out, unsigned short* out16, int C, int H, int W, hipStream_t s);
+// dx = mask(dy[window] / size) + inject; x (nullable) is the pool INPUT blob, the ReLU mask source (x > 0); inject nullable;
+// dx fp32 [C][H][W] and / or dx16 its bf16 channel-blocked copy [ceil(C/8)][H*W][8]
+hipError_t launch_avepool_bwd(const float* dy, const float* x, const float* inject, float* dx, unsigned short* dx16,
+                              int C, int H, int W, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------
 // Gram matrix  G = F F^T / n  (F is [C][hw]) as split-K MFMA GEMM + deterministic slab reduce.
 // ------------------------------------------------------------------------------------------
 struct GramPlan { int bt, tiles, splits, kslab; size_t slab_floats; };

@@ -6,7 +6,7 @@ from ctypes import POINTER, byref, c_double, c_float, c_int, c_longlong, c_void_
 
 import numpy as np
 
-from . import capi
+from . import capi, prototxt
 from .capi import check
 
 F32 = np.float32
@@ -53,7 +53,8 @@ class Engine:
             for d, layer in zip(descs, self.topology):
                 name = layer[1].encode()
                 self._names.append(name)
-                d.kind = 0 if layer[0] == 'conv' else 1
+                # ST_LAYER_CONV / ST_LAYER_POOL / ST_LAYER_AVEPOOL ('pool', name, 'ave': prototxt `pool: AVE`)
+                d.kind = 0 if layer[0] == 'conv' else (2 if prototxt.pool_method(layer) == 'ave' else 1)
                 d.name = name
                 d.cin, d.cout = (layer[2], layer[3]) if layer[0] == 'conv' else (0, 0)
             check(self.lib.st_create(byref(self._ctx), int(device), descs, len(self.topology)))

@@ -1,9 +1,15 @@
 """Network definition files: the subset of Caffe's ``.prototxt`` text format the reference's model uses
 (reference config.ini:28 ``prototxt = models/vgg19.prototxt``; worker.py:58-61 ``caffe.Net(prototxt, 1, weights=...)``;
-models/vgg19.prototxt:1-337) turned into the engine's topology ``(('conv', name, cin, cout) | ('pool', name), ...)``.
+models/vgg19.prototxt:1-337) turned into the engine's topology
+``(('conv', name, cin, cout) | ('pool', name) | ('pool', name, 'ave'), ...)``.
 
 What the engine runs is what that file describes and nothing else: a chain of 3x3 / pad 1 / stride 1 convolutions, each
-followed by an in-place ReLU, and 2x2 / stride 2 MAX pools.  Any other layer, parameter value or wiring is an error here
+followed by an in-place ReLU, and 2x2 / stride 2 / pad 0 pools, ``pool: MAX`` (or ``0``, the default) or -- when the caller asks
+for them with ``average_pools=True``, as worker.py does -- ``pool: AVE`` (or ``1``; Caffe's average over the window clipped to the
+blob).  A max pool is ``('pool', name)`` -- the stock VGG19 stays engine.VGG19_TOPOLOGY -- and an average pool
+``('pool', name, 'ave')``.  Average pools are opt-in because not every consumer of a topology runs them (tile-sharded mode refuses
+them); a caller that has not asked gets the MAX-only subset it was written for.  Stochastic and global pooling, other kernel /
+stride / pad values and any other layer, parameter value or wiring are an error here
 (loudly, at worker start) rather than a silently different network.  ``write`` emits the same subset -- the tests build
 miniature networks with it; the stock VGG19 is built in (engine.VGG19_TOPOLOGY) and needs no file.
 """
@@ -67,9 +73,13 @@ def _one(msg, key, default=None):
     return vals[-1]
 
 
-def parse(text):
+# PoolingParameter.PoolMethod: MAX = 0, AVE = 1 (STOCHASTIC = 2 is refused)
+_POOL_METHODS = {'MAX': 'max', '0': 'max', 'AVE': 'ave', '1': 'ave'}
+
+
+def parse(text, average_pools=False):
     """Topology of a network definition.  The first layer must be the 3-channel ``Input``; blobs are chained top to
-    bottom; ReLUs must be in place on the convolution above them."""
+    bottom; ReLUs must be in place on the convolution above them.  ``average_pools``: accept ``pool: AVE`` (else only MAX pools)."""
     net, _ = _message(_tokens(text), 0, False)
     topo, cur, channels, relu_pending = [], None, None, None
     for layer in net.get('layer', []):
@@ -105,11 +115,20 @@ def parse(text):
             relu_pending = None
         elif kind == 'Pooling':
             p = _one(layer, 'pooling_param', {})
-            if (_one(p, 'pool', 'MAX'), int(_one(p, 'kernel_size', 0)), int(_one(p, 'stride', 1)), int(_one(p, 'pad', 0))) != ('MAX', 2, 2, 0):
-                raise ValueError('prototxt: %s is not a 2x2 / stride 2 MAX pool' % name)
+            method = _POOL_METHODS.get(str(_one(p, 'pool', 'MAX')))
+            if method is None:
+                raise ValueError('prototxt: pool %s: method %s is not supported (MAX or AVE)' % (name, _one(p, 'pool')))
+            if method == 'ave' and not average_pools:
+                raise ValueError('prototxt: %s is an AVE pool; this caller runs MAX pools only (parse / read with average_pools=True '
+                                 'accept Caffe average pooling)' % name)
+            if str(_one(p, 'global_pooling', 'false')).lower() not in ('false', '0'):
+                raise ValueError('prototxt: pool %s: global pooling is not supported' % name)
+            if (int(_one(p, 'kernel_size', 0)), int(_one(p, 'stride', 1)), int(_one(p, 'pad', 0))) != (2, 2, 0) or \
+                    any(k in p for k in ('kernel_h', 'kernel_w', 'stride_h', 'stride_w', 'pad_h', 'pad_w')):
+                raise ValueError('prototxt: %s is not a 2x2 / stride 2 / pad 0 %s pool' % (name, method.upper()))
             if tops != [name]:
                 raise ValueError('prototxt: pool %s must write a blob of its own name' % name)
-            topo.append(('pool', name))
+            topo.append(('pool', name) if method == 'max' else ('pool', name, 'ave'))
             cur = tops[0]
         else:
             raise ValueError('prototxt: layer type %s (%s) is not supported' % (kind, name))
@@ -120,9 +139,16 @@ def parse(text):
     return tuple(topo)
 
 
-def read(path):
+def pool_method(layer):
+    """'max' or 'ave' for a pool layer of a topology; ValueError for anything else."""
+    if layer[0] != 'pool' or len(layer) not in (2, 3) or (len(layer) == 3 and layer[2] != 'ave'):
+        raise ValueError('not a pool layer of a topology: %r' % (layer,))
+    return 'ave' if len(layer) == 3 else 'max'
+
+
+def read(path, average_pools=False):
     with open(path) as f:
-        return parse(f.read())
+        return parse(f.read(), average_pools)
 
 
 def write(topology, name='net'):
@@ -138,6 +164,6 @@ def write(topology, name='net'):
             out.append('layer {\n    bottom: "%s"\n    top: "%s"\n    name: "relu%s"\n    type: "ReLU"\n}' % (n, n, n[4:] if n.startswith('conv') else '_' + n))
         else:
             out.append('layer {\n    bottom: "%s"\n    top: "%s"\n    name: "%s"\n    type: "Pooling"\n    pooling_param {\n'
-                       '        pool: MAX\n        kernel_size: 2\n        stride: 2\n    }\n}' % (cur, n, n))
+                       '        pool: %s\n        kernel_size: 2\n        stride: 2\n    }\n}' % (cur, n, n, pool_method(layer).upper()))
         cur = n
     return '\n'.join(out) + '\n'

@@ -70,6 +70,9 @@ class TileGrid:
     """Geometry of an R x C tiling of a gH x gW image for a given topology / deepest weighted blob."""
 
     def __init__(self, gH, gW, rows, cols, topology, last_blob, apron=None):
+        if any(layer[0] == 'pool' and len(layer) > 2 for layer in topology):
+            raise ValueError('tile-sharded mode does not run average pools (%s)' %
+                             ', '.join(layer[1] for layer in topology if layer[0] == 'pool' and len(layer) > 2))
         self.gH, self.gW, self.rows, self.cols = gH, gW, rows, cols
         self.stride = total_stride(topology, last_blob)
         self.apron = receptive_apron(topology, last_blob) if apron is None else apron

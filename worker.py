@@ -77,12 +77,12 @@ def build_transfer(config):
         from style_transfer2_amd import weights as st2_weights
         gpu = config.getint('gpu', fallback=0)
         # the network definition (reference config.ini:28, worker.py:58-61): the stock VGG19 is built in, a prototxt that exists
-        # is read (and refused loudly if it asks for anything the engine does not run)
+        # is read, max and average pools alike (and refused loudly if it asks for anything the engine does not run)
         proto_path = MODULE_DIR / config.get('prototxt', 'models/vgg19.prototxt')
         topology = st2.VGG19_TOPOLOGY
         if proto_path.exists():
             from style_transfer2_amd import prototxt
-            topology = prototxt.read(str(proto_path))
+            topology = prototxt.read(str(proto_path), average_pools=True)
         weights_path = MODULE_DIR / config.get('caffemodel', 'models/vgg19.npz')
         if weights_path.suffix == '.npz' and weights_path.exists():
             params = st2_weights.load_npz(str(weights_path), topology)
