@@ -30,6 +30,7 @@ SOURCES = (
     ('conv3x3_dgrad_first.hip', ()),
     ('conv3x3_first_split.hip', ()),
     ('engine.cpp', ('-x', 'hip')),
+    ('engine_route.cpp', ('-x', 'hip')),
     ('engine_objective.cpp', ('-x', 'hip')),
     ('engine_step.cpp', ('-x', 'hip')),
     ('engine_resample.cpp', ('-x', 'hip')),

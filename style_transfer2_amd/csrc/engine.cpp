@@ -61,18 +61,6 @@ void dfree16(unsigned short*& p)
     if (p && hipFree(p) != hipSuccess) (void)hipGetLastError();
     p = nullptr;
 }
-// does the data gradient of conv layer L at this size run on the split-operand Winograd kernel?
-static bool dgrad_takes_split(const st_ctx* c, const Layer& L, int h, int w)
-{
-    if (!(c->wino && c->wino_split && !c->bf16 && L.us_bwd && conv_wino_split_ok(L.cout, L.cin, h, w))) return false;
-    // ST2_WS_DGRAD64=0: K <= 64 launches that the fp32 kernel could unpool (conv1_2's data gradient) stay on the fp32 matrix cores.  With
-    // the first split epilogue that was the faster route (404 + 60 us of maxpool_bwd_amap_k against 429 us); since the branch-free
-    // epilogue it is not (same-box A/B, profiles/r05_s_ab_split.txt: 177.4 against 176.1 it/s) -- kept as a switch for the A/B only
-    { const char* e = getenv("ST2_WS_DGRAD64");
-      if (e && *e == '0' && L.cout <= 64 && L.u_bwd && conv_wino_can_unpool(L.cout, L.cin, h, w)) return false; }
-    return true;
-}
-
 int wino_scratch(st_ctx* c, ConvProblem& p, bool split_kernel)
 {
     const int sp = split_kernel ? conv_wino_split_splits(p.K, p.M, p.H, p.W) : conv_wino_splits(p.K, p.M, p.H, p.W);
@@ -121,181 +109,114 @@ int act_ensure(st_ctx* c, ActSet& a, int H, int W)
     a.data.assign(c->nb, nullptr);
     a.data16.assign(c->nb, nullptr);
     a.amap.assign(c->nb, nullptr);
-    a.has32.assign(c->nb, 0);
-    a.amap_ok.assign(c->nb, 0);
     a.bits.assign(c->nb, nullptr);
-    a.bits_ok.assign(c->nb, 0);
+    a.plan.fwd.assign(c->nb, FwdRoute{});
+    a.plan.bwd.assign(c->nb, BwdRoute{});
     for (int i = 1; i < c->nb; ++i) ST_TRY(dmalloc(&a.data[i], (size_t)a.C[i] * a.h[i] * a.w[i]));
     a.H = H; a.W = W;
     return ST_OK;
 }
 
-bool blob_active(const st_ctx* c, int b)
+// the buffers of blob b beyond the fp32 one, made when a plan first names them
+static int ensure16(ActSet& a, int b)
 {
-    for (const ActiveLayer& al : c->active) if (al.blob == b) return true;
-    return false;
+    if (!a.data16[b]) ST_TRY(dmalloc16(&a.data16[b], act16_elems(a.C[b], (size_t)a.h[b] * a.w[b])));
+    return ST_OK;
+}
+static int ensure_amap(ActSet& a, int b)
+{
+    // (one size for both layouts: the buffer is shared when the precision is switched)
+    if (!a.amap[b]) HIP_TRY(hipMalloc((void**)&a.amap[b], act16_elems(a.C[b], (size_t)a.h[b] * a.w[b])));
+    return ST_OK;
+}
+static int pack16(st_ctx* c, const float* src, unsigned short* dst, int C, size_t hw)
+{
+    ProfScope ps(c, P_MISC, 0, hw * 6.0 * C);
+    HIP_TRY(launch_pack_act16(src, dst, C, hw, c->stream));
+    return ST_OK;
 }
 
-// Will the style term of blob b (a style layer) run entirely on the blob's bf16 copy (gram16.hip + style16.hip)?  Decided from
-// shapes only, so that the forward (which may then skip the fp32 blob) and the objective agree.
-bool style_runs16(const st_ctx* c, const ActSet& a, int b)
-{
-    if (!c->bf16 || b < 1 || !c->topo[b - 1].is_conv) return false;
-    const int C = a.C[b], hw = a.h[b] * a.w[b];
-    if (!(conv16_ok(c, C) && style_grad16_ok(C, (size_t)hw) && C % 8 == 0)) return false;
-    // tile-sharded mode: the region-of-interest forms of both kernels take any region (ragged last step, 4-byte stores when the
-    // region's rows are not 16-byte aligned); ST2_TILE_STYLE16=0 keeps the fp32 region-of-interest kernels
-    if (c->tile.on) { const char* e = getenv("ST2_TILE_STYLE16"); return !(e && *e == '0'); }
-    return hw % 64 == 0 && gram16_ok(C, hw, gram_plan16(C, hw));
-}
-
-// lean evaluation: does anything read blob b in fp32?  Content / deep-dream terms do (layer_elem_k); a style term only when
-// its Gram / gradient cannot run on the bf16 copy.
-bool blob_needs32(const st_ctx* c, const ActSet& a, int b)
-{
-    for (const ActiveLayer& al : c->active)
-        if (al.blob == b && (al.c || al.d || (al.s && !style_runs16(c, a, b)))) return true;
-    return false;
-}
-
-// May the style gradient of blob b ride on the data-gradient conv of the layer above it (conv3x3_mfma_bf16.hip, fused style term)?
-bool style_fuse_ok(const st_ctx* c, const ActSet& a, int b, int last)
-{
-    const char* e = getenv("ST2_STYLE_FUSE");           // read per evaluation: the tests compare both flows in one process
-    if ((e && *e == '0') || !style_runs16(c, a, b) || b + 1 > last || a.C[b] % 32 != 0) return false;
-    const Layer& up = c->topo[b];                       // layer b + 1: consumes blob b
-    return up.is_conv && up.loaded && conv16_ok(c, up.cout) && up.cin == a.C[b];
-}
-
-// `lean` (bf16 objective evaluations only): a conv blob whose only consumers are bf16 convs / a fused pool is not written
-// in fp32 at all, and a pool that follows such a conv is computed in that conv's epilogue (bf16 pooled copy + arg-max map).
+// Executes plan_forward's routes for layers 1 .. last (engine_route.cpp says what `lean` skips).  The profiler's figures: flops are
+// the ALGORITHMIC (direct-convolution) count in every conv class -- Winograd executes 4/9 of them, the split kernel 6 x 4/9 on the
+// bf16 pipe --, bytes what the launch reads and writes.
 int forward_range(st_ctx* c, ActSet& a, const float* x, int last, bool lean)
 {
     a.data[0] = const_cast<float*>(x);
-    a.has32.assign(c->nb, 0); a.amap_ok.assign(c->nb, 0); a.bits_ok.assign(c->nb, 0);
-    a.has32[0] = 1;
-    const char* be = getenv("ST2_MASK_BITS");          // =0: the data gradients mask with the bf16 copies (read per forward: the tests compare both)
-    const bool want_bits = lean && c->bf16 && !(be && *be == '0');
-    int pooled_by_conv = -1;
+    plan_forward(c, a, last, lean, a.plan.fwd);
+    const std::vector<FwdRoute>& plan = a.plan.fwd;
     for (int i = 1; i <= last; ++i) {
         const Layer& L = c->topo[i - 1];
-        if (L.is_conv) {
-            if (!L.loaded) return fail(ST_ERR_STATE, "weights of %s were never loaded", L.name.c_str());
-            const double px = (double)a.h[i] * a.w[i];
-            // does the layer that consumes blob i run on the bf16 matrix cores?
-            bool next16 = c->bf16 && i < last && c->topo[i].is_conv && conv16_ok(c, L.cout);
-            const bool conv_next16 = next16;
-            // ... or does the style gradient of this blob (bf16 path: style16.hip reads the bf16 copy)?
-            if (c->bf16 && conv16_ok(c, L.cout) && style_grad16_ok(L.cout, (size_t)a.h[i] * a.w[i]))
-                for (const ActiveLayer& al : c->active) if (al.blob == i && al.s) next16 = true;
-            if (next16 && !a.data16[i]) ST_TRY(dmalloc16(&a.data16[i], act16_elems(a.C[i], (size_t)a.h[i] * a.w[i])));
-            a.has32[i] = 1;
-            // lean: the data gradient of the bf16 conv above masks with blob i -- through a sign map (1 bit per element, written by
-            // this launch's epilogue) instead of the bf16 copy (16 bits)
-            const bool bits_i = want_bits && conv_next16 && L.cout % 32 == 0;
-            if (bits_i && !a.bits[i]) ST_TRY(dmalloc16(&a.bits[i], conv16_bits_elems(a.C[i], (size_t)a.h[i] * a.w[i])));
-            if (c->bf16 && conv16_ok(c, L.cin) && a.data16[i - 1]) {
-                Conv16Problem p{};
-                p.in16 = a.data16[i - 1]; p.wpack16 = L.w16_fwd; p.bias = L.bias; p.out = a.data[i];
-                p.out16 = next16 ? a.data16[i] : nullptr;
-                p.K = L.cin; p.M = L.cout; p.MPad = conv_mpad(L.cout); p.H = a.h[i]; p.W = a.w[i]; p.relu = 1;
-                double bytes = px * (2.0 * L.cin + 4.0 * L.cout + (next16 ? 2.0 * L.cout : 0.0));
-                if (lean && !blob_needs32(c, a, i) && i < last) {
-                    const bool next_pool = !c->topo[i].is_conv;
-                    // (a weighted blob gets an injected diff: classic pool backward; an average pool always runs stand-alone on the fp32 blob)
-                    if (next_pool && !c->topo[i].ave && !blob_active(c, i) && conv16_can_pool(p)) {
-                        // the pool rides on this launch: pooled bf16 copy for the conv after it, arg-max map for the backward
-                        const int pb = i + 1, pc = a.C[pb];
-                        const size_t phw = (size_t)a.h[pb] * a.w[pb];
-                        const bool pool_feeds16 = pb < last && c->topo[pb].is_conv && conv16_ok(c, pc);
-                        if (pool_feeds16 && !a.data16[pb]) ST_TRY(dmalloc16(&a.data16[pb], act16_elems(pc, phw)));
-                        if (!a.amap[pb]) HIP_TRY(hipMalloc((void**)&a.amap[pb], act16_elems(pc, phw)));
-                        p.pool16 = pool_feeds16 ? a.data16[pb] : nullptr;
-                        p.pool32 = (!pool_feeds16 || blob_active(c, pb) || pb == last) ? a.data[pb] : nullptr;
-                        p.amap = a.amap[pb];
-                        p.out = nullptr;
-                        a.has32[i] = 0; a.has32[pb] = p.pool32 != nullptr; a.amap_ok[pb] = 1;
-                        pooled_by_conv = pb;
-                        bytes = px * (2.0 * L.cin + 0.25 * L.cout * (1.0 + (pool_feeds16 ? 2.0 : 0.0) + (p.pool32 ? 4.0 : 0.0)));
-                    } else if (conv_next16) {
-                        p.out = nullptr;                   // the next conv reads the bf16 copy; the backward masks with it too
-                        a.has32[i] = 0;
-                        bytes = px * (2.0 * L.cin + 2.0 * L.cout);
-                    }
+        const FwdRoute& r = plan[i];
+        const FwdRoute& pool = plan[std::min(i + 1, c->nb - 1)];      // what the launch writes of the pooled blob (r.pools_next)
+        const int C = a.C[i], H = a.h[i], W = a.w[i];
+        const size_t hw = (size_t)H * W;
+        const double px = (double)hw, n_in = (double)a.C[i - 1] * a.h[i - 1] * a.w[i - 1];
+        if (L.is_conv && !L.loaded) return fail(ST_ERR_STATE, "weights of %s were never loaded", L.name.c_str());
+        if (r.out16) ST_TRY(ensure16(a, i));
+        if (r.bits && !a.bits[i]) ST_TRY(dmalloc16(&a.bits[i], conv16_bits_elems(C, hw)));
+        if (r.pools_next && pool.out16) ST_TRY(ensure16(a, i + 1));
+        if (r.pools_next && pool.amap != AMAP_NONE) ST_TRY(ensure_amap(a, i + 1));
+        const double conv_flops = 2.0 * 9 * L.cin * L.cout * px;
+        switch (r.kind) {
+        case F_CONV16: {
+            Conv16Problem p{};
+            p.in16 = a.data16[i - 1]; p.wpack16 = L.w16_fwd; p.bias = L.bias;
+            p.out = r.out32 ? a.data[i] : nullptr;
+            p.out16 = r.out16 ? a.data16[i] : nullptr;
+            p.bits_out = r.bits ? a.bits[i] : nullptr;
+            p.K = L.cin; p.M = L.cout; p.MPad = conv_mpad(L.cout); p.H = H; p.W = W; p.relu = 1;
+            double bytes = px * (2.0 * L.cin + (r.out32 ? 4.0 : 0.0) * L.cout + (r.out16 ? 2.0 : 0.0) * L.cout + (r.bits ? 0.125 : 0.0) * L.cout);
+            if (r.pools_next) {         // pooled bf16 copy for the conv after it, arg-max map for the backward
+                p.pool16 = pool.out16 ? a.data16[i + 1] : nullptr;
+                p.pool32 = pool.out32 ? a.data[i + 1] : nullptr;
+                p.amap = a.amap[i + 1];
+                bytes += px * 0.25 * L.cout * (1.0 + (pool.out16 ? 2.0 : 0.0) + (pool.out32 ? 4.0 : 0.0));
+            }
+            ProfScope ps(c, P_CONV_FWD_BF16, conv_flops, bytes);
+            HIP_TRY(launch_conv3x3_bf16(p, c->stream));
+            break;
+        }
+        case F_WINO: case F_WINO_SPLIT: case F_DIRECT: case F_FIRST_SPLIT: {
+            ConvProblem p{};
+            p.in = a.data[i - 1]; p.wpack = L.w_fwd; p.bias = L.bias;
+            p.out = r.out32 ? a.data[i] : nullptr;
+            p.K = L.cin; p.M = L.cout; p.MPad = conv_mpad(L.cout); p.H = H; p.W = W; p.relu = 1;
+            if (r.pools_next) { p.pool_out = a.data[i + 1]; p.pool_amap = pool.amap != AMAP_NONE ? a.amap[i + 1] : nullptr; }
+            if (r.out16 && !r.pack16) p.out16 = a.data16[i];           // the epilogue writes the bf16 copy too
+            {
+                ProfScope ps(c, r.kind == F_WINO_SPLIT ? P_CONV_FWD_WSPLIT : r.kind == F_WINO ? P_CONV_FWD_WINO : P_CONV_FWD, conv_flops,
+                             4.0 * px * (L.cin + L.cout));
+                if (r.kind == F_WINO_SPLIT) {
+                    p.wpack = reinterpret_cast<const float*>(L.us_fwd); ST_TRY(wino_scratch(c, p, true));
+                    HIP_TRY(launch_conv3x3_wino_split(p, c->stream));
+                } else if (r.kind == F_WINO) {
+                    p.wpack = L.u_fwd; ST_TRY(wino_scratch(c, p, false));
+                    HIP_TRY(launch_conv3x3_wino(p, c->stream));
+                } else if (r.kind == F_FIRST_SPLIT) {
+                    HIP_TRY(launch_conv3x3_first_split(p.in, L.w_split, p.out, p.out16, p.K, p.M, H, W, p.relu, c->stream, r.bits ? a.bits[i] : nullptr));
+                } else {
+                    HIP_TRY(launch_conv3x3(p, c->stream));
                 }
-                if (bits_i && p.out16) { p.bits_out = a.bits[i]; a.bits_ok[i] = 1; bytes += px * L.cout / 8.0; }
-                ProfScope ps(c, P_CONV_FWD_BF16, 2.0 * 9 * L.cin * L.cout * px, bytes);
-                HIP_TRY(launch_conv3x3_bf16(p, c->stream));
-            } else {
-                ConvProblem p{};
-                bool packed = false;
-                p.in = a.data[i - 1]; p.wpack = L.w_fwd; p.bias = L.bias; p.out = a.data[i];
-                p.K = L.cin; p.M = L.cout; p.MPad = conv_mpad(L.cout); p.H = a.h[i]; p.W = a.w[i]; p.relu = 1;
-                { const bool wino = c->wino && L.u_fwd && conv_wino_ok(p.K, p.M, p.H, p.W);
-                  // st_set_conv_algo(ctx, 2): the same products as six bf16 partial products of split operands where the shape allows
-                  const bool wsplit = wino && c->wino_split && !c->bf16 && L.us_fwd && conv_wino_split_ok(p.K, p.M, p.H, p.W);
-                  // flops are the ALGORITHMIC (direct-convolution) count in every class; Winograd executes 4/9 of them (the split kernel 6 x 4/9 on the bf16 pipe)
-                  ProfScope ps(c, wsplit ? P_CONV_FWD_WSPLIT : wino ? P_CONV_FWD_WINO : P_CONV_FWD, 2.0 * 9 * L.cin * L.cout * px, 4.0 * px * (L.cin + L.cout));
-                  if (wino) {
-                      p.wpack = wsplit ? reinterpret_cast<const float*>(L.us_fwd) : L.u_fwd; ST_TRY(wino_scratch(c, p, wsplit));
-                      // the max-pool that follows rides on this launch's epilogue (the pooled blob is written beside the conv blob);
-                      // an average pool does not (avepool_fwd reads the fp32 blob)
-                      if (i < last && !c->topo[i].is_conv && !c->topo[i].ave && !c->bf16 && (wsplit ? conv_wino_split_can_pool(p.K, p.M, p.H, p.W) : conv_wino_can_pool(p.K, p.M, p.H, p.W))) {
-                          p.pool_out = a.data[i + 1]; pooled_by_conv = i + 1; a.has32[i + 1] = 1;
-                          // ... and a one-byte arg-max map for the pool's backward (maxpool_bwd_amap_k: neither blob is read again)
-                          const char* ae = getenv("ST2_POOL_AMAP");          // =0: the classic pool backward (read per forward: the tests compare both)
-                          if (!(ae && *ae == '0') && (wsplit ? conv_wino_split_pool_amap_ok(p.K, p.M, p.H, p.W) : conv_wino_pool_amap_ok(p.K, p.M, p.H, p.W))) {
-                              // (sized like the bf16 path's map of the same blob: the buffer is shared when the precision is switched)
-                              const size_t pn = act16_elems(a.C[i + 1], (size_t)a.h[i + 1] * a.w[i + 1]);
-                              if (!a.amap[i + 1]) HIP_TRY(hipMalloc((void**)&a.amap[i + 1], pn));
-                              p.pool_amap = a.amap[i + 1]; a.amap_ok[i + 1] = 2;      // 2: the fp32 layout [C][ph][pw]
-                              // lean (inside an iteration): the full-resolution blob of a pooled, un-weighted layer is dead -- the next conv
-                              // reads the pooled blob, the pool's backward the arg-max map (with the ReLU sign in it) -- so it is not
-                              // written (conv1_2 at 1024^2: 268 MB and a quarter of the epilogue's instructions); same values everywhere else
-                              if (lean && !c->bf16 && !blob_active(c, i) && (wsplit ? conv_wino_split_can_skip_out(p.K, p.M, p.H, p.W) : conv_wino_can_skip_out(p.K, p.M, p.H, p.W))) { p.out = nullptr; a.has32[i] = 0; }
-                          }
-                      }
-                      if (wsplit) HIP_TRY(launch_conv3x3_wino_split(p, c->stream)); else
-                      HIP_TRY(launch_conv3x3_wino(p, c->stream));
-                  }
-                  else { if (next16 && L.cout % 8 == 0) { p.out16 = a.data16[i]; packed = true; }      // the epilogue writes the bf16 copy too
-                         // lean: conv1_1's fp32 blob is written only if something reads it (conv1_2, the ReLU mask and a style term take the copy)
-                         if (lean && packed && conv_next16 && i < last && !blob_needs32(c, a, i)) { p.out = nullptr; a.has32[i] = 0; }
-                         // bf16 path: the image keeps its fp32 precision (three-way bf16 split, six partial products on the bf16 matrix cores)
-                         if (c->bf16 && L.w_split && conv_first_split_ok(p.K, p.M, p.H, p.W)) {
-                             unsigned short* bits = (bits_i && p.out16) ? a.bits[i] : nullptr;
-                             HIP_TRY(launch_conv3x3_first_split(p.in, L.w_split, p.out, p.out16, p.K, p.M, p.H, p.W, p.relu, c->stream, bits));
-                             if (bits) a.bits_ok[i] = 1;
-                         }
-                         else HIP_TRY(launch_conv3x3(p, c->stream)); } }
-                if (next16 && !packed) { ProfScope ps(c, P_MISC, 0, px * 6.0 * L.cout); HIP_TRY(launch_pack_act16(a.data[i], a.data16[i], a.C[i], (size_t)a.h[i] * a.w[i], c->stream)); }
             }
-        } else if (i == pooled_by_conv) {
-            // written by the producing conv's epilogue
-        } else if (L.ave) {
-            // average pool: stand-alone pass over the fp32 blob below, writing the fp32 pooled blob where something reads fp32
-            // (lean rules: a weighted blob, the last blob, a consumer that is not a bf16 conv) and the bf16 copy a bf16 conv reads
-            const int C = a.C[i - 1];
-            const size_t hw = (size_t)a.h[i] * a.w[i];
-            if (!a.has32[i - 1]) return fail(ST_ERR_STATE, "internal: the input blob of average pool %s is not materialised", L.name.c_str());
-            const bool feeds16 = c->bf16 && i < last && c->topo[i].is_conv && conv16_ok(c, C);
-            const bool want32 = !lean || !feeds16 || blob_active(c, i) || i == last;
-            if (feeds16 && !a.data16[i]) ST_TRY(dmalloc16(&a.data16[i], act16_elems(C, hw)));
-            a.has32[i] = want32;
-            const double n_in = (double)C * a.h[i - 1] * a.w[i - 1];
-            ProfScope ps(c, P_AVEPOOL_FWD, 0, 4.0 * n_in + (want32 ? 4.0 * C * hw : 0.0) + (feeds16 ? 2.0 * act16_elems(C, hw) : 0.0));
-            HIP_TRY(launch_avepool_fwd(a.data[i - 1], want32 ? a.data[i] : nullptr, feeds16 ? a.data16[i] : nullptr, C, a.h[i - 1], a.w[i - 1], c->stream));
-        } else {
-            const double n_in = (double)a.C[i - 1] * a.h[i - 1] * a.w[i - 1];
-            a.has32[i] = 1;
+            if (r.pack16) ST_TRY(pack16(c, a.data[i], a.data16[i], C, hw));
+            break;
+        }
+        case F_BY_CONV_BELOW:
+            break;
+        case F_AVEPOOL: {
+            if (!plan[i - 1].out32) return fail(ST_ERR_STATE, "internal: the input blob of average pool %s is not materialised", L.name.c_str());
+            ProfScope ps(c, P_AVEPOOL_FWD, 0, 4.0 * n_in + (r.out32 ? 4.0 * C * hw : 0.0) + (r.out16 ? 2.0 * act16_elems(C, hw) : 0.0));
+            HIP_TRY(launch_avepool_fwd(a.data[i - 1], r.out32 ? a.data[i] : nullptr, r.out16 ? a.data16[i] : nullptr, C, a.h[i - 1], a.w[i - 1], c->stream));
+            break;
+        }
+        case F_MAXPOOL: {
             { ProfScope ps(c, P_POOL_FWD, 0, 4.0 * n_in * 1.25);
-              HIP_TRY(launch_maxpool_fwd(a.data[i - 1], a.data[i], a.C[i - 1], a.h[i - 1], a.w[i - 1], c->stream)); }
-            if (c->bf16 && i < last && c->topo[i].is_conv && conv16_ok(c, a.C[i])) {
-                const size_t hw = (size_t)a.h[i] * a.w[i];
-                if (!a.data16[i]) ST_TRY(dmalloc16(&a.data16[i], act16_elems(a.C[i], hw)));
-                ProfScope ps(c, P_MISC, 0, hw * 6.0 * a.C[i]);
-                HIP_TRY(launch_pack_act16(a.data[i], a.data16[i], a.C[i], hw, c->stream));
-            }
+              HIP_TRY(launch_maxpool_fwd(a.data[i - 1], a.data[i], C, a.h[i - 1], a.w[i - 1], c->stream)); }
+            if (r.pack16) ST_TRY(pack16(c, a.data[i], a.data16[i], C, hw));
+            break;
+        }
+        case F_NONE:
+            return fail(ST_ERR_STATE, "internal: no route for layer %s", L.name.c_str());
         }
     }
     a.valid_to = last;
@@ -339,168 +260,115 @@ int gram_into(st_ctx* c, const float* F, int C, int hw, const float* target, flo
     return ST_OK;
 }
 
-// backward chain from blob `top` whose diff is `cur` down to data; returns pointer in *out.
-// `lean` must be what the forward that filled c->act ran with: the fp32 diff of a layer is then written only when its
-// consumer needs fp32 (a pool without arg-max map, the 3-channel conv1_1 kernel, a non-bf16 conv), ReLU masks come from the
-// bf16 copies, and pools fused into their producing conv are back-propagated through their arg-max maps in bf16.
+// backward chain from blob `top` whose diff is `top_diff` down to data; returns pointer in *out.  Executes plan_backward's routes;
+// `lean` must be what the forward that filled c->act ran with.
 int backward_chain(st_ctx* c, int top, const float* top_diff, const std::vector<const float*>& inj, const float** out, bool lean)
 {
-    const ActSet& a = c->act;
+    ActSet& a = c->act;
+    plan_backward(c, a, top, inj, c->sf_w, lean, a.plan.bwd);
+    const std::vector<FwdRoute>& fwd = a.plan.fwd;
     const float* cur = top_diff;
     const unsigned short* cur16 = nullptr;             // bf16 copy of the running diff, when a producer already made it
-    const unsigned char* pending_unpool = nullptr;     // arg-max map of the pool just passed: `cur` is still the POOLED diff (Winograd unpool)
     if (c->bf16 && !c->diff16A) {
         const size_t cap = c->max_blob + 8 * (size_t)a.h[0] * a.w[0];
         ST_TRY(dmalloc16(&c->diff16A, cap)); ST_TRY(dmalloc16(&c->diff16B, cap));
     }
-    auto conv_takes16 = [&](int layer_index) {         // does conv layer `layer_index` (1-based blob index) read its diff as bf16?
-        const Layer& P = c->topo[layer_index - 1];
-        if (!P.is_conv || !conv16_ok(c, P.cout)) return false;
-        const bool first_small = conv_dgrad_smallM_ok(P.cout, P.cin) && !(layer_index - 1 >= 1 && c->topo[layer_index - 2].is_conv);
-        return !conv_dgrad_smallM_ok(P.cout, P.cin) || (first_small && P.w_raw_r != nullptr);
-    };
     for (int i = top; i >= 1; --i) {
         const Layer& L = c->topo[i - 1];
+        const BwdRoute& r = a.plan.bwd[i];
         const int below = i - 1;
+        const int Cb = a.C[below], Hb = a.h[below], Wb = a.w[below];          // the blob the diff is propagated to
+        const int H = a.h[i], W = a.w[i];
+        const size_t hw = (size_t)H * W;
+        const double px = (double)hw, n_below = (double)Cb * Hb * Wb;
         float* dst = (cur == c->diffA) ? c->diffB : c->diffA;
-        unsigned short* dst16 = (cur16 == c->diff16A) ? c->diff16B : c->diff16A;
-        const bool below_is_conv = below >= 1 && c->topo[below - 1].is_conv;
-        const float* mask_src = below_is_conv ? a.data[below] : nullptr;
         const float* inject = inj[below];
-        if (L.is_conv) {
-            const double px = (double)a.h[i] * a.w[i];
-            const bool small_m = !mask_src && conv_dgrad_smallM_ok(L.cout, L.cin);
-            if (small_m && pending_unpool) return fail(ST_ERR_STATE, "internal: an unpooling data gradient was planned for %s but the small-M kernel runs", L.name.c_str());
-            const bool wino_bwd = !small_m && !(c->bf16 && conv16_ok(c, L.cout)) && c->wino && L.u_bwd && conv_wino_ok(L.cout, L.cin, a.h[i], a.w[i]);
-            if (small_m && c->bf16 && L.w_raw_r) {
-                // bf16 feature path: this conv's operands are bf16 too -- the diff arrives as (or is packed into) a bf16 copy
-                const size_t hw = (size_t)a.h[i] * a.w[i];
-                if (!cur16) {
-                    if (!cur) return fail(ST_ERR_STATE, "internal: no diff above %s", L.name.c_str());
-                    ProfScope ps(c, P_MISC, 0, hw * 6.0 * L.cout);
-                    HIP_TRY(launch_pack_act16(cur, dst16, L.cout, hw, c->stream));
-                    cur16 = dst16;
-                }
-                ProfScope ps(c, P_CONV_DGRAD, 2.0 * 9 * L.cin * L.cout * px, px * (2.0 * L.cout + 4.0 * L.cin));
-                HIP_TRY(launch_conv3x3_dgrad_smallM16(cur16, L.w_raw_r, dst, inject, L.cout, L.cin, a.h[i], a.w[i], c->stream));
-                cur16 = nullptr; cur = dst;
-            } else if (small_m) {
-                if (!cur) return fail(ST_ERR_STATE, "internal: fp32 diff missing above %s", L.name.c_str());
-                ProfScope ps(c, P_CONV_DGRAD, 2.0 * 9 * L.cin * L.cout * px, 4.0 * px * (L.cin + L.cout));
-                HIP_TRY(launch_conv3x3_dgrad_smallM(cur, L.w_raw, dst, inject, L.cout, L.cin, a.h[i], a.w[i], c->stream));
-                cur16 = nullptr; cur = dst;
-            } else if (c->bf16 && conv16_ok(c, L.cout)) {
-                const size_t hw = (size_t)a.h[i] * a.w[i];
-                if (!cur16) {                                      // top diff / classic pool-backward output: make the bf16 copy
-                    if (!cur) return fail(ST_ERR_STATE, "internal: no diff above %s", L.name.c_str());
-                    unsigned short* tmp16 = dst16;
-                    ProfScope ps(c, P_MISC, 0, hw * 6.0 * L.cout);
-                    HIP_TRY(launch_pack_act16(cur, tmp16, L.cout, hw, c->stream));
-                    cur16 = tmp16;
-                    dst16 = (cur16 == c->diff16A) ? c->diff16B : c->diff16A;
-                }
-                // the consumer of this launch's output takes bf16 iff it is a bf16 dgrad conv, or (lean) a pool with an arg-max map
-                bool below16 = below >= 1 && conv_takes16(below);
-                if (lean && below >= 1 && !c->topo[below - 1].is_conv && a.amap_ok[below] && L.cin % 8 == 0) below16 = true;
-                Conv16Problem p{};
-                p.in16 = cur16; p.wpack16 = L.w16_bwd; p.bias = nullptr; p.out = dst; p.out16 = below16 ? dst16 : nullptr;
-                p.mask_src = mask_src; p.inject = inject;
-                if (lean && mask_src && a.data16[below]) { p.mask16 = a.data16[below]; p.mask_src = nullptr; }
-                const bool bits_below = lean && mask_src && a.bits_ok[below];
-                const bool fused = below >= 1 && (size_t)below < c->sf_w.size() && c->sf_w[below] != nullptr;
-                if (fused) {                // the style gradient of blob `below` rides on this launch: out = mask(conv) + D' @ F (+ inject)
-                    p.s_in16 = c->sf_in[below]; p.s_wpack16 = c->sf_w[below];
-                    if (mask_src) { p.mask16 = a.data16[below]; p.mask_src = nullptr; }      // the mask is applied in registers, from the bf16 copy
-                }
-                if (bits_below) { p.mask_bits = a.bits[below]; p.mask16 = nullptr; p.mask_src = nullptr; }      // ... or from the blob's sign map
-                if (p.mask_src && !a.has32[below]) return fail(ST_ERR_STATE, "internal: mask blob %d missing", below);
-                if (lean && below16) p.out = nullptr;
-                p.K = L.cout; p.M = L.cin; p.MPad = conv_mpad(L.cin); p.H = a.h[i]; p.W = a.w[i]; p.relu = 0;
-                p.unpool_amap = pending_unpool; pending_unpool = nullptr;      // cur16 is the POOLED diff then (3/4 byte per pooled channel value more, 1.5 less per full one)
-                if (fused) prof_note(c, P_STYLE_FUSED_BF16, 2.0 * L.cin * L.cin * px);      // (extra K chunks of the launch below; its own flops stay SURVEY 8(d)'s)
-                ProfScope ps(c, P_CONV_DGRAD_BF16, 2.0 * 9 * L.cin * L.cout * px,
-                             px * ((p.unpool_amap ? 0.75 : 2.0) * L.cout + (fused ? 2.0 : 0.0) * L.cin + (p.out ? 4.0 : 0.0) * L.cin + (p.out16 ? 2.0 : 0.0) * L.cin + (mask_src ? (p.mask_bits ? 0.125 : p.mask16 ? 2.0 : 4.0) : 0.0) * L.cin));
-                HIP_TRY(launch_conv3x3_bf16(p, c->stream));
-                cur16 = below16 ? dst16 : nullptr;
-                cur = p.out ? dst : nullptr;
-            } else {
-                if (!cur) return fail(ST_ERR_STATE, "internal: fp32 diff missing above %s", L.name.c_str());
-                cur16 = nullptr;
-                ConvProblem p{};
-                p.in = cur; p.wpack = L.w_bwd; p.bias = nullptr; p.out = dst;
-                p.mask_src = mask_src; p.inject = inject;
-                p.K = L.cout; p.M = L.cin; p.MPad = conv_mpad(L.cin); p.H = a.h[i]; p.W = a.w[i]; p.relu = 0;
-                if (pending_unpool && !wino_bwd) return fail(ST_ERR_STATE, "internal: an unpooling data gradient was planned for %s but the direct kernel runs", L.name.c_str());
-                p.unpool_amap = pending_unpool; pending_unpool = nullptr;
-                const bool wsplit = wino_bwd && dgrad_takes_split(c, L, a.h[i], a.w[i]);
-                if (wsplit && p.unpool_amap) return fail(ST_ERR_STATE, "internal: an unpooling data gradient was planned for %s but the split-operand kernel runs", L.name.c_str());
-                ProfScope ps(c, wsplit ? P_CONV_DGRAD_WSPLIT : wino_bwd ? P_CONV_DGRAD_WINO : P_CONV_DGRAD, 2.0 * 9 * L.cin * L.cout * px,
-                             4.0 * px * (L.cin + (p.unpool_amap ? 0.3125 : 1.0) * L.cout));
-                if (wsplit) { p.wpack = reinterpret_cast<const float*>(L.us_bwd); ST_TRY(wino_scratch(c, p, true)); HIP_TRY(launch_conv3x3_wino_split(p, c->stream)); }
-                else if (wino_bwd) { p.wpack = L.u_bwd; ST_TRY(wino_scratch(c, p, false)); HIP_TRY(launch_conv3x3_wino(p, c->stream)); }
-                else HIP_TRY(launch_conv3x3(p, c->stream));
-                cur = dst;
-            }
-        } else if (L.ave) {
-            // average pool: dx = mask(dy / window size) + inject in one pass; the bf16 copy for a bf16 dgrad conv below comes out of
-            // the same pass (no pack_act16), the fp32 diff where the consumer below reads fp32 (or every diff is materialised)
-            if (!cur) return fail(ST_ERR_STATE, "internal: fp32 diff missing above %s", L.name.c_str());
-            if (mask_src && !a.has32[below]) return fail(ST_ERR_STATE, "internal: pool input blob %d missing", below);
-            const bool to16 = c->bf16 && below >= 1 && conv_takes16(below);
-            const bool to32 = !(lean && to16);
-            const double n_in = (double)a.C[below] * a.h[below] * a.w[below];
-            ProfScope ps(c, P_AVEPOOL_BWD, 0, 4.0 * (double)a.C[below] * a.h[i] * a.w[i] +
-                         n_in * (4.0 * ((mask_src ? 1 : 0) + (inject ? 1 : 0) + (to32 ? 1 : 0)) + (to16 ? 2.0 : 0.0)));
-            HIP_TRY(launch_avepool_bwd(cur, mask_src, inject, to32 ? dst : nullptr, to16 ? dst16 : nullptr, a.C[below], a.h[below], a.w[below], c->stream));
-            cur16 = to16 ? dst16 : nullptr;
-            cur = to32 ? dst : nullptr;
-        } else if (lean && a.amap_ok[i] && !inject && below >= 1 && conv_takes16(below)) {
-            // pool fused into its producing conv: route the bf16 diff through the arg-max map (ReLU mask of the conv blob included)
-            const int C = a.C[below];
-            const size_t hw_top = (size_t)a.h[i] * a.w[i], hw = (size_t)a.h[below] * a.w[below];
-            if (!cur16) {
-                if (!cur) return fail(ST_ERR_STATE, "internal: no diff above %s", L.name.c_str());
-                unsigned short* tmp16 = dst16;
-                ProfScope ps(c, P_MISC, 0, hw_top * 6.0 * C);
-                HIP_TRY(launch_pack_act16(cur, tmp16, C, hw_top, c->stream));
-                cur16 = tmp16;
-                dst16 = (cur16 == c->diff16A) ? c->diff16B : c->diff16A;
-            }
-            {   // ... inside the data gradient of the conv below when it has the build (conv16_body, UNPOOL): it stages the pooled diff and
-                // expands it in LDS through the map (maxpool_bwd_idx16_k, its full-resolution output and the conv's read of it are gone)
-                const Layer& P = c->topo[below - 1];
-                Conv16Problem q{};
-                q.K = P.cout; q.M = P.cin; q.MPad = conv_mpad(P.cin); q.H = a.h[below]; q.W = a.w[below];
-                if (conv16_ok(c, P.cout) && !conv_dgrad_smallM_ok(P.cout, P.cin) && conv16_can_unpool(q)) { pending_unpool = a.amap[i]; continue; }
-            }
-            ProfScope ps(c, P_POOL_BWD, 0, (double)C * (hw_top * 3.0 + hw * 2.0));
-            HIP_TRY(launch_maxpool_bwd_idx16(cur16, a.amap[i], dst16, C, a.h[below], a.w[below], c->stream));
-            cur16 = dst16; cur = nullptr;
-        } else if (a.amap_ok[i] == 2 && !inject && mask_src && cur) {
-            // pool fused into its producing Winograd conv (fp32): route the diff through the arg-max map, ReLU mask included ...
-            const Layer& P = c->topo[below - 1];             // the conv that produced the pooled-from blob: its data gradient runs next
-            const bool p_wino = !c->bf16 && c->wino && P.u_bwd && !(below - 1 < 1 && conv_dgrad_smallM_ok(P.cout, P.cin)) &&
-                                conv_wino_ok(P.cout, P.cin, a.h[below], a.w[below]);
-            // (the split-operand kernel has no unpooling input transform: its launches keep maxpool_bwd_amap_k)
-            if (p_wino && !dgrad_takes_split(c, P, a.h[below], a.w[below]) && conv_wino_can_unpool(P.cout, P.cin, a.h[below], a.w[below])) {
-                // ... inside that data gradient: it stages the pooled diff and the map and unpools in its input transform
-                // (maxpool_bwd_amap_k, its full-resolution output and the conv's read of it are gone; same values bit for bit)
-                pending_unpool = a.amap[i];
-                continue;
-            }
-            ProfScope ps(c, P_POOL_BWD, 0, (double)a.C[below] * ((double)a.h[i] * a.w[i] * 5.0 + (double)a.h[below] * a.w[below] * 4.0));
-            HIP_TRY(launch_maxpool_bwd_amap(cur, a.amap[i], dst, a.C[below], a.h[below], a.w[below], c->stream));
-            cur16 = nullptr; cur = dst;
-        } else {
-            if (!cur) return fail(ST_ERR_STATE, "internal: fp32 diff missing above %s", L.name.c_str());
-            if (!a.has32[below]) return fail(ST_ERR_STATE, "internal: pool input blob %d missing", below);
-            const double n_in = (double)a.C[below] * a.h[below] * a.w[below];
-            ProfScope ps(c, P_POOL_BWD, 0, 4.0 * n_in * 2.25);
-            HIP_TRY(launch_maxpool_bwd(cur, a.data[below], dst, inject, mask_src != nullptr, a.C[below], a.h[below], a.w[below], c->stream));
-            cur16 = nullptr; cur = dst;
+        if (r.in16 ? !(cur16 || cur) : !cur) return fail(ST_ERR_STATE, "internal: no %s diff above %s", r.in16 ? "bf16 or fp32" : "fp32", L.name.c_str());
+        if (r.pack_in16) {                                 // top diff / fp32 producer: make the bf16 copy of the running diff
+            unsigned short* tmp16 = (cur16 == c->diff16A) ? c->diff16B : c->diff16A;
+            ST_TRY(pack16(c, cur, tmp16, a.C[i], hw));
+            cur16 = tmp16;
         }
+        unsigned short* dst16 = (cur16 == c->diff16A) ? c->diff16B : c->diff16A;
+        if ((r.mask == MASK_F32 || r.kind == B_POOL_CLASSIC) && !fwd[below].out32)
+            return fail(ST_ERR_STATE, "internal: blob %d, which the backward of %s reads, is not materialised in fp32", below, L.name.c_str());
+        // conv: the diff above is still the POOLED one, expanded through the map of the max pool above (r.unpool)
+        const unsigned char* unpool_amap = r.unpool ? a.amap[i + 1] : nullptr;
+        const double conv_flops = 2.0 * 9 * L.cin * L.cout * px;
+        switch (r.kind) {
+        case B_SMALLM16: {
+            // bf16 feature path: this conv's operands are bf16 too
+            ProfScope ps(c, P_CONV_DGRAD, conv_flops, px * (2.0 * L.cout + 4.0 * L.cin));
+            HIP_TRY(launch_conv3x3_dgrad_smallM16(cur16, L.w_raw_r, dst, inject, L.cout, L.cin, H, W, c->stream));
+            break;
+        }
+        case B_SMALLM: {
+            ProfScope ps(c, P_CONV_DGRAD, conv_flops, 4.0 * px * (L.cin + L.cout));
+            HIP_TRY(launch_conv3x3_dgrad_smallM(cur, L.w_raw, dst, inject, L.cout, L.cin, H, W, c->stream));
+            break;
+        }
+        case B_CONV16: {
+            Conv16Problem p{};
+            p.in16 = cur16; p.wpack16 = L.w16_bwd; p.bias = nullptr;
+            p.out = r.out32 ? dst : nullptr; p.out16 = r.out16 ? dst16 : nullptr;
+            p.inject = inject;
+            if (r.mask == MASK_F32) p.mask_src = a.data[below];
+            if (r.mask == MASK_BF16) p.mask16 = a.data16[below];
+            if (r.mask == MASK_BITS) p.mask_bits = a.bits[below];
+            if (r.style) {              // the style gradient of blob `below` rides on this launch: out = mask(conv) + D' @ F (+ inject)
+                p.s_in16 = c->sf_in[below]; p.s_wpack16 = c->sf_w[below];
+                prof_note(c, P_STYLE_FUSED_BF16, 2.0 * L.cin * L.cin * px);      // (extra K chunks of the launch below; its own flops stay SURVEY 8(d)'s)
+            }
+            p.K = L.cout; p.M = L.cin; p.MPad = conv_mpad(L.cin); p.H = H; p.W = W; p.relu = 0;
+            p.unpool_amap = unpool_amap;               // (3/4 byte per pooled channel value more, 1.5 less per full one)
+            const double mask_bytes = r.mask == MASK_BITS ? 0.125 : r.mask == MASK_BF16 ? 2.0 : r.mask == MASK_F32 ? 4.0 : 0.0;
+            ProfScope ps(c, P_CONV_DGRAD_BF16, conv_flops,
+                         px * ((r.unpool ? 0.75 : 2.0) * L.cout + (r.style ? 2.0 : 0.0) * L.cin + (r.out32 ? 4.0 : 0.0) * L.cin + (r.out16 ? 2.0 : 0.0) * L.cin + mask_bytes * L.cin));
+            HIP_TRY(launch_conv3x3_bf16(p, c->stream));
+            break;
+        }
+        case B_WINO: case B_WINO_SPLIT: case B_DIRECT: {
+            ConvProblem p{};
+            p.in = cur; p.wpack = L.w_bwd; p.bias = nullptr; p.out = dst;
+            p.mask_src = r.mask == MASK_F32 ? a.data[below] : nullptr; p.inject = inject;
+            p.K = L.cout; p.M = L.cin; p.MPad = conv_mpad(L.cin); p.H = H; p.W = W; p.relu = 0;
+            p.unpool_amap = unpool_amap;
+            ProfScope ps(c, r.kind == B_WINO_SPLIT ? P_CONV_DGRAD_WSPLIT : r.kind == B_WINO ? P_CONV_DGRAD_WINO : P_CONV_DGRAD, conv_flops,
+                         4.0 * px * (L.cin + (r.unpool ? 0.3125 : 1.0) * L.cout));
+            if (r.kind == B_WINO_SPLIT) { p.wpack = reinterpret_cast<const float*>(L.us_bwd); ST_TRY(wino_scratch(c, p, true)); HIP_TRY(launch_conv3x3_wino_split(p, c->stream)); }
+            else if (r.kind == B_WINO) { p.wpack = L.u_bwd; ST_TRY(wino_scratch(c, p, false)); HIP_TRY(launch_conv3x3_wino(p, c->stream)); }
+            else HIP_TRY(launch_conv3x3(p, c->stream));
+            break;
+        }
+        case B_AVEPOOL: {
+            ProfScope ps(c, P_AVEPOOL_BWD, 0, 4.0 * (double)Cb * H * W +
+                         n_below * (4.0 * ((r.mask != MASK_NONE ? 1 : 0) + (inject ? 1 : 0) + (r.out32 ? 1 : 0)) + (r.out16 ? 2.0 : 0.0)));
+            HIP_TRY(launch_avepool_bwd(cur, r.mask != MASK_NONE ? a.data[below] : nullptr, inject, r.out32 ? dst : nullptr, r.out16 ? dst16 : nullptr, Cb, Hb, Wb, c->stream));
+            break;
+        }
+        case B_POOL_IDX16: {
+            ProfScope ps(c, P_POOL_BWD, 0, (double)Cb * (hw * 3.0 + (size_t)Hb * Wb * 2.0));
+            HIP_TRY(launch_maxpool_bwd_idx16(cur16, a.amap[i], dst16, Cb, Hb, Wb, c->stream));
+            break;
+        }
+        case B_POOL_AMAP: {
+            ProfScope ps(c, P_POOL_BWD, 0, (double)Cb * (px * 5.0 + (double)Hb * Wb * 4.0));
+            HIP_TRY(launch_maxpool_bwd_amap(cur, a.amap[i], dst, Cb, Hb, Wb, c->stream));
+            break;
+        }
+        case B_POOL_CLASSIC: {
+            ProfScope ps(c, P_POOL_BWD, 0, 4.0 * n_below * 2.25);
+            HIP_TRY(launch_maxpool_bwd(cur, a.data[below], dst, inject, r.mask != MASK_NONE, Cb, Hb, Wb, c->stream));
+            break;
+        }
+        case B_IN_DGRAD_BELOW:
+            continue;                                      // the running diff stays the pooled one: the next launch expands it
+        case B_NONE:
+            return fail(ST_ERR_STATE, "internal: no route for the backward of layer %s", L.name.c_str());
+        }
+        cur = r.out32 ? dst : nullptr;
+        cur16 = r.out16 ? dst16 : nullptr;
     }
-    if (pending_unpool) return fail(ST_ERR_STATE, "internal: a pooled diff was left un-expanded");
     if (!cur) return fail(ST_ERR_STATE, "internal: the backward chain ended without an fp32 image gradient");
     *out = cur;
     return ST_OK;
@@ -877,7 +745,7 @@ int st_get_blob(st_ctx* c, int index, float* out)
 {
     if (!c || index < 0 || index >= c->nb || !out) return fail(ST_ERR_ARG, "bad argument");
     if (index > c->act.valid_to) return fail(ST_ERR_STATE, "blob %d was not computed by the last forward", index);
-    if (!c->act.has32[index]) return fail(ST_ERR_STATE, "blob %d (%s) is not materialised in fp32 by the lean evaluation of an iteration (st_opfunc / st_forward write every fp32 blob; bf16: st_set_precision(ctx, 2))", index, c->blob_names[index].c_str());
+    if (!c->act.plan.fwd[index].out32) return fail(ST_ERR_STATE, "blob %d (%s) is not materialised in fp32 by the lean evaluation of an iteration (st_opfunc / st_forward write every fp32 blob; bf16: st_set_precision(ctx, 2))", index, c->blob_names[index].c_str());
     const size_t n = (size_t)c->act.C[index] * c->act.h[index] * c->act.w[index];
     HIP_TRY(hipMemcpy(out, c->act.data[index], n * sizeof(float), hipMemcpyDeviceToHost));
     return ST_OK;

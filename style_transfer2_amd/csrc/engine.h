@@ -54,15 +54,47 @@ struct Layer {
     bool loaded = false;
 };
 
+// ------------------------------------------------------------------------------------- route plan
+// What every layer of one evaluation does, decided before the first launch (engine_route.cpp); forward_range and
+// backward_chain only execute it.  Entry i describes layer i (topo[i - 1]) and the blob it produces; entry 0 is the image.
+enum FwdKind : unsigned char { F_NONE, F_CONV16, F_WINO, F_WINO_SPLIT, F_DIRECT, F_FIRST_SPLIT, F_MAXPOOL, F_AVEPOOL,
+                               F_BY_CONV_BELOW };          // F_BY_CONV_BELOW: a max pool written by the epilogue of the conv below it
+enum AmapLayout : unsigned char { AMAP_NONE, AMAP_BLOCKED16,      // channel-blocked like the bf16 copies (bf16 conv epilogue)
+                                  AMAP_PLANAR32 };               // [C][ph][pw] (Winograd epilogues)
+enum BwdKind : unsigned char { B_NONE, B_SMALLM, B_SMALLM16, B_CONV16, B_WINO, B_WINO_SPLIT, B_DIRECT, B_AVEPOOL, B_POOL_IDX16,
+                               B_POOL_AMAP, B_POOL_CLASSIC,
+                               B_IN_DGRAD_BELOW };         // a max pool expanded inside the data gradient of the conv below it
+enum MaskSrc : unsigned char { MASK_NONE, MASK_F32, MASK_BF16, MASK_BITS };
+
+struct FwdRoute {
+    FwdKind kind = F_NONE;
+    // what the forward leaves of blob i, whichever launch writes it
+    bool out32 = false, out16 = false, bits = false;       // fp32 blob, bf16 copy, sign map
+    AmapLayout amap = AMAP_NONE;                           // arg-max map of a pool blob
+    bool pack16 = false;                                   // the bf16 copy comes from a pack_act16 pass after the launch
+    bool pools_next = false;                               // conv: the max pool above rides on this launch (entry i + 1 says what it writes)
+    bool style16 = false;                                  // the Gram / style gradient of this blob take their F operand from the bf16 copy
+    bool style_all16 = false;                              // ... and nothing of the style term reads the fp32 blob (style_runs16)
+};
+struct BwdRoute {
+    BwdKind kind = B_NONE;
+    bool in16 = false;                                     // reads the incoming diff as its bf16 copy ...
+    bool pack_in16 = false;                                // ... which nobody made: pack_act16 first
+    bool out32 = false, out16 = false;                     // forms of the diff it produces
+    MaskSrc mask = MASK_NONE;                              // ReLU mask of the blob below
+    bool unpool = false;                                   // conv: the incoming diff is the POOLED one, expanded through the map of the pool above
+    bool style = false;                                    // conv: the style gradient of the blob below rides on the launch
+};
+struct RoutePlan { std::vector<FwdRoute> fwd; std::vector<BwdRoute> bwd; };
+
 struct ActSet {                    // activations of one forward geometry
     int H = 0, W = 0;
     std::vector<int> C, h, w;
     std::vector<float*> data;      // data[0] is borrowed (the image itself)
     std::vector<unsigned short*> data16;   // bf16 channel-blocked copies of the blobs that feed a bf16 conv
-    std::vector<unsigned char*> amap;      // lean bf16 path: arg-max maps of the pools fused into the producing conv
-    std::vector<char> has32, amap_ok;      // per blob: fp32 copy / arg-max map written by the last forward
-    std::vector<unsigned short*> bits;     // bf16 lean flow: sign map of a conv blob that feeds a bf16 conv (Conv16Problem::bits_out) ...
-    std::vector<char> bits_ok;             // ... written by the last forward: the data gradient above masks with it instead of the bf16 copy
+    std::vector<unsigned char*> amap;      // arg-max maps of the pools fused into the producing conv
+    std::vector<unsigned short*> bits;     // bf16 lean flow: sign map of a conv blob that feeds a bf16 conv (Conv16Problem::bits_out)
+    RoutePlan plan;                        // of the last forward_range / backward_chain on these activations: which of the buffers above it wrote
     int valid_to = -1;
 };
 
@@ -265,10 +297,6 @@ inline void prof_note(st_ctx* c, int cls, double flops)
 void shapes_for(const st_ctx* c, int H, int W, std::vector<int>& C, std::vector<int>& h, std::vector<int>& w);
 void act_free(ActSet& a);
 int act_ensure(st_ctx* c, ActSet& a, int H, int W);
-bool blob_active(const st_ctx* c, int b);
-bool style_runs16(const st_ctx* c, const ActSet& a, int b);
-bool blob_needs32(const st_ctx* c, const ActSet& a, int b);
-bool style_fuse_ok(const st_ctx* c, const ActSet& a, int b, int last);
 int forward_range(st_ctx* c, ActSet& a, const float* x, int last, bool lean = false);
 int ensure_gram_bufs(st_ctx* c, int C, int hw, GramPlan& pl, bool plan16 = false);
 int gram_into(st_ctx* c, const float* F, int C, int hw, const float* target, float* out, int out_ld, float* partial, int* n_partial,
@@ -280,6 +308,17 @@ int preprocess_into(st_ctx* c, const void* hwc, int H, int W, int is_u8, float* 
 int set_input_common(st_ctx* c, int H, int W);
 int content_from_device(st_ctx* c, const float* xdev, int H, int W);
 int ensure_content_features(st_ctx* c);           // features of content-weighted blobs dropped by st_set_weights: recompute from the kept image
+// ---------------------------------------------------------------------------------------- engine_route.cpp
+// The planners only decide: no HIP call, no allocation on the device, nothing in the context changes.  Every shape predicate and
+// every per-call environment switch of the routing is read here, once per forward_range / backward_chain call (never cached: the
+// tests flip the switches between evaluations of one process).
+void plan_forward(const st_ctx* c, const ActSet& a, int last, bool lean, std::vector<FwdRoute>& fwd);
+// `a.plan.fwd` must be the plan of the forward that filled `a`; inj / fused_w: per blob, non-null where a diff is injected /
+// where a fused style operand waits for the data gradient above the blob
+void plan_backward(const st_ctx* c, const ActSet& a, int top, const std::vector<const float*>& inj,
+                   const std::vector<const unsigned short*>& fused_w, bool lean, std::vector<BwdRoute>& bwd);
+bool style_fuse_ok(const st_ctx* c, const ActSet& a, int b, int last);
+bool lean32_enabled();                            // ST2_LEAN32 (read per evaluation: A/B runs)
 // ---------------------------------------------------------------------------------------- engine_objective.cpp
 int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, bool adam, float* x_next);
 int read_trace(st_ctx* c, double* trace, float* loss);

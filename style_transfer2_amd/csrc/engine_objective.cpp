@@ -20,7 +20,7 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
     // Identical values either way.  ST2_LEAN32=0 switches the fp32 part off (read per evaluation: A/B runs).
     const bool lean = c->bf16 && c->lean && !c->tile.on;         // the bf16 data flow (forward AND backward)
     bool lean32 = false;                                          // fp32: the forward only (dead pooled-layer blobs)
-    if (!c->bf16 && c->in_step && !c->tile.on) { const char* e = getenv("ST2_LEAN32"); lean32 = !(e && *e == '0'); }
+    if (!c->bf16 && c->in_step && !c->tile.on) lean32 = lean32_enabled();
     ST_TRY(ensure_content_features(c));
     ST_TRY(forward_range(c, a, x, last, lean || lean32));
 
@@ -66,13 +66,13 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
                 ST_TRY(dmalloc(&c->dbuf, cc));
                 HIP_TRY(hipMemsetAsync(c->dbuf, 0, cc * sizeof(float), c->stream));
             }
-            // bf16 path: the Gram of the CURRENT features is taken from their bf16 copy (the style targets stay fp32 Grams)
-            const bool f16_fresh = c->bf16 && !c->tile.on && a.data16[b] && b >= 1 && c->topo[b - 1].is_conv && style_grad16_ok(C, (size_t)hw);
-            if (!a.has32[b] && !(a.data16[b] && style_runs16(c, a, b))) return fail(ST_ERR_STATE, "internal: style blob %d has neither an fp32 nor a usable bf16 copy", b);
-            ST_TRY(gram_into(c, a.data[b], C, hw, c->style_gram[b], c->dbuf, conv_mpad(C), part + 4 * kMaxPartials, &cnt[4], f16_fresh ? a.data16[b] : nullptr));
+            // bf16 path: the Gram of the CURRENT features and F of the style gradient are taken from the blob's bf16 copy where this
+            // forward wrote one the kernels can take (the style targets stay fp32 Grams)
+            const FwdRoute& fr = a.plan.fwd[b];
+            const bool s16 = !c->tile.on && fr.style16;
+            if (!fr.out32 && !(fr.out16 && fr.style_all16)) return fail(ST_ERR_STATE, "internal: style blob %d has neither an fp32 nor a usable bf16 copy", b);
+            ST_TRY(gram_into(c, a.data[b], C, hw, c->style_gram[b], c->dbuf, conv_mpad(C), part + 4 * kMaxPartials, &cnt[4], s16 ? a.data16[b] : nullptr));
             const float c2 = (float)(2.0 / ((double)C * C * (double)n));
-            // bf16 path: F from its bf16 copy on the bf16 matrix cores (written by this forward: b <= last, a style layer)
-            const bool s16 = c->bf16 && !c->tile.on && a.data16[b] && b >= 1 && c->topo[b - 1].is_conv && style_grad16_ok(C, (size_t)hw);
             // bf16 path, norm known: the gradient rides on the data-gradient conv above this blob; only its trace value is taken here
             const bool fuse = want_grad && s16 && c->norm_valid[b * 3 + 1] && style_fuse_ok(c, a, b, last);
             const int need = fuse ? style_s2_trace_blocks(C) : s16 ? style_grad16_blocks(C, (size_t)hw) : style_grad_blocks(C, a.h[b], a.w[b]);

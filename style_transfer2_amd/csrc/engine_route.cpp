@@ -1,0 +1,265 @@
+// The route plan: which kernel every layer of one evaluation runs, what it writes and what it reads, decided once before the
+// first launch.  forward_range / backward_chain (engine.cpp) execute the plan; nothing here touches the device or the context.
+#include "engine.h"
+
+namespace st2e {
+static bool env_off(const char* name) { const char* e = getenv(name); return e && *e == '0'; }
+
+bool lean32_enabled() { return !env_off("ST2_LEAN32"); }
+
+static bool blob_active(const st_ctx* c, int b)
+{
+    for (const ActiveLayer& al : c->active) if (al.blob == b) return true;
+    return false;
+}
+
+// Will the style term of blob b (a style layer) run entirely on the blob's bf16 copy (gram16.hip + style16.hip)?  Decided from
+// shapes only, so that the forward (which may then skip the fp32 blob) and the objective agree.
+static bool style_runs16(const st_ctx* c, const ActSet& a, int b)
+{
+    if (!c->bf16 || b < 1 || !c->topo[b - 1].is_conv) return false;
+    const int C = a.C[b], hw = a.h[b] * a.w[b];
+    if (!(conv16_ok(c, C) && style_grad16_ok(C, (size_t)hw) && C % 8 == 0)) return false;
+    // tile-sharded mode: the region-of-interest forms of both kernels take any region (ragged last step, 4-byte stores when the
+    // region's rows are not 16-byte aligned); ST2_TILE_STYLE16=0 keeps the fp32 region-of-interest kernels
+    if (c->tile.on) return !env_off("ST2_TILE_STYLE16");
+    return hw % 64 == 0 && gram16_ok(C, hw, gram_plan16(C, hw));
+}
+
+// lean evaluation: does anything read blob b in fp32?  Content / deep-dream terms do (layer_elem_k); a style term only when
+// its Gram / gradient cannot run on the bf16 copy.
+static bool blob_needs32(const st_ctx* c, const ActSet& a, int b)
+{
+    for (const ActiveLayer& al : c->active)
+        if (al.blob == b && (al.c || al.d || (al.s && !style_runs16(c, a, b)))) return true;
+    return false;
+}
+
+// May the style gradient of blob b ride on the data-gradient conv of the layer above it (conv3x3_mfma_bf16.hip, fused style term)?
+bool style_fuse_ok(const st_ctx* c, const ActSet& a, int b, int last)
+{
+    // (ST2_STYLE_FUSE is read per evaluation: the tests compare both flows in one process)
+    if (env_off("ST2_STYLE_FUSE") || !style_runs16(c, a, b) || b + 1 > last || a.C[b] % 32 != 0) return false;
+    const Layer& up = c->topo[b];                       // layer b + 1: consumes blob b
+    return up.is_conv && up.loaded && conv16_ok(c, up.cout) && up.cin == a.C[b];
+}
+
+// does the layer that consumes blob i run on the bf16 matrix cores?
+static bool feeds_conv16(const st_ctx* c, const ActSet& a, int i, int last)
+{
+    return c->bf16 && i < last && c->topo[i].is_conv && conv16_ok(c, a.C[i]);
+}
+
+static Conv16Problem shape16(int K, int M, int H, int W)
+{
+    Conv16Problem p{};
+    p.K = K; p.M = M; p.MPad = conv_mpad(M); p.H = H; p.W = W;
+    return p;
+}
+
+// ------------------------------------------------------------------------------------------ forward
+// `lean`: a conv blob whose only consumers are bf16 convs / a fused pool is not written in fp32 at all, a pool that follows such a
+// conv is computed in that conv's epilogue (bf16 pooled copy + arg-max map); fp32 (inside an iteration): the full-resolution blob
+// of a pooled, un-weighted layer is not written when the Winograd epilogue pools it and writes the arg-max map.
+void plan_forward(const st_ctx* c, const ActSet& a, int last, bool lean, std::vector<FwdRoute>& fwd)
+{
+    fwd.assign(c->nb, FwdRoute{});
+    fwd[0].out32 = true;
+    // ST2_MASK_BITS=0: the data gradients mask with the bf16 copies; ST2_POOL_AMAP=0: the classic pool backward
+    // (both read per forward: the tests compare both)
+    const bool want_bits = lean && c->bf16 && !env_off("ST2_MASK_BITS");
+    const bool want_amap = !env_off("ST2_POOL_AMAP");
+    for (int i = 1; i <= last; ++i) {
+        const Layer& L = c->topo[i - 1];
+        FwdRoute& r = fwd[i];
+        const int H = a.h[i], W = a.w[i];
+        if (!L.is_conv) {
+            if (r.kind == F_BY_CONV_BELOW) continue;       // (filled in by the conv's entry)
+            const bool to16 = feeds_conv16(c, a, i, last);
+            if (L.ave) {
+                // stand-alone pass over the fp32 blob below: the fp32 pooled blob where something reads fp32 (lean rules: a weighted
+                // blob, the last blob, a consumer that is not a bf16 conv), the bf16 copy a bf16 conv reads from the same pass
+                r.kind = F_AVEPOOL;
+                r.out16 = to16;
+                r.out32 = !lean || !to16 || blob_active(c, i) || i == last;
+            } else {
+                r.kind = F_MAXPOOL;
+                r.out32 = true;
+                r.out16 = r.pack16 = to16;
+            }
+            continue;
+        }
+        const bool conv_next16 = feeds_conv16(c, a, i, last);
+        // ... or does the style gradient of this blob read the bf16 copy (style16.hip)?
+        bool next16 = conv_next16;
+        if (c->bf16 && conv16_ok(c, L.cout) && style_grad16_ok(L.cout, (size_t)H * W))
+            for (const ActiveLayer& al : c->active) if (al.blob == i && al.s) next16 = true;
+        // lean: the data gradient of the bf16 conv above masks with blob i -- through a sign map (1 bit per element, written by
+        // this launch's epilogue) instead of the bf16 copy (16 bits)
+        const bool bits_i = want_bits && conv_next16 && L.cout % 32 == 0;
+        const bool next_max_pool = i < last && !c->topo[i].is_conv && !c->topo[i].ave;
+        r.out32 = true;
+        if (c->bf16 && conv16_ok(c, L.cin) && fwd[i - 1].out16) {
+            r.kind = F_CONV16;
+            r.out16 = next16;
+            if (lean && !blob_needs32(c, a, i) && i < last) {
+                // (a weighted blob gets an injected diff: classic pool backward; an average pool always runs stand-alone on the fp32 blob)
+                if (next_max_pool && !blob_active(c, i) && conv16_can_pool(shape16(L.cin, L.cout, H, W))) {
+                    // the pool rides on this launch: pooled bf16 copy for the conv after it, arg-max map for the backward
+                    FwdRoute& pool = fwd[i + 1];
+                    pool.kind = F_BY_CONV_BELOW;
+                    pool.out16 = feeds_conv16(c, a, i + 1, last);
+                    pool.out32 = !pool.out16 || blob_active(c, i + 1) || i + 1 == last;
+                    pool.amap = AMAP_BLOCKED16;
+                    r.pools_next = true;
+                    r.out32 = false;
+                } else if (conv_next16) {
+                    r.out32 = false;                       // the next conv reads the bf16 copy; the backward masks with it too
+                }
+            }
+            r.bits = bits_i && r.out16;
+        } else if (c->wino && L.u_fwd && conv_wino_ok(L.cin, L.cout, H, W)) {
+            // st_set_conv_algo(ctx, 2): the same products as six bf16 partial products of split operands where the shape allows
+            const bool split = c->wino_split && !c->bf16 && L.us_fwd && conv_wino_split_ok(L.cin, L.cout, H, W);
+            r.kind = split ? F_WINO_SPLIT : F_WINO;
+            r.out16 = r.pack16 = next16;
+            // the max pool that follows rides on this launch's epilogue (the pooled blob is written beside the conv blob);
+            // an average pool does not (avepool_fwd reads the fp32 blob)
+            if (next_max_pool && !c->bf16 && (split ? conv_wino_split_can_pool(L.cin, L.cout, H, W) : conv_wino_can_pool(L.cin, L.cout, H, W))) {
+                FwdRoute& pool = fwd[i + 1];
+                pool.kind = F_BY_CONV_BELOW;
+                pool.out32 = true;
+                r.pools_next = true;
+                // ... and a one-byte arg-max map for the pool's backward (maxpool_bwd_amap_k: neither blob is read again)
+                if (want_amap && (split ? conv_wino_split_pool_amap_ok(L.cin, L.cout, H, W) : conv_wino_pool_amap_ok(L.cin, L.cout, H, W))) {
+                    pool.amap = AMAP_PLANAR32;
+                    // lean (inside an iteration): the full-resolution blob of a pooled, un-weighted layer is dead -- the next conv
+                    // reads the pooled blob, the pool's backward the arg-max map (with the ReLU sign in it) -- so it is not
+                    // written (conv1_2 at 1024^2: 268 MB and a quarter of the epilogue's instructions); same values everywhere else
+                    if (lean && !blob_active(c, i) && (split ? conv_wino_split_can_skip_out(L.cin, L.cout, H, W) : conv_wino_can_skip_out(L.cin, L.cout, H, W)))
+                        r.out32 = false;
+                }
+            }
+        } else {
+            // bf16 path: the image keeps its fp32 precision (three-way bf16 split, six partial products on the bf16 matrix cores)
+            r.kind = (c->bf16 && L.w_split && conv_first_split_ok(L.cin, L.cout, H, W)) ? F_FIRST_SPLIT : F_DIRECT;
+            r.out16 = next16;
+            r.pack16 = next16 && L.cout % 8 != 0;          // (otherwise the epilogue writes the bf16 copy too)
+            // lean: conv1_1's fp32 blob is written only if something reads it (conv1_2, the ReLU mask and a style term take the copy)
+            if (lean && next16 && !r.pack16 && conv_next16 && i < last && !blob_needs32(c, a, i)) r.out32 = false;
+            r.bits = r.kind == F_FIRST_SPLIT && bits_i && next16 && !r.pack16;
+        }
+    }
+    for (const ActiveLayer& al : c->active) {
+        const int b = al.blob;
+        if (!al.s || b < 1 || b > last || !c->topo[b - 1].is_conv) continue;
+        fwd[b].style16 = fwd[b].out16 && style_grad16_ok(a.C[b], (size_t)a.h[b] * a.w[b]);
+        fwd[b].style_all16 = fwd[b].out16 && style_runs16(c, a, b);
+    }
+}
+
+// ----------------------------------------------------------------------------------------- backward
+namespace {
+// the data gradient of conv layer i (1-based; its input is blob i - 1), from shapes, weights and switches alone
+struct Dgrad {
+    BwdKind kind;
+    bool wants16;                                  // whatever produces its incoming diff writes the bf16 copy
+    bool reads16() const { return kind == B_SMALLM16 || kind == B_CONV16; }      // (packed first where nobody made the copy)
+};
+
+Dgrad dgrad_route(const st_ctx* c, const ActSet& a, int i)
+{
+    const Layer& L = c->topo[i - 1];
+    const bool below_is_conv = i - 1 >= 1 && c->topo[i - 2].is_conv;
+    const bool small_m = !below_is_conv && conv_dgrad_smallM_ok(L.cout, L.cin);
+    if (small_m) return (c->bf16 && L.w_raw_r) ? Dgrad{B_SMALLM16, true} : Dgrad{B_SMALLM, false};
+    // (a conv of few input channels ABOVE a conv keeps the bf16 kernel but is handed an fp32 diff, which it packs)
+    if (c->bf16 && conv16_ok(c, L.cout)) return Dgrad{B_CONV16, !conv_dgrad_smallM_ok(L.cout, L.cin)};
+    if (!(c->wino && L.u_bwd && conv_wino_ok(L.cout, L.cin, a.h[i], a.w[i]))) return Dgrad{B_DIRECT, false};
+    if (!(c->wino_split && !c->bf16 && L.us_bwd && conv_wino_split_ok(L.cout, L.cin, a.h[i], a.w[i]))) return Dgrad{B_WINO, false};
+    // ST2_WS_DGRAD64=0: K <= 64 launches that the fp32 kernel could unpool (conv1_2's data gradient) stay on the fp32 matrix cores.  With
+    // the first split epilogue that was the faster route (404 + 60 us of maxpool_bwd_amap_k against 429 us); since the branch-free
+    // epilogue it is not (same-box A/B, profiles/r05_s_ab_split.txt: 177.4 against 176.1 it/s) -- kept as a switch for the A/B only
+    if (env_off("ST2_WS_DGRAD64") && L.cout <= 64 && conv_wino_can_unpool(L.cout, L.cin, a.h[i], a.w[i])) return Dgrad{B_WINO, false};
+    return Dgrad{B_WINO_SPLIT, false};
+}
+
+// may that data gradient take the POOLED diff and expand it through the arg-max map of the max pool above its output?
+bool dgrad_can_unpool(const st_ctx* c, const ActSet& a, int i, const Dgrad& d)
+{
+    const Layer& L = c->topo[i - 1];
+    // conv16_body's UNPOOL builds stage the pooled diff and expand it in LDS; the Winograd kernel unpools in its input transform
+    // (the split-operand kernel has no unpooling input transform: its launches keep maxpool_bwd_amap_k)
+    if (d.kind == B_CONV16) return conv16_can_unpool(shape16(L.cout, L.cin, a.h[i], a.w[i]));
+    if (d.kind == B_WINO) return conv_wino_can_unpool(L.cout, L.cin, a.h[i], a.w[i]);
+    return false;
+}
+}  // namespace
+
+// `lean` must be what the forward that filled `a` ran with: the fp32 diff of a layer is then written only when its consumer needs
+// fp32 (a pool without arg-max map, the 3-channel conv1_1 kernel, a non-bf16 conv), ReLU masks come from the bf16 copies or sign
+// maps, and pools fused into their producing conv are back-propagated through their arg-max maps in bf16.
+void plan_backward(const st_ctx* c, const ActSet& a, int top, const std::vector<const float*>& inj,
+                   const std::vector<const unsigned short*>& fused_w, bool lean, std::vector<BwdRoute>& bwd)
+{
+    const std::vector<FwdRoute>& fwd = a.plan.fwd;
+    bwd.assign(c->nb, BwdRoute{});
+    bool have32 = true, have16 = false;            // forms of the running diff (the top diff arrives in fp32)
+    bool pooled = false;                           // ... which is still the POOLED diff of the max pool just passed
+    for (int i = top; i >= 1; --i) {
+        const Layer& L = c->topo[i - 1];
+        BwdRoute& r = bwd[i];
+        const int below = i - 1;
+        const bool below_is_conv = below >= 1 && c->topo[below - 1].is_conv;
+        const Dgrad next = below_is_conv ? dgrad_route(c, a, below) : Dgrad{B_NONE, false};      // the data gradient that runs after this layer's
+        if (L.is_conv) {
+            const Dgrad d = dgrad_route(c, a, i);
+            r.kind = d.kind;
+            r.mask = below_is_conv ? MASK_F32 : MASK_NONE;
+            r.unpool = pooled; pooled = false;
+            r.in16 = d.reads16();
+            r.pack_in16 = r.in16 && !have16;
+            r.out32 = true;
+            if (d.kind == B_CONV16) {
+                // the consumer of this launch's output takes bf16 iff it is a bf16 dgrad conv, or (lean) a pool with an arg-max map
+                r.out16 = next.wants16 || (lean && below >= 1 && !c->topo[below - 1].is_conv && fwd[below].amap != AMAP_NONE && L.cin % 8 == 0);
+                r.out32 = !(lean && r.out16);
+                r.style = below >= 1 && (size_t)below < fused_w.size() && fused_w[below] != nullptr;
+                // the mask is applied in registers: from the fp32 blob, (lean, or under a fused style term) from the bf16 copy,
+                // or from the blob's sign map
+                if (below_is_conv && ((lean && fwd[below].out16) || r.style)) r.mask = MASK_BF16;
+                if (below_is_conv && lean && fwd[below].bits) r.mask = MASK_BITS;
+            }
+            have32 = r.out32; have16 = r.out16;
+        } else if (L.ave) {
+            // dx = mask(dy / window size) + inject in one pass; the bf16 copy for a bf16 dgrad conv below comes out of the same pass
+            // (no pack_act16), the fp32 diff where the consumer below reads fp32 (or every diff is materialised)
+            r.kind = B_AVEPOOL;
+            r.mask = below_is_conv ? MASK_F32 : MASK_NONE;
+            r.out16 = c->bf16 && next.wants16;
+            r.out32 = !(lean && r.out16);
+            have32 = r.out32; have16 = r.out16;
+        } else if (lean && fwd[i].amap != AMAP_NONE && !inj[below] && next.wants16) {
+            // pool fused into its producing conv: the bf16 diff goes through the arg-max map (ReLU mask of the conv blob included) ...
+            r.in16 = true;
+            r.pack_in16 = !have16;
+            have16 = true;
+            // ... inside the data gradient of the conv below when it has the build (maxpool_bwd_idx16_k, its full-resolution
+            // output and the conv's read of it are gone)
+            if (dgrad_can_unpool(c, a, below, next)) { r.kind = B_IN_DGRAD_BELOW; pooled = true; }
+            else { r.kind = B_POOL_IDX16; r.out16 = true; have32 = false; }
+        } else if (fwd[i].amap == AMAP_PLANAR32 && !inj[below] && below_is_conv && have32) {
+            // pool fused into its producing Winograd conv (fp32): through the arg-max map, ReLU mask included, inside the data
+            // gradient below (maxpool_bwd_amap_k, its full-resolution output and the conv's read of it are gone; same values bit
+            // for bit) or stand-alone
+            if (!c->bf16 && dgrad_can_unpool(c, a, below, next)) { r.kind = B_IN_DGRAD_BELOW; pooled = true; }
+            else { r.kind = B_POOL_AMAP; r.out32 = true; have32 = true; have16 = false; }
+        } else {
+            r.kind = B_POOL_CLASSIC;
+            r.mask = below_is_conv ? MASK_F32 : MASK_NONE;
+            r.out32 = true;
+            have32 = true; have16 = false;
+        }
+    }
+}
+}  // namespace st2e

@@ -29,7 +29,8 @@ int tile_ensure(float** p, size_t* cap, size_t n)
 // bf16 operands: does the style term of blob b run on its bf16 copy here (region-of-interest forms of gram16.hip / style16.hip)?
 bool tile_style16(const st_ctx* c, int b)
 {
-    return c->bf16 && c->act.data16[b] && style_runs16(c, c->act, b);
+    const FwdRoute& fr = c->act.plan.fwd[b];
+    return fr.out16 && fr.style_all16;
 }
 
 // the style gradient of blob b over the tile's region (worker.py:262-269): fp32 kernel on the fp32 blob, or -- bf16 operands -- the
@@ -39,7 +40,7 @@ int tile_style_grad(st_ctx* c, int b, const BlobRoi& r, float* dst, bool is_inje
     const ActSet& a = c->act;
     const int C = a.C[b];
     if (!tile_style16(c, b)) {
-        if (!a.has32[b]) return fail(ST_ERR_STATE, "internal: style blob %d has no fp32 copy", b);
+        if (!a.plan.fwd[b].out32) return fail(ST_ERR_STATE, "internal: style blob %d has no fp32 copy", b);
         const int need = style_grad_blocks(C, a.h[b], a.w[b]);
         if (c->s2_cap[b] < need) { dfree(c->s2_part[b]); ST_TRY(dmalloc(&c->s2_part[b], need)); c->s2_cap[b] = need; }
         PixRoi pr{r.y0, r.x0, r.y1, r.x1};
@@ -120,7 +121,7 @@ int st_tile_forward(st_ctx* c, float** dev_ptr, int* n_floats)
     // blobs: the region-of-interest loss kernels are fp32), pools ride on their producing conv, the backward masks from the bf16 copies
     // fp32, inside the fused iteration (st_tile_step): the full-resolution blobs of pooled, un-weighted layers are not written either
     bool lean32 = false;
-    if (!c->bf16 && c->tile.fused) { const char* e = getenv("ST2_LEAN32"); lean32 = !(e && *e == '0'); }
+    if (!c->bf16 && c->tile.fused) lean32 = lean32_enabled();
     ST_TRY(forward_range(c, a, c->x[c->cur], last, (c->bf16 && c->lean) || lean32));
     size_t pos = 0;
     for (const ActiveLayer& al : c->active) {
@@ -149,7 +150,7 @@ int st_tile_forward(st_ctx* c, float** dev_ptr, int* n_floats)
                 ST_TRY(ensure_gram_bufs(c, C, hw, pl, true));
                 HIP_TRY(launch_gram16_partial(a.data16[b], c->gram_slabs, C, hw, pl, c->stream, &roi));
             } else {
-                if (!a.has32[b]) return fail(ST_ERR_STATE, "internal: style blob %d has no fp32 copy", b);
+                if (!a.plan.fwd[b].out32) return fail(ST_ERR_STATE, "internal: style blob %d has no fp32 copy", b);
                 ST_TRY(ensure_gram_bufs(c, C, hw, pl));
                 HIP_TRY(launch_gram_partial(a.data[b], c->gram_slabs, C, hw, pl, c->stream, &roi));
             }
