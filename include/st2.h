@@ -55,6 +55,19 @@ int st_load_conv_weights(st_ctx* ctx, const char* layer, const float* w, const f
  * exact bf16 x bf16 partial products of three-way split fp32 operands, accumulated in fp32 (conv3x3_wino_split.hip):
  * fp32-grade results (closer to a double-precision convolution than algorithm 1's), not bit-identical to them. */
 int st_set_conv_algo(st_ctx* ctx, int winograd);
+/* The style statistics (worker.py:109-114, 258-269) of fp32 features.  0 (default): Gram partials and style gradients on the
+ * fp32 matrix cores.  1 (opt-in): where the shape allows it (whole blobs, channels % 64 == 0 from 128 up, tensors below 4 GiB) both GEMMs
+ * run on the bf16 matrix cores as the six exact bf16 x bf16 partial products of three-way split fp32 operands, accumulated
+ * in fp32 (gram_split.hip): fp32-grade results, not bit-identical to algorithm 0's; every other shape runs algorithm 0's
+ * kernels bit for bit.  Anything else is ST_ERR_ARG.  It applies to every Gram and style gradient the context computes
+ * afterwards, st_gram and the style targets of st_set_style included; targets computed earlier are kept as they are.
+ * It has effect only with fp32 features: under st_set_precision(ctx, 1 | 2) the bf16 kernels keep running; and the
+ * tile-sharded mode keeps the fp32 kernels whatever the option says.  A non-finite feature gives a non-finite Gram under
+ * both algorithms, but entries that algorithm 0 gives as Inf may be NaN under 1 (the split forms Inf - Inf).
+ * The call allocates its scratch first: when that fails it returns the error and changes nothing. */
+int st_set_gram_algo(st_ctx* ctx, int algo);
+/* the algorithms in force: *conv = 0 | 1 | 2 (st_set_conv_algo), *gram = 0 | 1 (st_set_gram_algo); either pointer may be NULL */
+int st_get_algos(st_ctx* ctx, int* conv, int* gram);
 /* 0 (default): fp32 throughout.  1: bf16 feature path (BASELINE config 3) -- conv operands (activations, weights,
  * backward diffs) in bf16 on v_mfma_f32_32x32x16_bf16, fp32 accumulate; Gram, losses, optimizer stay fp32.  Objective
  * evaluations then write an fp32 blob / diff only where something reads fp32 (weighted layers, pools without a fused

@@ -27,6 +27,7 @@ SOURCES = (
     ('lbfgs.hip', ('-ffp-contract=off',)),
     ('style16.hip', ()),
     ('gram16.hip', ()),
+    ('gram_split.hip', ()),
     ('conv3x3_dgrad_first.hip', ()),
     ('conv3x3_first_split.hip', ()),
     ('engine.cpp', ('-x', 'hip')),

@@ -22,7 +22,8 @@ const char* const kProfNames[P_COUNT] = {"conv3x3_fwd_mfma_f32", "conv3x3_dgrad_
                                           "image_pass", "finalize", "vector_ops", "misc", "conv3x3_fwd_wino_f32", "conv3x3_dgrad_wino_f32",
                                           "conv3x3_fwd_mfma_bf16", "conv3x3_dgrad_mfma_bf16", "tile_comm",
                                           "gram_partial_mfma_bf16", "style_grad_mfma_bf16", "conv3x3_fwd_wino_split_bf16x6", "conv3x3_dgrad_wino_split_bf16x6",
-                                          "style_grad_fused_in_conv_dgrad_bf16", "avepool_fwd", "avepool_bwd"};
+                                          "style_grad_fused_in_conv_dgrad_bf16", "avepool_fwd", "avepool_bwd",
+                                          "gram_partial_split_bf16x6", "style_grad_split_bf16x6"};
 
 static const struct { int kind; const char* name; int cin, cout; } kVgg19[] = {
     {0, "conv1_1", 3, 64}, {0, "conv1_2", 64, 64}, {1, "pool1", 0, 0},
@@ -240,6 +241,13 @@ int ensure_gram_bufs(st_ctx* c, int C, int hw, GramPlan& pl, bool plan16)
     return ST_OK;
 }
 
+// fp32 features, not tile-sharded (the ROI Grams of that mode and their all-reduced raw sums keep the fp32 kernels), a shape the
+// split kernels take
+bool use_gram_split(const st_ctx* c, int C, int hw)
+{
+    return c->gram_split && !c->bf16 && !c->tile.on && gram_split_ok(C, hw) && style_grad_split_ok(C, hw);
+}
+
 // G (or G - target) of blob data F -> out (C*C); optional sum-of-squares partials
 // F16 (optional): the bf16 channel-blocked copy of the blob -- the bf16 feature path then takes the partials on the bf16 matrix cores
 int gram_into(st_ctx* c, const float* F, int C, int hw, const float* target, float* out, int out_ld, float* partial, int* n_partial,
@@ -247,10 +255,12 @@ int gram_into(st_ctx* c, const float* F, int C, int hw, const float* target, flo
 {
     GramPlan pl;
     const bool use16 = F16 && C % 8 == 0 && hw % 64 == 0 && gram16_ok(C, hw, gram_plan16(C, hw));
+    const bool split = !use16 && use_gram_split(c, C, hw);       // st_set_gram_algo(ctx, 1): same plan, same slabs, same reduction
     ST_TRY(ensure_gram_bufs(c, C, hw, pl, use16));
     {
-        ProfScope ps(c, use16 ? P_GRAM_BF16 : P_GRAM, 2.0 * C * C * (double)hw, (use16 ? 2.0 : 4.0) * C * (double)hw);      // (the class names the matrix core that ran)
+        ProfScope ps(c, use16 ? P_GRAM_BF16 : split ? P_GRAM_SPLIT : P_GRAM, 2.0 * C * C * (double)hw, (use16 ? 2.0 : 4.0) * C * (double)hw);      // (the class names the matrix core that ran)
         if (use16) HIP_TRY(launch_gram16_partial(F16, c->gram_slabs, C, hw, pl, c->stream));
+        else if (split) HIP_TRY(launch_gram_split_partial(F, c->gram_slabs, C, hw, pl, c->stream));
         else HIP_TRY(launch_gram_partial(F, c->gram_slabs, C, hw, pl, c->stream));
     }
     {
@@ -573,7 +583,7 @@ int st_destroy(st_ctx* c)
     for (auto& p : c->layer_part) dfree(p);
     for (auto& p : c->s2_part) dfree(p);
     for (auto& p : c->sfuse_w) dfree16(p);
-    dfree(c->diffA); dfree(c->diffB); dfree(c->stmp); dfree(c->gram_slabs); dfree(c->gram_fold); dfree(c->dbuf); dfree16(c->d16); dfree(c->conv_scratch);
+    dfree(c->diffA); dfree(c->diffB); dfree(c->stmp); dfree(c->gram_slabs); dfree(c->gram_fold); dfree(c->dbuf); dfree16(c->d16); dfree16(c->dsplit); dfree(c->conv_scratch);
     comm_free(c);
     dfree(c->tile.p1); dfree(c->tile.p2); dfree(c->tile.p3); dfree(c->tile.pd); dfree(c->tile.wgrad); dfree(c->tile.lb_x); dfree(c->tile.lb_sums);
     dfree(c->norms); dfree(c->image_part); dfree(c->trace_dev); dfree(c->lb_part); dfree(c->hwc_dev);
@@ -692,6 +702,37 @@ int st_set_conv_algo(st_ctx* c, int winograd)
             ST_TRY(make_split_packs(L, w.data()));
         }
     }
+    return ST_OK;
+}
+
+int st_set_gram_algo(st_ctx* c, int algo)
+{
+    if (!c) return fail(ST_ERR_ARG, "ctx is NULL");
+    if (algo != 0 && algo != 1) return fail(ST_ERR_ARG, "gram algorithm %d: 0 fp32 matrix cores, 1 split operands (bf16 matrix cores, fp32 results)", algo);
+    if (algo == 1) {           // the operand image of D for the widest blob the kernels take; the flag is committed last
+        std::vector<int> C, h, w;
+        shapes_for(c, 16, 16, C, h, w);
+        size_t need = 0;
+        for (int i = 0; i < c->nb; ++i) if (style_grad_split_ok(C[i], 4)) need = std::max(need, style_grad_split_pack_elems(C[i]));
+        if (need > c->dsplit_cap) {
+            HIP_TRY(hipSetDevice(c->device));
+            unsigned short* p = nullptr;
+            ST_TRY(dmalloc16(&p, need));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            dfree16(c->dsplit);
+            c->dsplit = p; c->dsplit_cap = need;
+        }
+    }
+    c->epoch++;                // anything but st_step may change what a step launches: captured step graphs are stale
+    c->gram_split = algo == 1;
+    return ST_OK;
+}
+
+int st_get_algos(st_ctx* c, int* conv, int* gram)
+{
+    if (!c) return fail(ST_ERR_ARG, "ctx is NULL");
+    if (conv) *conv = c->wino_split ? 2 : c->wino ? 1 : 0;
+    if (gram) *gram = c->gram_split ? 1 : 0;
     return ST_OK;
 }
 

@@ -36,7 +36,7 @@ int fail(int code, const char* fmt, ...);
 enum ProfClass { P_CONV_FWD, P_CONV_DGRAD, P_POOL_FWD, P_POOL_BWD, P_GRAM, P_GRAM_REDUCE, P_STYLE_GRAD,
                  P_LAYER_ELEM, P_IMAGE_PASS, P_FINALIZE, P_VECTOR, P_MISC, P_CONV_FWD_WINO, P_CONV_DGRAD_WINO,
                  P_CONV_FWD_BF16, P_CONV_DGRAD_BF16, P_COMM, P_GRAM_BF16, P_STYLE_GRAD_BF16, P_CONV_FWD_WSPLIT, P_CONV_DGRAD_WSPLIT, P_STYLE_FUSED_BF16,
-                 P_AVEPOOL_FWD, P_AVEPOOL_BWD, P_COUNT };
+                 P_AVEPOOL_FWD, P_AVEPOOL_BWD, P_GRAM_SPLIT, P_STYLE_GRAD_SPLIT, P_COUNT };
 extern const char* const kProfNames[P_COUNT];
 struct ProfRec { int cls; hipEvent_t a, b; double flops, bytes; };
 
@@ -113,6 +113,8 @@ struct st_ctx {
     bool in_step = false;                          // inside step_enqueue: objective evaluations may skip fp32 blobs nothing reads (lean fp32)
     bool wino = true;                              // Winograd F(2x2,3x3) for the eligible fp32 convs (ST2_WINO=0 disables)
     bool wino_split = false;                       // ... on the bf16 matrix cores with three-way split operands where the shape allows (st_set_conv_algo(ctx, 2))
+    bool gram_split = false;                       // fp32 features: Gram partials and style gradients on the bf16 matrix cores with three-way split operands where the shape allows (st_set_gram_algo(ctx, 1))
+    unsigned short* dsplit = nullptr; size_t dsplit_cap = 0;      // ... and the three-term operand image of D (gram_split.hip), sized for the widest blob when the option is set
     unsigned short *diff16A = nullptr, *diff16B = nullptr;
     std::vector<Layer> topo;
     std::vector<std::string> blob_names;
@@ -301,6 +303,7 @@ int forward_range(st_ctx* c, ActSet& a, const float* x, int last, bool lean = fa
 int ensure_gram_bufs(st_ctx* c, int C, int hw, GramPlan& pl, bool plan16 = false);
 int gram_into(st_ctx* c, const float* F, int C, int hw, const float* target, float* out, int out_ld, float* partial, int* n_partial,
               const unsigned short* F16 = nullptr);
+bool use_gram_split(const st_ctx* c, int C, int hw);      // this whole-blob fp32 Gram / style gradient runs on gram_split.hip
 int backward_chain(st_ctx* c, int top, const float* top_diff, const std::vector<const float*>& inj, const float** out, bool lean = false);
 int ensure_input_buffers(st_ctx* c, int H, int W);
 int stage_upload(st_ctx* c, const void* host, size_t bytes);

@@ -75,7 +75,9 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
             const float c2 = (float)(2.0 / ((double)C * C * (double)n));
             // bf16 path, norm known: the gradient rides on the data-gradient conv above this blob; only its trace value is taken here
             const bool fuse = want_grad && s16 && c->norm_valid[b * 3 + 1] && style_fuse_ok(c, a, b, last);
-            const int need = fuse ? style_s2_trace_blocks(C) : s16 ? style_grad16_blocks(C, (size_t)hw) : style_grad_blocks(C, a.h[b], a.w[b]);
+            // st_set_gram_algo(ctx, 1), fp32 features: the same S from split operands on the bf16 matrix cores (gram_split.hip)
+            const bool ssplit = !s16 && use_gram_split(c, C, hw) && style_grad_split_pack_elems(C) <= c->dsplit_cap;
+            const int need = fuse ? style_s2_trace_blocks(C) : s16 ? style_grad16_blocks(C, (size_t)hw) : ssplit ? style_grad_split_blocks(C, hw) : style_grad_blocks(C, a.h[b], a.w[b]);
             if (c->s2_cap[b] < need) { dfree(c->s2_part[b]); ST_TRY(dmalloc(&c->s2_part[b], need)); c->s2_cap[b] = need; }
             if (s16 && style_grad16_pack_elems(C) > c->d16_cap) {
                 dfree16(c->d16); c->d16_cap = 0;
@@ -84,8 +86,9 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
             }
             const double fl = 2.0 * C * C * (double)hw;
             auto style_launch = [&](float* dst, int fused, int accumulate) -> int {
-                ProfScope ps(c, s16 ? P_STYLE_GRAD_BF16 : P_STYLE_GRAD, fl, n * (s16 ? 6.0 : 8.0));
-                if (s16) HIP_TRY(launch_style_grad16(c->dbuf, conv_mpad(C), c->d16, a.data16[b], dst, c2, fused, al.sw, nrm + 1, accumulate, c->s2_part[b], &cnt[5], C, (size_t)hw, c->stream));
+                ProfScope ps(c, s16 ? P_STYLE_GRAD_BF16 : ssplit ? P_STYLE_GRAD_SPLIT : P_STYLE_GRAD, fl, n * (s16 ? 6.0 : 8.0));
+                if (ssplit) HIP_TRY(launch_style_grad_split(c->dbuf, conv_mpad(C), c->dsplit, a.data[b], dst, c2, fused, al.sw, nrm + 1, accumulate, c->s2_part[b], &cnt[5], C, hw, c->stream));
+                else if (s16) HIP_TRY(launch_style_grad16(c->dbuf, conv_mpad(C), c->d16, a.data16[b], dst, c2, fused, al.sw, nrm + 1, accumulate, c->s2_part[b], &cnt[5], C, (size_t)hw, c->stream));
                 else HIP_TRY(launch_style_grad(c->dbuf, a.data[b], dst, c2, fused, al.sw, nrm + 1, accumulate, c->s2_part[b], &cnt[5], C, a.h[b], a.w[b], c->stream));
                 return ST_OK;
             };

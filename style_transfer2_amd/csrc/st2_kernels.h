@@ -185,6 +185,10 @@ hipError_t launch_gram16_partial(const unsigned short* F16, float* slabs, int C,
                                  const GramRoi* roi = nullptr);
 hipError_t launch_gram_partial(const float* F, float* slabs, int C, int hw, const GramPlan& pl, hipStream_t s,
                                const GramRoi* roi = nullptr);
+// Split operands (gram_split.hip; st_set_gram_algo(ctx, 1)): the same partials from six exact bf16 partial products of three-way split
+// fp32 operands on the bf16 matrix cores; whole blobs, gram_plan's plan and slab format.  C % 64 == 0, tensors below 4 GiB.
+bool gram_split_ok(int C, int hw);
+hipError_t launch_gram_split_partial(const float* F, float* slabs, int C, int hw, const GramPlan& pl, hipStream_t s);
 // out[i][j] = sum_s slabs[s][i][j] / n  - (target ? target[i][j] : 0);  partial[blockIdx] = sum out^2
 // `folded` is scratch of gram_fold_groups(pl) * C * C floats (two-stage reduction when there are many splits)
 int gram_fold_groups(const GramPlan& pl);
@@ -203,6 +207,13 @@ struct PixRoi { int y0, x0, y1, x1; };               // half-open pixel rectangl
 hipError_t launch_style_grad(const float* Dp, const float* F, float* dst, float c2, int fused, float sw, const float* norm,
                              int accumulate, float* partial, int* n_partial, int C, int H, int W, hipStream_t s,
                              const PixRoi* roi = nullptr);
+// Split operands (gram_split.hip; st_set_gram_algo(ctx, 1)): the same S and epilogue for a whole fp32 blob, D and F split three ways
+// (A16 = scratch of style_grad_split_pack_elems(C) bf16, 16-byte aligned).  C % 64 == 0, tensors below 4 GiB.
+bool style_grad_split_ok(int C, int hw);
+size_t style_grad_split_pack_elems(int C);
+int style_grad_split_blocks(int C, int hw);
+hipError_t launch_style_grad_split(const float* Dp, int ld, unsigned short* A16, const float* F, float* dst, float c2, int fused, float sw,
+                                   const float* norm, int accumulate, float* partial, int* n_partial, int C, int hw, hipStream_t s);
 // bf16 feature path: the same S on the bf16 matrix cores, F read from its bf16 channel-blocked copy [C/8][hw][8], D split
 // on the device into hi + lo bf16 terms (A16 = scratch of style_grad16_pack_elems(C) bf16).  C % 64 == 0.
 bool style_grad16_ok(int C, size_t hw);

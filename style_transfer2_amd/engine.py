@@ -83,7 +83,23 @@ class Engine:
     def set_conv_algo(self, winograd):
         """True / 1 (default): eligible fp32 convs run as Winograd F(2x2,3x3) on the fp32 matrix cores; False / 0: direct kernel only;
         2: Winograd with the transform-domain products as six bf16 partial products of split operands (fp32 results) where the shape allows."""
-        check(self.lib.st_set_conv_algo(self._ctx, 2 if winograd == 2 else (1 if winograd else 0)))
+        if winograd not in (0, 1, 2):         # (False == 0 and True == 1)
+            raise ValueError('conv_algo must be 0 (direct), 1 (Winograd, fp32 matrix cores) or 2 (split-operand Winograd), not %r' % (winograd,))
+        check(self.lib.st_set_conv_algo(self._ctx, int(winograd)))
+
+    def set_gram_algo(self, algo):
+        """0 (default): Gram partials and style gradients of fp32 features on the fp32 matrix cores; 1: as six bf16 partial products of
+        three-way split operands on the bf16 matrix cores (fp32 results) where the shape allows.  Applies to every Gram computed afterwards
+        (style targets included); no effect on the bf16 feature path or in tile-sharded mode."""
+        if algo not in (0, 1):
+            raise ValueError('gram_algo must be 0 (fp32 matrix cores) or 1 (split operands), not %r' % (algo,))
+        check(self.lib.st_set_gram_algo(self._ctx, int(algo)))
+
+    def algos(self):
+        """(conv_algo, gram_algo) in force."""
+        conv, gram = c_int(), c_int()
+        check(self.lib.st_get_algos(self._ctx, byref(conv), byref(gram)))
+        return conv.value, gram.value
 
     # -- lifecycle -------------------------------------------------------------------------------
     def close(self):

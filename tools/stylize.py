@@ -21,6 +21,8 @@ ap.add_argument('--iters', type=int, default=500)
 ap.add_argument('--optimizer', default='adam', choices=['adam', 'lbfgs'])
 ap.add_argument('--weights', default='', help='.npz or .caffemodel; default: seeded synthetic weights')
 ap.add_argument('--gpu', type=int, default=0)
+ap.add_argument('--conv-algo', type=int, default=None, choices=[0, 1, 2], help='st_set_conv_algo (default: the engine\'s, 1)')
+ap.add_argument('--gram-algo', type=int, default=None, choices=[0, 1], help='st_set_gram_algo (default: the engine\'s, 0)')
 ap.add_argument('--grid', default='', help='RxC: tile-shard the image over this one GPU (large images)')
 args = ap.parse_args()
 
@@ -36,7 +38,7 @@ if args.grid:
     image = jobs.run_tiled_job(params, jobs.load_rgb(args.content), jobs.load_rgb(args.style), args.iters, (rows, cols), size=args.size,
                                style_size=args.style_size or None, device=args.gpu, optimizer=args.optimizer)
 else:
-    job = st2.StyleTransfer(st2.HipModel(params, device=args.gpu))
+    job = st2.StyleTransfer(st2.HipModel(params, device=args.gpu, conv_algo=args.conv_algo, gram_algo=args.gram_algo))
     image = jobs.run_job(job, jobs.load_rgb(args.content), jobs.load_rgb(args.style), args.iters, size=args.size,
                          style_size=args.style_size or None, optimizer=args.optimizer)
 Image.fromarray(np.uint8(np.clip(image, 0, 255))).save(args.out)

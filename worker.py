@@ -69,6 +69,29 @@ def setup_signals():
 
 
 # ---------------------------------------------------------------------------------------------------
+ALGO_KEYS = {'conv_algo': (0, 1, 2), 'gram_algo': (0, 1)}
+
+
+def read_algo_keys(config):
+    """The optional integer config keys that select the engine's arithmetic: ``conv_algo`` (0 direct, 1 Winograd on the fp32 matrix
+    cores, 2 split-operand Winograd) and ``gram_algo`` (0 fp32 matrix cores, 1 split operands).  Returns the HipModel keyword
+    arguments of the keys that are present (an absent key makes no call: the engine's default stays); a value outside a key's set is
+    a ValueError that names the key.  Pure: any mapping with ``get`` will do."""
+    kwargs = {}
+    for key, allowed in ALGO_KEYS.items():
+        raw = config.get(key, None)
+        if raw is None or str(raw).strip() == '':
+            continue
+        try:
+            value = int(str(raw).strip())
+        except ValueError:
+            value = None
+        if value not in allowed:
+            raise ValueError('config key %s = %r: must be one of %s' % (key, raw, ', '.join(map(str, allowed))))
+        kwargs[key] = value
+    return kwargs
+
+
 def build_transfer(config):
     """Model + StyleTransfer for this worker (reference worker.py:326-332).  Exits with code 2 when the
     HIP library, the GPU or the weights are missing."""
@@ -97,7 +120,7 @@ def build_transfer(config):
             raise st2.HipUnavailable('weights file %s not found (.npz or .caffemodel; or set weights = synthetic)'
                                      % weights_path)
         model = st2.HipModel(params, topology=None if topology == st2.VGG19_TOPOLOGY else topology, device=max(gpu, 0),
-                             precision=config.get('precision', 'fp32'))
+                             precision=config.get('precision', 'fp32'), **read_algo_keys(config))
         return st2.StyleTransfer(model)
     except Exception as err:  # HipUnavailable, StError, OSError ...
         print(BACKEND_MSG % err, file=sys.stderr)
