@@ -82,11 +82,19 @@ int st_blob_shape(st_ctx* ctx, int index, int H, int W, int* c, int* h, int* w);
 /* ---- model test hooks: CaffeModel.forward / backward (worker.py:77-106) ----------------------- */
 /* runs the net on a preprocessed (1,3,H,W) image up to blob `last_blob` (-1: whole net) */
 int st_forward(st_ctx* ctx, const float* x_nchw, int H, int W, int last_blob);
+/* The three hooks below read the ONE activation set of the context, which every evaluation overwrites: st_forward, and the
+ * forward inside st_opfunc / st_step / st_step_begin (then up to the deepest weighted blob).  They answer for the image
+ * that evaluation read or fail with ST_ERR_STATE / ST_ERR_ARG naming the blob: a blob above the last one computed; a blob
+ * the evaluation did not write in fp32 (the lean forward of an fp32 iteration skips pooled, un-weighted conv blobs, the
+ * bf16 flow of st_set_precision(ctx, 1) every fp32 blob only bf16 convs read); any blob after st_set_content / st_set_style,
+ * after the iterate was overwritten or resized (st_set_input*, st_resample_state) under an evaluation that read it. */
 int st_get_blob(st_ctx* ctx, int index, float* out_chw);
 /* ranged backward with per-blob diff injection after st_forward; diffs[i] is (C,h,w) of blob
- * blob_index[i]; writes d/d(data) as (3,H,W) */
+ * blob_index[i]; writes d/d(data) as (3,H,W).  After a lean evaluation it fails, naming the blob, where it would read
+ * an fp32 blob that evaluation did not write (a ReLU mask, the input of a pool without arg-max map). */
 int st_backward(st_ctx* ctx, int n, const int* blob_index, const float* const* diffs, float* out_grad);
-/* gram_matrix (worker.py:109-114) of a blob of the last st_forward: out is C*C */
+/* gram_matrix (worker.py:109-114) of a blob of the last st_forward: out is C*C.  Contracts the fp32 blob: refused, as
+ * st_get_blob refuses it, for a blob the last evaluation did not write in fp32. */
 int st_gram(st_ctx* ctx, int index, float* out);
 
 /* ---- image slots: StyleTransfer.set_input / set_content / set_style (worker.py:191-218) ------- */

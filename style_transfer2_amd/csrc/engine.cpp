@@ -387,6 +387,9 @@ int backward_chain(st_ctx* c, int top, const float* top_diff, const std::vector<
 int ensure_input_buffers(st_ctx* c, int H, int W)
 {
     if (c->H == H && c->W == W && c->x[0]) return ST_OK;
+    // the activations are those of the old geometry (blob "data" may be one of the buffers freed below; st_backward sizes its
+    // work buffers by the new one): the hooks refuse until the next forward
+    c->act.valid_to = -1;
     const size_t n3 = (size_t)3 * H * W;
     for (int i = 0; i < 2; ++i) { dfree(c->x[i]); ST_TRY(dmalloc(&c->x[i], n3)); }
     dfree(c->grad); ST_TRY(dmalloc(&c->grad, n3));
@@ -428,6 +431,14 @@ int preprocess_into(st_ctx* c, const void* hwc, int H, int W, int is_u8, float* 
     if (is_u8) HIP_TRY(launch_preprocess_u8((const uint8_t*)c->stage_dev, dst, H, W, c->stream));
     else HIP_TRY(launch_preprocess_f32((const float*)c->stage_dev, dst, H, W, c->stream));
     return ST_OK;
+}
+
+// The iterate is about to be overwritten.  After an evaluation blob "data" IS the iterate's buffer (ActSet::data[0] is borrowed):
+// the other blobs would no longer belong to it, so the hooks refuse until the next forward (st_forward's probe image has a buffer
+// of its own and stays valid).
+void iterate_overwritten(st_ctx* c)
+{
+    if (!c->act.data.empty() && c->act.data[0] && (c->act.data[0] == c->x[0] || c->act.data[0] == c->x[1])) c->act.valid_to = -1;
 }
 
 // an input of a new geometry: every size-dependent optimizer tensor starts from zero
@@ -825,6 +836,8 @@ int st_gram(st_ctx* c, int index, float* out)
     if (c) c->epoch++;       // anything but st_step may change what a step launches: captured step graphs are stale
     if (!c || index < 0 || index >= c->nb || !out) return fail(ST_ERR_ARG, "bad argument");
     if (index > c->act.valid_to) return fail(ST_ERR_STATE, "blob %d was not computed by the last forward", index);
+    // (the Gram contracts the fp32 blob: what the last evaluation did not write is an earlier evaluation's, or nothing)
+    if (!c->act.plan.fwd[index].out32) return fail(ST_ERR_STATE, "blob %d (%s) is not materialised in fp32 by the lean evaluation of an iteration: no Gram of it (st_opfunc / st_forward write every fp32 blob; bf16: st_set_precision(ctx, 2))", index, c->blob_names[index].c_str());
     HIP_TRY(hipSetDevice(c->device));
     const int C = c->act.C[index], hw = c->act.h[index] * c->act.w[index];
     float* g = nullptr;
@@ -846,6 +859,7 @@ int st_set_input(st_ctx* c, const void* hwc, int H, int W, int is_u8)
     if (!c) return fail(ST_ERR_ARG, "ctx is NULL");
     HIP_TRY(hipSetDevice(c->device));
     ST_TRY(set_input_common(c, H, W));
+    iterate_overwritten(c);
     ST_TRY(preprocess_into(c, hwc, H, W, is_u8, c->x[c->cur]));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return ST_OK;
@@ -857,6 +871,7 @@ int st_set_input_nchw(st_ctx* c, const float* x, int H, int W)
     if (!c || !x || H <= 0 || W <= 0) return fail(ST_ERR_ARG, "bad argument");
     HIP_TRY(hipSetDevice(c->device));
     ST_TRY(set_input_common(c, H, W));
+    iterate_overwritten(c);
     HIP_TRY(hipMemcpy(c->x[c->cur], x, (size_t)3 * H * W * sizeof(float), hipMemcpyHostToDevice));
     return ST_OK;
 }

@@ -309,6 +309,7 @@ int ensure_input_buffers(st_ctx* c, int H, int W);
 int stage_upload(st_ctx* c, const void* host, size_t bytes);
 int preprocess_into(st_ctx* c, const void* hwc, int H, int W, int is_u8, float* dst);
 int set_input_common(st_ctx* c, int H, int W);
+void iterate_overwritten(st_ctx* c);
 int content_from_device(st_ctx* c, const float* xdev, int H, int W);
 int ensure_content_features(st_ctx* c);           // features of content-weighted blobs dropped by st_set_weights: recompute from the kept image
 // ---------------------------------------------------------------------------------------- engine_route.cpp

@@ -72,6 +72,7 @@ int st_resample_state(st_ctx* c, const st_resample_table* lan_x, const st_resamp
     if (rc == ST_OK) rc = ensure_input_buffers(c, H2, W2);            // frees and re-creates x, m, v, L-BFGS vectors
     if (rc == ST_OK) {
         c->lb_clear = true; c->have_cur = false;
+        iterate_overwritten(c);                        // (a resample to the SAME size keeps the buffers)
         hip_ok(hipMemcpyAsync(c->x[c->cur], tx, n2 * sizeof(float), hipMemcpyDeviceToDevice, c->stream), "x copy");
         if (keep_m) hip_ok(hipMemcpyAsync(c->m, tm, n2 * sizeof(float), hipMemcpyDeviceToDevice, c->stream), "m copy");
         if (keep_v) hip_ok(hipMemcpyAsync(c->v, tv, n2 * sizeof(float), hipMemcpyDeviceToDevice, c->stream), "v copy");
