@@ -12,6 +12,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "st2_kernels.h"
+#include "env.h"
 
 namespace st2 {
 
@@ -432,8 +433,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_dgrad_first_f32q(const float* 
 // ST2_DGRAD_FIRST=1 routes fp32 here too, =0 neither; read per launch (the tests run every combination).
 bool conv_dgrad_first_ok(int Cout, int Cin, int H, int W, bool bf16)
 {
-    const char* e = getenv("ST2_DGRAD_FIRST");
-    const bool enabled = e && *e ? (*e == '1') : bf16;
+    const bool enabled = env_get("ST2_DGRAD_FIRST") ? env_on("ST2_DGRAD_FIRST") : bf16;
     return enabled && Cin >= 1 && Cin <= 3 && Cout >= 2 && Cout % (bf16 ? 16 : 2) == 0 && H >= 1 && W >= 1 &&
            (unsigned long long)H * W < 0x7fffffffull;
 }
@@ -443,8 +443,7 @@ bool conv_dgrad_first_ok(int Cout, int Cin, int H, int W, bool bf16)
 // unless ST2_DGRAD_FIRST_Q=1 (read per launch; the tests run it)
 bool conv_dgrad_first_quad_ok(int Cout, int Cin, int H, int W, const float* dy)
 {
-    const char* e = getenv("ST2_DGRAD_FIRST_Q");
-    return (e && *e == '1') && Cin >= 1 && Cin <= 3 && Cout >= 2 && Cout % 2 == 0 && W % 4 == 0 && H >= 1 &&
+    return env_on("ST2_DGRAD_FIRST_Q") && Cin >= 1 && Cin <= 3 && Cout >= 2 && Cout % 2 == 0 && W % 4 == 0 && H >= 1 &&
            (unsigned long long)H * W < 0x7fffffffull && (reinterpret_cast<uintptr_t>(dy) & 15) == 0;
 }
 
@@ -480,8 +479,7 @@ static dim3 dgrad_strip_grid(int H, int W, int* seg_out)
 // fp32 strip walker: Cout = 64, tensor below 4 GiB (32-bit buffer offsets); ST2_DGRAD_FIRST_STRIP=0 switches it off (read per launch)
 bool conv_dgrad_first_strip_ok(int Cout, int Cin, int H, int W)
 {
-    const char* e = getenv("ST2_DGRAD_FIRST_STRIP");
-    return !(e && *e == '0') && Cout == 64 && Cin >= 1 && Cin <= 3 && H >= 1 && W >= 1 && 4ull * Cout * H * W < 0xfffffff0ull;
+    return !env_off("ST2_DGRAD_FIRST_STRIP") && Cout == 64 && Cin >= 1 && Cin <= 3 && H >= 1 && W >= 1 && 4ull * Cout * H * W < 0xfffffff0ull;
 }
 
 hipError_t launch_conv3x3_dgrad_first_strip(const float* dy, const float* w, float* dx, const float* inject, int Cout, int Cin, int H, int W, hipStream_t s)
@@ -516,9 +514,8 @@ hipError_t launch_conv3x3_dgrad_first16(const unsigned short* dy16, const float*
     if (!conv_dgrad_first_ok(Cout, Cin, H, W, true) || (reinterpret_cast<uintptr_t>(dy16) & 15) != 0) return hipErrorInvalidValue;
     const uint4* q16 = reinterpret_cast<const uint4*>(dy16);
     {   // Cout = 64: the strip walker (ST2_DGRAD_FIRST_STRIP=0: the tile kernel; read per launch, the tests compare both)
-        const char* e = getenv("ST2_DGRAD_FIRST_STRIP");
         const unsigned long long bytes = 16ull * (Cout / 8) * H * W;
-        if (!(e && *e == '0') && Cout == 64 && bytes < 0xfffffff0ull) {
+        if (!env_off("ST2_DGRAD_FIRST_STRIP") && Cout == 64 && bytes < 0xfffffff0ull) {
             int seg = 0;
             const dim3 grid = dgrad_strip_grid(H, W, &seg);
             switch (Cin) {

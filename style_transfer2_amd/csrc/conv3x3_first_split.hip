@@ -17,6 +17,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "st2_kernels.h"
+#include "env.h"
 
 namespace st2 {
 
@@ -217,8 +218,7 @@ __global__ __launch_bounds__(256, MT <= 2 ? 4 : 3) void conv3x3_first_split_k(co
 // ST2_FIRST_SPLIT=0: the fp32-matrix-core kernel for this layer (read per launch; the tests compare both)
 bool conv_first_split_ok(int Cin, int Cout, int H, int W)
 {
-    const char* e = getenv("ST2_FIRST_SPLIT");
-    if (e && *e == '0') return false;
+    if (env_off("ST2_FIRST_SPLIT")) return false;
     return Cin == FS_MAXC && Cout >= 32 && Cout % 32 == 0 && Cout <= FS_MAXM && H >= 1 && W >= 1 && (unsigned long long)H * W * Cout < 0x7fffffffull * 2;
 }
 

@@ -15,6 +15,7 @@
 // The next chunk's global loads are issued before the MFMA block and parked in registers.
 // fp32 MFMA == a k-ordered fmaf chain, so results are plain IEEE fp32.
 #include "st2_kernels.h"
+#include "env.h"
 #include <type_traits>
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
@@ -502,9 +503,9 @@ hipError_t launch_conv3x3_cfg(const ConvProblem& p, int cfg, hipStream_t s)
 hipError_t launch_conv3x3(const ConvProblem& p, hipStream_t s)
 {
     // ST2_CONV_CFG=<id> forces one tile configuration (debugging / tests of every configuration)
-    static const int forced = [] { const char* e = getenv("ST2_CONV_CFG"); return e ? atoi(e) : -1; }();
+    const long long forced = env_int("ST2_CONV_CFG", -1);
     if (forced >= 0 && !((forced == 0 || forced == 1 || forced == 5 || forced == 6) && p.MPad % 128 != 0))
-        return launch_conv3x3_cfg(p, forced, s);
+        return launch_conv3x3_cfg(p, (int)forced, s);
     return launch_conv3x3_cfg(p, -1, s);
 }
 
@@ -519,8 +520,7 @@ static void style_tile(int C, int H, int W, int* bm, int* rows)
     if (C <= 64) { *bm = 64; *rows = 8; return; }
     *bm = 128; *rows = 4;
     const long long blocks = (long long)((W + 31) / 32) * ((H + 3) / 4) * (conv_mpad(C) / 128);
-    const char* e = getenv("ST2_STYLE_SMALL");
-    if (blocks < 256 && conv_mpad(C) % 64 == 0 && !(e && *e == '0')) *bm = 64;
+    if (blocks < 256 && conv_mpad(C) % 64 == 0 && !env_off("ST2_STYLE_SMALL")) *bm = 64;
 }
 
 int style_grad_blocks(int C, int H, int W)
@@ -603,8 +603,8 @@ __global__ __launch_bounds__(256) void style_grad_big_k(const float* __restrict_
 }
 static bool style_big(int C, int H, int W)
 {
-    const char* fb = getenv("ST2_STYLE_FORCE_BIG");         // test hook: =1 runs the 64-bit-addressed kernel on blobs of any size
-    return 4ull * C * H * W >= 0xfffffff0ull || (fb && *fb == '1' && ((size_t)H * W) % 4 == 0);
+    // test hook: ST2_STYLE_FORCE_BIG=1 runs the 64-bit-addressed kernel on blobs of any size
+    return 4ull * C * H * W >= 0xfffffff0ull || (((size_t)H * W) % 4 == 0 && env_on("ST2_STYLE_FORCE_BIG"));
 }
 
 hipError_t launch_style_grad(const float* Dp, const float* F, float* dst, float c2, int fused, float sw, const float* norm,
@@ -941,17 +941,14 @@ hipError_t launch_conv3x3_dgrad_smallM(const float* dy, const float* w, float* d
                                        int Cout, int Cin, int H, int W, hipStream_t s)
 {
     if (!conv_dgrad_smallM_ok(Cout, Cin)) return hipErrorInvalidValue;
-    {   // ST2_DGRAD_FIRST selects among the older kernels when it is set; unset, the strip walker takes the layer it is built for
-        const char* e = getenv("ST2_DGRAD_FIRST");
-        if (!(e && *e) && conv_dgrad_first_strip_ok(Cout, Cin, H, W)) return launch_conv3x3_dgrad_first_strip(dy, w, dx, inject, Cout, Cin, H, W, s);
-    }
+    // ST2_DGRAD_FIRST selects among the older kernels when it is set; unset, the strip walker takes the layer it is built for
+    if (!env_get("ST2_DGRAD_FIRST") && conv_dgrad_first_strip_ok(Cout, Cin, H, W)) return launch_conv3x3_dgrad_first_strip(dy, w, dx, inject, Cout, Cin, H, W, s);
     if (conv_dgrad_first_quad_ok(Cout, Cin, H, W, dy)) return launch_conv3x3_dgrad_first_quad(dy, w, dx, inject, Cout, Cin, H, W, s);        // matrix cores, quads
     if (conv_dgrad_first_ok(Cout, Cin, H, W, false)) return launch_conv3x3_dgrad_first(dy, w, dx, inject, Cout, Cin, H, W, s);              // matrix cores
     dim3 grid((W + SM_TX - 1) / SM_TX, (H + SM_TY - 1) / SM_TY);
     {   // LDS-DMA staging where the layout allows it (ST2_DGRAD_SMALLM_DMA=0: the register-staged kernel; read per launch: A/B runs)
-        const char* e = getenv("ST2_DGRAD_SMALLM_DMA");
         const unsigned long long bytes = 4ull * Cout * H * W;
-        if (!(e && *e == '0') && W % 4 == 0 && bytes < 0xfffffff0ull && (reinterpret_cast<uintptr_t>(dy) & 15) == 0 &&
+        if (!env_off("ST2_DGRAD_SMALLM_DMA") && W % 4 == 0 && bytes < 0xfffffff0ull && (reinterpret_cast<uintptr_t>(dy) & 15) == 0 &&
             (reinterpret_cast<uintptr_t>(dx) & 15) == 0 && (!inject || (reinterpret_cast<uintptr_t>(inject) & 15) == 0)) {
             switch (Cin) {
             case 1: conv3x3_dgrad_smallM_dma<1><<<grid, dim3(256), 0, s>>>(dy, (unsigned)bytes, w, dx, inject, Cout, H, W); break;

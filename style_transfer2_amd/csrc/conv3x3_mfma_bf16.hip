@@ -19,6 +19,7 @@
 //      w_s  [9 taps][2 blocks][BM][8 bf16]      in_s [2 blocks][ROWS+2][34 px][8 bf16]
 // A chunk is 16 input channels x 9 taps = 9 k-steps; three operand register sets rotate (9 is odd).
 #include "st2_kernels.h"
+#include "env.h"
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <string.h>
@@ -1014,71 +1015,88 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_mfma_bf16_64x512_dgb16i(const C
 __global__ __launch_bounds__(NT, 2) void conv3x3_mfma_bf16_64x256_f16(const Conv16KArgs a) { conv16_body<64, 8, 1, 4, false, false, false, false, false, 1>(a); }
 __global__ __launch_bounds__(NT, 2) void conv3x3_mfma_bf16_64x256_dgb16(const Conv16KArgs a) { conv16_body<64, 8, 1, 4, false, false, true, true, false, 3>(a); }
 
-static int conv16_pick_cfg(const Conv16Problem& p)
+Conv16Launch conv16_resolve(const Conv16Problem& p)
 {
-    const char* env = getenv("ST2_CONV16_CFG");             // forces one tile configuration (tests of every configuration)
-    const int forced = env && *env ? atoi(env) : -1;
+    Conv16Launch c{};
     const long long tx = (p.W + 31) / 32;
-    const char* big = getenv("ST2_CONV16_BIG_MIN");         // tuning knob: least number of 64x512 workgroups that selects that tile
-    const long long big_min = big && *big ? atoll(big) : 512;
-    int cfg;                                               // 0: 64x256px, 1: 128x128px, 2: 64x128px, 3: 64x512px
-    if (forced >= 0) cfg = forced;
-    else if (tx * ((p.H + 15) / 16) * (p.MPad / 64) >= big_min) cfg = 3;    // enough workgroups even at 512 pixels each
-    else cfg = (tx * ((p.H + 7) / 8) * (p.MPad / 64) >= 512) ? 0 : 2;
-    if (cfg == 1 && p.MPad % 128 != 0) cfg = 0;
-    if (cfg > 3) cfg = 0;
-    return cfg;
-}
-
-// may this launch pool its own output (Conv16Problem::pool16 / pool32 / amap)?  Needs a tile configuration whose waves
-// hold two rows (0 and 1) and M % 8 == 0 (channel-blocked outputs).
-bool conv16_can_pool(const Conv16Problem& p) { return conv16_pick_cfg(p) != 2 && p.M % 8 == 0; }
-
-// may a data-gradient launch of this shape take the pooled diff + the pool's arg-max map (Conv16Problem::unpool_amap)?  The 64 x 512
-// and 64 x 256 pixel tiles have the build; even H and W (every window whole).  ST2_CONV16_UNPOOL=0: keep maxpool_bwd_idx16_k (read per call).
-bool conv16_can_unpool(const Conv16Problem& p)
-{
-    const char* e = getenv("ST2_CONV16_UNPOOL");
-    if (e && *e == '0') return false;
+    const long long forced = env_int("ST2_CONV16_CFG", -1);        // forces one tile configuration (tests of every configuration)
+    const long long big_min = env_int("ST2_CONV16_BIG_MIN", 512);  // tuning knob: least number of 64x512 workgroups that selects that tile
+    if (forced >= 0) c.cfg = (int)forced;
+    else if (tx * ((p.H + 15) / 16) * (p.MPad / 64) >= big_min) c.cfg = 3;    // enough workgroups even at 512 pixels each
+    else c.cfg = (tx * ((p.H + 7) / 8) * (p.MPad / 64) >= 512) ? 0 : 2;
+    if (c.cfg == 1 && p.MPad % 128 != 0) c.cfg = 0;
+    if (c.cfg > 3) c.cfg = 0;
+    const bool wide = c.cfg == 3 || c.cfg == 0;                    // the tiles with the UNPOOL and the single-buffer builds
+    // short reductions (K <= ST2_CONV16_SB_MAXK, default 64): the 64x256 tile with ONE staging buffer, four workgroups per CU (120
+    // registers, 29 KiB of LDS each since the forward / data-gradient epilogues became builds of their own).  Measured in isolation
+    // (tools/probes/conv16_shallow.sh, 2048^2 job): conv1_2 forward with its pool 386 -> 344 us, conv2_1 forward 186 -> 175, K = 128: 279 -> 268;
+    // in the 2048^2 bf16 job: forward class 2.507 -> 2.466 ms with 64, the same with 128 but the data gradients +0.01 (profiles/r04_k_bf16_sb_ab.txt)
+    // (read per launch: the tests compare both pipelines; the unpooling builds are double-buffered)
+    c.sb = wide && !p.unpool_amap && p.K <= env_int("ST2_CONV16_SB_MAXK", 64);
+    if (c.sb) c.cfg = 0;
+    c.BM = c.cfg == 1 ? 128 : 64; c.ROWS = c.cfg == 0 ? 8 : c.cfg == 3 ? 16 : 4;
+    // a tile whose waves hold two rows and M % 8 == 0 (channel-blocked outputs)
+    c.can_pool = c.cfg != 2 && p.M % 8 == 0;
+    // even H and W (every window whole), whole 16-channel chunks; ST2_CONV16_UNPOOL=0: keep maxpool_bwd_idx16_k;
     // ... and K <= 128 (ST2_CONV16_UNPOOL_MAXK): the expansion costs the launch about as much per pooled element as the separate kernel
     // did, which pays where that kernel's full-resolution output was the expense -- measured at 2048^2: conv1_2 -145 + 0 us,
     // conv2_2 -73 + 12, conv3_4 -39 + 32, conv4_4 -24 + 33
-    const char* mk = getenv("ST2_CONV16_UNPOOL_MAXK");
-    if (p.K > (mk && *mk ? atoi(mk) : 128)) return false;
-    const int cfg = conv16_pick_cfg(p);
-    return (cfg == 3 || cfg == 0) && p.H % 2 == 0 && p.W % 2 == 0 && p.K % 16 == 0;      // whole windows, whole 16-channel chunks
+    c.can_unpool = wide && p.H % 2 == 0 && p.W % 2 == 0 && p.K % 16 == 0 && !env_off("ST2_CONV16_UNPOOL") && p.K <= env_int("ST2_CONV16_UNPOOL_MAXK", 128);
+    return c;
 }
+
+namespace {
+enum Conv16Form { C16_FWD, C16_DG, C16_DGB, C16_DIAG };      // plain epilogue; data gradient; ... masked by a sign map; stamped forward (tools/probes)
+struct Conv16Build { void (*kernel)(const Conv16KArgs); int cfg; bool sb; Conv16Form form; bool unpool; int epi; };   // epi 0: the general epilogue (any kind), 1..5: that kind's (conv16_body, EPI)
+// every build, the specialised epilogues first: the first row whose facts are the launch's runs, and a launch without a row has no build
+#define ST2_CONV16_ROWS3(NAME, CFG, SB) {NAME, CFG, SB, C16_FWD, false, 0}, {NAME##_dg, CFG, SB, C16_DG, false, 0}, {NAME##_dgb, CFG, SB, C16_DGB, false, 0}
+const Conv16Build kConv16Builds[] = {
+    //                                   tile sb     form      unpool epi
+    {conv3x3_mfma_bf16_64x512_f16o,       3, false, C16_FWD,  false, 4},
+    {conv3x3_mfma_bf16_64x512_dgb16i,     3, false, C16_DGB,  false, 5},
+    {conv3x3_mfma_bf16_64x256_sb_f16,     0, true,  C16_FWD,  false, 1},
+    {conv3x3_mfma_bf16_64x256_sb_pool,    0, true,  C16_FWD,  false, 2},
+    {conv3x3_mfma_bf16_64x512_f16,        3, false, C16_FWD,  false, 1},
+    {conv3x3_mfma_bf16_64x512_pool,       3, false, C16_FWD,  false, 2},
+    {conv3x3_mfma_bf16_64x512_dgb16,      3, false, C16_DGB,  false, 3},
+    {conv3x3_mfma_bf16_64x512_unpool_b16, 3, false, C16_DGB,  true,  3},
+    {conv3x3_mfma_bf16_64x256_f16,        0, false, C16_FWD,  false, 1},
+    {conv3x3_mfma_bf16_64x256_dgb16,      0, false, C16_DGB,  false, 3},
+    ST2_CONV16_ROWS3(conv3x3_mfma_bf16_64x256_sb, 0, true ),
+    {conv3x3_mfma_bf16_64x256_sb_diag,    0, true,  C16_DIAG, false, 0},
+    ST2_CONV16_ROWS3(conv3x3_mfma_bf16_64x512, 3, false),
+    {conv3x3_mfma_bf16_64x512_unpool,     3, false, C16_DG,   true,  0},
+    {conv3x3_mfma_bf16_64x512_unpool_b,   3, false, C16_DGB,  true,  0},
+    {conv3x3_mfma_bf16_64x512_diag,       3, false, C16_DIAG, false, 0},
+    ST2_CONV16_ROWS3(conv3x3_mfma_bf16_64x256, 0, false),
+    {conv3x3_mfma_bf16_64x256_unpool,     0, false, C16_DG,   true,  0},
+    {conv3x3_mfma_bf16_64x256_unpool_b,   0, false, C16_DGB,  true,  0},
+    ST2_CONV16_ROWS3(conv3x3_mfma_bf16_128x128, 1, false),
+    ST2_CONV16_ROWS3(conv3x3_mfma_bf16_64x128, 2, false),
+};
+#undef ST2_CONV16_ROWS3
+}  // namespace
 
 hipError_t launch_conv3x3_bf16(const Conv16Problem& p, hipStream_t s)
 {
     if (p.MPad % kCoutQuantum != 0 || p.MPad < p.M) return hipErrorInvalidValue;
     if ((p.out16 || p.mask16) && p.M % 8 != 0) return hipErrorInvalidValue;
+    const Conv16Launch c = conv16_resolve(p);
     const bool pools = p.pool16 || p.pool32 || p.amap;
-    if (pools && !conv16_can_pool(p)) return hipErrorInvalidValue;
+    if (pools && !c.can_pool) return hipErrorInvalidValue;
     if (!p.out && !p.out16 && !pools) return hipErrorInvalidValue;          // nothing to write
-    const long long tx = (p.W + 31) / 32;
-    int cfg = conv16_pick_cfg(p);
-    // short reductions (K <= ST2_CONV16_SB_MAXK, default 64): the 64x256 tile with ONE staging buffer, four workgroups per CU (120
-    // registers, 29 KiB of LDS each since the forward / data-gradient epilogues became builds of their own).  Measured in isolation
-    // (tools/probes/conv16_shallow.sh, 2048^2 job): conv1_2 forward with its pool 386 -> 344 us, conv2_1 forward 186 -> 175, K = 128: 279 -> 268;
-    // in the 2048^2 bf16 job: forward class 2.507 -> 2.466 ms with 64, the same with 128 but the data gradients +0.01 (profiles/r04_k_bf16_sb_ab.txt)
-    const char* sbe = getenv("ST2_CONV16_SB_MAXK");          // read per launch: the tests compare both pipelines
-    const int sb_maxk = sbe && *sbe ? atoi(sbe) : 64;
-    const bool sb = p.K <= sb_maxk && (cfg == 3 || cfg == 0) && !p.unpool_amap;       // (the unpooling builds are double-buffered)
-    if (sb) cfg = 0;
-    const int BM = cfg == 1 ? 128 : 64, ROWS = cfg == 0 ? 8 : cfg == 3 ? 16 : 4;
     Conv16KArgs k{};
     k.in16 = p.in16; k.wpack = p.wpack16; k.bias = p.bias; k.out = p.out; k.out16 = p.out16;
     k.mask_src = p.mask_src; k.inject = p.inject; k.mask16 = p.mask16;
     k.pool16 = p.pool16; k.pool32 = p.pool32; k.amap = p.amap; k.pool_h = (p.H + 1) / 2; k.pool_w = (p.W + 1) / 2;
     k.K = p.K; k.M = p.M; k.MPad = p.MPad; k.H = p.H; k.W = p.W;
     k.nch = (p.K + 15) / 16;
-    k.tiles_x = (int)tx; k.tiles_y = (p.H + ROWS - 1) / ROWS; k.n_mtiles = p.MPad / BM; k.relu = p.relu;
+    k.tiles_x = (p.W + 31) / 32; k.tiles_y = (p.H + c.ROWS - 1) / c.ROWS; k.n_mtiles = p.MPad / c.BM; k.relu = p.relu;
     if ((p.bits_out || p.mask_bits) && p.M % 32 != 0) return hipErrorInvalidValue;
     if (p.bits_out && (!p.out16 || (reinterpret_cast<uintptr_t>(p.bits_out) & 3) != 0)) return hipErrorInvalidValue;
     k.bits_out = p.bits_out; k.mask_bits = p.mask_bits;
     const bool unpool = p.unpool_amap != nullptr;
-    if (unpool && (!conv16_can_unpool(p) || pools)) return hipErrorInvalidValue;
+    if (unpool && (!c.can_unpool || pools)) return hipErrorInvalidValue;
     k.up_amap = p.unpool_amap; k.up_h = p.H / 2; k.up_w = p.W / 2;
     const unsigned long long in_bytes = 16ull * ((p.K + 7) / 8) * (unpool ? (unsigned long long)k.up_h * k.up_w : (unsigned long long)p.H * p.W),
                              w_bytes = 2ull * conv16_pack_elems(p.K, p.M);
@@ -1096,48 +1114,33 @@ hipError_t launch_conv3x3_bf16(const Conv16Problem& p, hipStream_t s)
     // which epilogue: the data-gradient build iff the launch uses one of its options; both directions' options together have no build
     const bool dg = p.mask_src || p.mask16 || p.mask_bits || p.inject || p.s_in16 || unpool;
     if (dg && (p.bias || p.relu || pools || p.bits_out)) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)nblk), block(NT);
-    if (p.stamps) {                                                              // measurement builds: forward launches of two tiles
-        if (dg || !(cfg == 3 || (cfg == 0 && sb))) return hipErrorInvalidValue;
-        k.stamps = p.stamps;
-        { const char* nd = getenv("ST2_BENCH_NODMA"); k.diag_nodma = nd && *nd == '1'; }
-        { const char* sg = getenv("ST2_BENCH_STAGGER"); k.diag_stagger = sg && *sg ? atoi(sg) : 0; }
-        if (sb) conv3x3_mfma_bf16_64x256_sb_diag<<<grid, block, 0, s>>>(k); else conv3x3_mfma_bf16_64x512_diag<<<grid, block, 0, s>>>(k);
-        return hipGetLastError();
-    }
     const bool mb = p.mask_bits != nullptr;
-    if (mb && (p.mask_src || p.mask16)) return hipErrorInvalidValue;            // one form of the mask per launch
-    // one epilogue per launch kind (conv16_body, EPI) where the launch is one of those kinds; ST2_CONV16_EPI=0: the general epilogue (read per launch: tests)
+    Conv16Form form = mb ? C16_DGB : dg ? C16_DG : C16_FWD;
     int epi = 0;
-    {
-        const char* ee = getenv("ST2_CONV16_EPI");
-        const bool kinds = !(ee && *ee == '0') && p.M % BM == 0 && !p.mask_src && !p.mask16 && !p.pool32;
+    if (p.stamps) {                                                             // measurement builds: forward launches of two tiles
+        if (dg) return hipErrorInvalidValue;
+        form = C16_DIAG;
+        k.stamps = p.stamps; k.diag_nodma = env_on("ST2_BENCH_NODMA"); k.diag_stagger = (int)env_int("ST2_BENCH_STAGGER", 0);
+    } else {
+        if (mb && (p.mask_src || p.mask16)) return hipErrorInvalidValue;        // one form of the mask per launch
+        // one epilogue per launch kind (conv16_body, EPI) where the launch is one of those kinds and its tile has the build;
+        // ST2_CONV16_EPI=0: the general epilogue (read per launch: tests)
+        const bool kinds = p.M % c.BM == 0 && !p.mask_src && !p.mask16 && !p.pool32 && !env_off("ST2_CONV16_EPI");
         const bool lean16 = kinds && !p.out && !p.inject;
         if (lean16 && !dg && p.out16 && !pools) epi = 1;
         else if (lean16 && !dg && pools && p.pool16 && p.amap && !p.out16 && !p.bits_out && p.H % 2 == 0 && p.W % 2 == 0) epi = 2;
         else if (lean16 && dg && mb && p.out16) epi = 3;
-        else if (kinds && !dg && p.out && p.out16 && !pools && !p.inject && cfg == 3 && !sb) epi = 4;
-        else if (kinds && dg && mb && p.out16 && !p.out && p.inject && cfg == 3 && !unpool) epi = 5;
-        const char* ek = getenv("ST2_CONV16_EPI_KINDS");     // bit (kind - 1): that kind may run (default: all five)
-        if (epi && ek && *ek && !((atoi(ek) >> (epi - 1)) & 1)) epi = 0;
+        else if (kinds && !dg && p.out && p.out16 && !pools && !p.inject && c.cfg == 3) epi = 4;
+        else if (kinds && dg && mb && p.out16 && !p.out && p.inject && c.cfg == 3 && !unpool) epi = 5;
+        // ST2_CONV16_EPI_KINDS: bit (kind - 1): that kind may run (default: all five)
+        if (epi && !((env_int("ST2_CONV16_EPI_KINDS", 31) >> (epi - 1)) & 1)) epi = 0;
     }
-    if (epi == 4) { conv3x3_mfma_bf16_64x512_f16o<<<grid, block, 0, s>>>(k); return hipGetLastError(); }
-    if (epi == 5) { conv3x3_mfma_bf16_64x512_dgb16i<<<grid, block, 0, s>>>(k); return hipGetLastError(); }
-    if (epi && cfg == 0 && sb && !dg) { if (epi == 1) conv3x3_mfma_bf16_64x256_sb_f16<<<grid, block, 0, s>>>(k); else conv3x3_mfma_bf16_64x256_sb_pool<<<grid, block, 0, s>>>(k); return hipGetLastError(); }
-    if (epi && cfg == 3 && !dg) { if (epi == 1) conv3x3_mfma_bf16_64x512_f16<<<grid, block, 0, s>>>(k); else conv3x3_mfma_bf16_64x512_pool<<<grid, block, 0, s>>>(k); return hipGetLastError(); }
-    if (epi == 3 && cfg == 3) { if (unpool) conv3x3_mfma_bf16_64x512_unpool_b16<<<grid, block, 0, s>>>(k); else conv3x3_mfma_bf16_64x512_dgb16<<<grid, block, 0, s>>>(k); return hipGetLastError(); }
-    if (epi == 1 && cfg == 0 && !sb) { conv3x3_mfma_bf16_64x256_f16<<<grid, block, 0, s>>>(k); return hipGetLastError(); }
-    if (epi == 3 && cfg == 0 && !sb && !unpool) { conv3x3_mfma_bf16_64x256_dgb16<<<grid, block, 0, s>>>(k); return hipGetLastError(); }
-#define ST2_CONV16_LAUNCH3(NAME) do { if (mb) NAME##_dgb<<<grid, block, 0, s>>>(k); else if (dg) NAME##_dg<<<grid, block, 0, s>>>(k); else NAME<<<grid, block, 0, s>>>(k); } while (0)
-    if (cfg == 0 && sb) ST2_CONV16_LAUNCH3(conv3x3_mfma_bf16_64x256_sb);
-    else if (cfg == 3 && unpool) { if (mb) conv3x3_mfma_bf16_64x512_unpool_b<<<grid, block, 0, s>>>(k); else conv3x3_mfma_bf16_64x512_unpool<<<grid, block, 0, s>>>(k); }
-    else if (cfg == 0 && unpool) { if (mb) conv3x3_mfma_bf16_64x256_unpool_b<<<grid, block, 0, s>>>(k); else conv3x3_mfma_bf16_64x256_unpool<<<grid, block, 0, s>>>(k); }
-    else if (cfg == 3) ST2_CONV16_LAUNCH3(conv3x3_mfma_bf16_64x512);
-    else if (cfg == 0) ST2_CONV16_LAUNCH3(conv3x3_mfma_bf16_64x256);
-    else if (cfg == 1) ST2_CONV16_LAUNCH3(conv3x3_mfma_bf16_128x128);
-    else ST2_CONV16_LAUNCH3(conv3x3_mfma_bf16_64x128);
-#undef ST2_CONV16_LAUNCH3
-    return hipGetLastError();
+    for (const Conv16Build& b : kConv16Builds) {
+        if (b.cfg != c.cfg || b.sb != c.sb || b.form != form || b.unpool != unpool || (b.epi != epi && b.epi != 0)) continue;
+        b.kernel<<<dim3((unsigned)nblk), dim3(NT), 0, s>>>(k);
+        return hipGetLastError();
+    }
+    return hipErrorInvalidValue;                    // no such build (a stamped launch of another tile)
 }
 
 // Max-pool backward from the arg-max map of the fused forward pool, all operands channel-blocked:

@@ -45,6 +45,7 @@
 #include <string.h>
 #include <type_traits>
 #include "st2_kernels.h"
+#include "env.h"
 
 namespace st2 {
 
@@ -564,35 +565,24 @@ static void ws_pack(const float* w, int Cout, int Cin, bool dgrad, unsigned shor
 void pack_wino_split_weights_fwd(const float* w, int Cout, int Cin, unsigned short* dst) { ws_pack(w, Cout, Cin, false, dst); }
 void pack_wino_split_weights_dgrad(const float* w, int Cout, int Cin, unsigned short* dst) { ws_pack(w, Cout, Cin, true, dst); }
 
-bool conv_wino_split_ok(int K, int M, int H, int W)
+WinoLaunch wino_split_resolve(int K, int M, int H, int W)
 {
-    if (!(K >= 16 && K % 16 == 0 && M >= 64 && M % 64 == 0 && W >= 4 && W % 4 == 0 && H >= 1)) return false;
-    return 4ull * K * H * W < 0xfffffff0ull && 4ull * M * H * W < 0xfffffff0ull && 2ull * wino_split_pack_elems(K, M) < 0xfffffff0ull;
+    WinoLaunch w{};
+    w.variant = WV_64x256; w.quad = W % 4 == 0; w.bm = 64; w.prows = 8;
+    w.nblk = (long long)((W + 31) / 32) * ((H + 7) / 8) * (M / 64);
+    w.ok = K >= 16 && K % 16 == 0 && M >= 64 && M % 64 == 0 && W >= 4 && w.quad && H >= 1 &&
+           4ull * K * H * W < 0xfffffff0ull && 4ull * M * H * W < 0xfffffff0ull && 2ull * wino_split_pack_elems(K, M) < 0xfffffff0ull;
+    w.splits = (w.ok && !env_off("ST2_WINO_SPLITK")) ? wino_splitk(w.nblk, K / WS_CH) : 1;
+    w.can_pool = w.ok && w.splits == 1 && !env_off("ST2_WINO_POOL");
+    w.pool_amap = w.can_skip_out = w.can_pool && H % 2 == 0;
+    return w;                                       // (no BIG builds, no unpooling input transform)
 }
-
-// Split-K factor for a launch that would leave most CUs idle (conv5_1 at 1024^2: 128 workgroups on 256 CUs)
-int conv_wino_split_splits(int K, int M, int H, int W)
-{
-    static const bool off = [] { const char* e = getenv("ST2_WINO_SPLITK"); return e && *e == '0'; }();
-    if (off || !conv_wino_split_ok(K, M, H, W)) return 1;
-    const long long nblk = (long long)((W + 31) / 32) * ((H + 7) / 8) * (M / 64);
-    const int nch = K / WS_CH;
-    int sp = 1;
-    while (nblk * sp * 2 <= 256 && nch % (sp * 2) == 0 && nch / (sp * 2) >= 4 && sp < 16) sp *= 2;
-    return sp;
-}
-bool conv_wino_split_can_pool(int K, int M, int H, int W)
-{
-    static const bool off = [] { const char* e = getenv("ST2_WINO_POOL"); return e && *e == '0'; }();
-    return !off && conv_wino_split_ok(K, M, H, W) && conv_wino_split_splits(K, M, H, W) == 1;
-}
-bool conv_wino_split_pool_amap_ok(int K, int M, int H, int W) { return conv_wino_split_can_pool(K, M, H, W) && H % 2 == 0; }
-bool conv_wino_split_can_skip_out(int K, int M, int H, int W) { return conv_wino_split_pool_amap_ok(K, M, H, W); }
 
 // p.wpack = the split pack (pack_wino_split_weights_*, passed as const float*); the ConvProblem fields of launch_conv3x3_wino but unpool_amap
 hipError_t launch_conv3x3_wino_split(const ConvProblem& p, hipStream_t s)
 {
-    if (!conv_wino_split_ok(p.K, p.M, p.H, p.W) || (reinterpret_cast<uintptr_t>(p.in) & 15) != 0 || p.unpool_amap) return hipErrorInvalidValue;
+    const WinoLaunch w = wino_split_resolve(p.K, p.M, p.H, p.W);
+    if (!w.ok || (reinterpret_cast<uintptr_t>(p.in) & 15) != 0 || p.unpool_amap) return hipErrorInvalidValue;
     WsKArgs k{};
     k.in = p.in; k.upack = reinterpret_cast<const uint4*>(p.wpack); k.bias = p.bias; k.out = p.out;
     k.mask_src = p.mask_src; k.inject = p.inject;
@@ -601,21 +591,18 @@ hipError_t launch_conv3x3_wino_split(const ConvProblem& p, hipStream_t s)
     k.in_bytes = (unsigned)(4ull * p.K * p.H * p.W);
     k.u_bytes = (unsigned)(2ull * wino_split_pack_elems(p.K, p.M));
     k.stamps = p.stamps;
-    const long long nblk = (long long)k.tiles_x * k.tiles_y * (p.M / 64);
-    if (nblk <= 0 || nblk > 0x7fffffffLL) return hipErrorInvalidValue;
+    if (w.nblk <= 0 || w.nblk > 0x7fffffffLL) return hipErrorInvalidValue;
     k.splits = 1; k.scratch = nullptr;
     k.pool_out = p.pool_out; k.pool_h = (p.H + 1) / 2; k.pool_w = (p.W + 1) / 2;
-    k.pool_amap = p.pool_out ? p.pool_amap : nullptr;
-    if (p.scratch) {
-        const int sp = conv_wino_split_splits(p.K, p.M, p.H, p.W);
-        if (sp > 1 && p.scratch_floats >= (size_t)sp * p.M * p.H * p.W) { k.splits = sp; k.scratch = p.scratch; }
-    }
-    if (k.splits > 1 && p.pool_out) return hipErrorInvalidValue;              // the caller asks conv_wino_split_can_pool() first
+    k.pool_amap = p.pool_out ? p.pool_amap : nullptr;      // quiet: pool_amap without pool_out is ignored
+    // quiet: without scratch, or with too little of it, the launch runs in one pass
+    if (w.splits > 1 && p.scratch && p.scratch_floats >= (size_t)w.splits * p.M * p.H * p.W) { k.splits = w.splits; k.scratch = p.scratch; }
+    if (k.splits > 1 && p.pool_out) return hipErrorInvalidValue;              // the planner reads can_pool first
     if (p.pool_amap && p.pool_out && p.H % 2 != 0) return hipErrorInvalidValue;
     // out == nullptr: only with the fused pool AND its arg-max map, one pass, no mask / inject
     const bool noout = !p.out;
     if (noout && (!k.pool_out || !k.pool_amap || k.splits > 1 || p.mask_src || p.inject)) return hipErrorInvalidValue;
-    const dim3 g((unsigned)(nblk * k.splits)), b(256);
+    const dim3 g((unsigned)(w.nblk * k.splits)), b(256);
     // data-gradient epilogue (mask / inject), forward epilogue (bias / ReLU) with or without the pool; a split-K launch writes raw partial
     // sums: the plain forward build
     const bool dg = k.splits == 1 && (p.mask_src || p.inject);

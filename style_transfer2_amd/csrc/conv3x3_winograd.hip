@@ -11,6 +11,7 @@
 #include <string.h>
 #include <type_traits>
 #include "st2_kernels.h"
+#include "env.h"
 
 namespace st2 {
 
@@ -874,198 +875,170 @@ hipError_t launch_wino_combine(const float* scratch, int splits, const float* bi
     return hipGetLastError();
 }
 
-static int wino_default_variant(int M, int W);
-static bool wino_variant_small(int variant);
-static bool wino_needs_big(int K, int M, int H, int W);
-bool conv_wino_ok(int K, int M, int H, int W);
-
-// Split-K factor for a launch that would leave most CUs idle (conv5_1 at 1024^2: 128 workgroups on 256 CUs)
-int conv_wino_splits(int K, int M, int H, int W)
+int wino_splitk(long long nblk, int nch)
 {
-    static const bool off = [] { const char* e = getenv("ST2_WINO_SPLITK"); return e && *e == '0'; }();
-    if (off || !conv_wino_ok(K, M, H, W) || ((size_t)H * W) % 4 != 0) return 1;      // the combine pass works on float4
-    int v = wino_default_variant(M, W);
-    if (v == 3 && W % 4 != 0) v = 1;
-    if (v == 6 && W % 4 != 0) v = 0;
-    if ((v == 8 || v == 9) && W % 4 != 0) v = 1;
-    const bool half = v == 8 || v == 9;
-    const int bm = (wino_variant_small(v) || half) ? 64 : 128, prows = wino_variant_small(v) ? 8 : 4;
-    const long long nblk = (long long)((W + 31) / 32) * ((H + prows - 1) / prows) * ((M + bm - 1) / bm);
-    const int nch = K / WN_CH;
+    // a launch that would leave most CUs idle (conv5_1 at 1024^2: 128 workgroups on 256 CUs) splits K while every part keeps 4 chunks
     int sp = 1;
     while (nblk * sp * 2 <= 256 && nch % (sp * 2) == 0 && nch / (sp * 2) >= 4 && sp < 16) sp *= 2;
     return sp;
 }
 
-// may this launch also write the max-pooled blob?  (forward epilogue only; not when K is split across workgroups)
-bool conv_wino_can_pool(int K, int M, int H, int W)
+namespace {
+// what a variant is: its tile, and which builds exist for it.  amap: its fused pool writes the arg-max map (the one-tile-group builds);
+// full: it has the NOOUT, UNPOOL and BIG builds and the specialised epilogues; stamped: a diagnostic build (aligned widths, one pass)
+struct WinoTraits { int bm, prows; bool amap, full, stamped; };
+WinoTraits wino_traits(int variant)
 {
-    static const bool off = [] { const char* e = getenv("ST2_WINO_POOL"); return e && *e == '0'; }();
-    return !off && conv_wino_ok(K, M, H, W) && conv_wino_splits(K, M, H, W) == 1;
-}
-
-// does a fused-pool launch of this shape also write the arg-max map (ConvProblem::pool_amap)?  The one-tile-group builds of aligned widths do.
-bool conv_wino_pool_amap_ok(int K, int M, int H, int W)
-{
-    if (!conv_wino_can_pool(K, M, H, W) || W % 4 != 0 || H % 2 != 0) return false;
-    const int v = wino_default_variant(M, W);
-    return v == 0 || v == 6 || v == 8;
-}
-
-// may a forward launch of this shape with the fused pool skip its full-resolution blob (ConvProblem::out == nullptr)?
-bool conv_wino_can_skip_out(int K, int M, int H, int W)
-{
-    if (!conv_wino_pool_amap_ok(K, M, H, W) || wino_needs_big(K, M, H, W)) return false;
-    const int v = wino_default_variant(M, W);
-    return v == 0 || v == 8;
-}
-
-// may a data-gradient launch of this shape read the pooled diff + the arg-max map of the pool above its input (ConvProblem::unpool_amap)?
-// The 128-channel and the half-tile build have the variant; the staged pooled rows need W % 32 == 0 and H % 2 == 0.
-bool conv_wino_can_unpool(int K, int M, int H, int W)
-{
-    const char* e = getenv("ST2_WINO_UNPOOL");               // =0: keep maxpool_bwd_amap_k (read per launch: the tests compare both)
-    if ((e && *e == '0') || !conv_wino_ok(K, M, H, W) || W % 32 != 0 || H % 2 != 0) return false;
-    const int v = wino_default_variant(M, W);
-    return v == 0 || v == 8;                                 // (a pooled diff of 4 GiB or more: the BIG builds, conv_wino_ok has checked the sizes)
-}
-
-// a tensor of 4 GiB or more on either side: the BIG builds (aligned widths, the 128-channel or the half-tile variant) take it while one
-// chunk of 8 planes stays below 4 GiB (32-bit byte offsets from the chunk's base) and the output below 2^32 elements (32-bit element offsets)
-static bool wino_needs_big(int K, int M, int H, int W) { return 4ull * K * H * W >= 0xfffffff0ull || 4ull * M * H * W >= 0xfffffff0ull; }
-static bool wino_big_ok(int K, int M, int H, int W)
-{
-    const char* e = getenv("ST2_WINO_BIG");                  // =0: refuse tensors >= 4 GiB as before (read per call)
-    if (e && *e == '0') return false;
-    const int v = wino_default_variant(M, W);
-    (void)K;                                                 // (the input is addressed chunk by chunk: any depth)
-    return W % 4 == 0 && (v == 0 || v == 8) && 32ull * H * W < 0xfffffff0ull && (unsigned long long)M * H * W <= 0x100000000ull;
-}
-
-bool conv_wino_ok(int K, int M, int H, int W)
-{
-    static const bool anyw = [] { const char* e = getenv("ST2_WINO_ANYW"); return !(e && *e == '0'); }();
-    if (!(K >= 8 && K % 8 == 0 && (W % 4 == 0 || anyw) && W >= 1 && M >= 48 && H >= 1)) return false;
-    return !wino_needs_big(K, M, H, W) || wino_big_ok(K, M, H, W);
-}
-
-// variant: 0 = 128 channels x 4x32 pixels, 1 = 64 channels x 8x32 pixels (tile groups split over the waves),
-// 3 = 64 channels x 8x32 pixels with the POSITIONS split over the waves (half the U stream), -1 = choose;
-// 6 = 128 channels x 4x32 pixels with EIGHT waves (two per SIMD, positions split between the partners);
-// 8 = 64 channels x 4x32 pixels, positions split between two waves, two workgroups per CU;
-// 2 / 5 / 4 / 7 / 9 = 0 / 1 / 3 / 6 / 8 with cycle stamps (diagnostic builds).
-// p.wpack = the Winograd pack (pack_wino_weights_*); p.bias may be any length >= M
-static int wino_default_variant(int M, int W)
-{
-    const char* fe = getenv("ST2_WINO_CFG");               // read per launch: the tests force every variant on every shape
-    if (fe && *fe) return atoi(fe);
-    const char* pe = getenv("ST2_WINO_PS");
-    const bool ps = pe && *pe == '1';                      // measured (profiles/r02_c_*): no faster than variant 1 -- off unless asked for
-    const int pad128 = (M + 127) / 128 * 128, pad64 = (M + 63) / 64 * 64;
-    if (ps && W % 4 == 0) return 3;       // the any-width build of the position split would spill (it is not built)
-    const char* w8 = getenv("ST2_WINO_W8");                  // measured (profiles/r02_d_*): main loop 2 % slower, epilogue 25 % faster,
-    if (w8 && *w8 == '1' && W % 4 == 0 && pad128 <= pad64) return 6;   // layer times within 1 % of variant 0 -- off unless asked for
-    if (pad64 < pad128) {
-        // <= 64 useful channels per 128: the half tile with two workgroups per CU where the width allows it (measured,
-        // profiles/r02_v_*: conv1_2 -10 %, conv2_1 dgrad -8 % against variant 1; within 3 % of variant 0 elsewhere)
-        const char* h4 = getenv("ST2_WINO_H4");
-        return (W % 4 == 0 && !(h4 && *h4 == '0')) ? 8 : 1;
+    switch (variant) {
+    case WV_128x128: return {128, 4, true, true, false};
+    case WV_H4_64x128: return {64, 4, true, true, false};
+    case WV_W8_128x128: return {128, 4, true, false, false};
+    case WV_64x256: case WV_PS64x256: return {64, 8, false, false, false};
+    case WV_64x256_STAMPED: case WV_PS64x256_STAMPED: return {64, 8, false, false, true};
+    case WV_H4_64x128_STAMPED: return {64, 4, false, false, true};
+    case WV_128x128_STAMPED: case WV_W8_128x128_STAMPED: return {128, 4, false, false, true};
+    default: return {128, 4, false, false, false};          // a value that names no variant: the launcher has no build for it
     }
-    return 0;
 }
-static bool wino_variant_small(int variant) { return variant == 1 || variant == 3 || variant == 4 || variant == 5; }
 
+// the variant of the automatic path
+int wino_default_variant(int M, int W)
+{
+    const long long forced = env_int("ST2_WINO_CFG", -1);  // read per launch: the tests force every variant on every shape
+    if (forced >= 0) return (int)forced;
+    const int pad128 = (M + 127) / 128 * 128, pad64 = (M + 63) / 64 * 64;
+    // measured (profiles/r02_c_*): no faster than variant 1 -- off unless asked for (its any-width build would spill: it is not built)
+    if (W % 4 == 0 && env_on("ST2_WINO_PS")) return WV_PS64x256;
+    // measured (profiles/r02_d_*): main loop 2 % slower, epilogue 25 % faster, layer times within 1 % of variant 0 -- off unless asked for
+    if (W % 4 == 0 && pad128 <= pad64 && env_on("ST2_WINO_W8")) return WV_W8_128x128;
+    if (pad128 <= pad64) return WV_128x128;
+    // <= 64 useful channels per 128: the half tile with two workgroups per CU where the width allows it (measured,
+    // profiles/r02_v_*: conv1_2 -10 %, conv2_1 dgrad -8 % against variant 1; within 3 % of variant 0 elsewhere)
+    return (W % 4 == 0 && !env_off("ST2_WINO_H4")) ? WV_H4_64x128 : WV_64x256;
+}
+}  // namespace
+
+WinoLaunch wino_resolve(int K, int M, int H, int W, int forced_variant)
+{
+    WinoLaunch w{};
+    w.quad = W % 4 == 0;                            // else the any-width kernels (dword staging, narrower epilogue accesses)
+    int v = forced_variant >= 0 ? forced_variant : wino_default_variant(M, W);
+    if (!w.quad) {                                  // builds of aligned widths only: their nearest any-width relative
+        if (v == WV_PS64x256 || v == WV_H4_64x128) v = WV_64x256;
+        if (v == WV_W8_128x128) v = WV_128x128;
+        if (v == WV_H4_64x128_STAMPED) v = WV_64x256;      // quiet: the stamp request is dropped with the tile (the other stamped builds refuse)
+    }
+    w.variant = (WinoVariant)v;
+    const WinoTraits t = wino_traits(v);
+    w.bm = t.bm; w.prows = t.prows;
+    w.nblk = (long long)((W + 31) / 32) * ((H + t.prows - 1) / t.prows) * ((M + t.bm - 1) / t.bm);
+    // a tensor of 4 GiB or more on either side: the BIG builds take it while one chunk of 8 planes stays below 4 GiB (32-bit byte offsets
+    // from the chunk's base; the input is addressed chunk by chunk: any depth) and the output below 2^32 elements (32-bit element offsets)
+    const bool needs_big = 4ull * K * H * W >= 0xfffffff0ull || 4ull * M * H * W >= 0xfffffff0ull;
+    auto big_ok = [&] {                             // ST2_WINO_BIG=0: refuse tensors >= 4 GiB
+        return w.quad && t.full && 32ull * H * W < 0xfffffff0ull && (unsigned long long)M * H * W <= 0x100000000ull && !env_off("ST2_WINO_BIG");
+    };
+    w.ok = K >= 8 && K % 8 == 0 && W >= 1 && M >= 48 && H >= 1 && (w.quad || !env_off("ST2_WINO_ANYW")) && (!needs_big || big_ok());
+    // test hook: ST2_WINO_FORCE_BIG=1 runs the BIG builds on tensors of any size (tests/test_gpu_winograd.py compares them bit for bit)
+    w.big = needs_big || (env_on("ST2_WINO_FORCE_BIG") && big_ok());
+    w.splits = 1;                                   // (the combine pass works on float4)
+    if (forced_variant < 0 && w.ok && ((size_t)H * W) % 4 == 0 && !env_off("ST2_WINO_SPLITK")) w.splits = wino_splitk(w.nblk, K / WN_CH);
+    w.can_pool = w.ok && w.splits == 1 && !env_off("ST2_WINO_POOL");      // (forward epilogue only; not when K is split across workgroups)
+    w.pool_amap = w.can_pool && w.quad && H % 2 == 0 && t.amap;
+    w.can_skip_out = w.pool_amap && !needs_big && t.full;
+    // the staged pooled rows need W % 32 == 0 and H % 2 == 0 (a pooled diff of 4 GiB or more: the BIG builds, `ok` has checked the sizes);
+    // ST2_WINO_UNPOOL=0: keep maxpool_bwd_amap_k
+    w.can_unpool = w.ok && W % 32 == 0 && H % 2 == 0 && t.full && !env_off("ST2_WINO_UNPOOL");
+    return w;
+}
+
+namespace {
+// the epilogue a launch may take: the generic one, or the one specialised for its kind (conv3x3_wino_body, EPI) where there is a build
+enum WinoEpi { WE_GENERIC, WE_FWD, WE_FWD_POOL, WE_POOLONLY, WE_DGM, WE_DG };
+struct WinoBuild { void (*kernel)(const WinoKArgs); unsigned block; int variant; WinoEpi epi; bool quad, big, unpool, noout; };   // WE_GENERIC: any kind
+// every build, the specialised epilogues first: the first row whose facts are the launch's runs, and a launch without a row has no build
+const WinoBuild kWinoBuilds[] = {
+    //                                        block  variant                  epilogue     quad   big    unpool noout
+    {conv3x3_wino_f32_128x128_fwd,            256, WV_128x128,               WE_FWD,      true,  false, false, false},
+    {conv3x3_wino_f32_128x128_pool,           256, WV_128x128,               WE_FWD_POOL, true,  false, false, false},
+    {conv3x3_wino_f32_128x128_poolonly,       256, WV_128x128,               WE_POOLONLY, true,  false, false, true},
+    {conv3x3_wino_f32_128x128_dgm,            256, WV_128x128,               WE_DGM,      true,  false, false, false},
+    {conv3x3_wino_f32_128x128_dg,             256, WV_128x128,               WE_DG,       true,  false, false, false},
+    {conv3x3_wino_f32_128x128_unpool_dgm,     256, WV_128x128,               WE_DGM,      true,  false, true,  false},
+    {conv3x3_wino_f32_h4_64x128_fwd,          256, WV_H4_64x128,             WE_FWD,      true,  false, false, false},
+    {conv3x3_wino_f32_h4_64x128_pool,         256, WV_H4_64x128,             WE_FWD_POOL, true,  false, false, false},
+    {conv3x3_wino_f32_h4_64x128_poolonly,     256, WV_H4_64x128,             WE_POOLONLY, true,  false, false, true},
+    {conv3x3_wino_f32_h4_64x128_dgm,          256, WV_H4_64x128,             WE_DGM,      true,  false, false, false},
+    {conv3x3_wino_f32_h4_64x128_dg,           256, WV_H4_64x128,             WE_DG,       true,  false, false, false},
+    {conv3x3_wino_f32_h4_64x128_unpool_dgm,   256, WV_H4_64x128,             WE_DGM,      true,  false, true,  false},
+    {conv3x3_wino_f32_128x128,                256, WV_128x128,               WE_GENERIC,  true,  false, false, false},
+    {conv3x3_wino_f32_128x128_anyw,           256, WV_128x128,               WE_GENERIC,  false, false, false, false},
+    {conv3x3_wino_f32_128x128_noout,          256, WV_128x128,               WE_GENERIC,  true,  false, false, true},
+    {conv3x3_wino_f32_128x128_unpool,         256, WV_128x128,               WE_GENERIC,  true,  false, true,  false},
+    {conv3x3_wino_f32_128x128_big,            256, WV_128x128,               WE_GENERIC,  true,  true,  false, false},
+    {conv3x3_wino_f32_128x128_unpool_big,     256, WV_128x128,               WE_GENERIC,  true,  true,  true,  false},
+    {conv3x3_wino_f32_h4_64x128,              256, WV_H4_64x128,             WE_GENERIC,  true,  false, false, false},
+    {conv3x3_wino_f32_h4_64x128_noout,        256, WV_H4_64x128,             WE_GENERIC,  true,  false, false, true},
+    {conv3x3_wino_f32_h4_64x128_unpool,       256, WV_H4_64x128,             WE_GENERIC,  true,  false, true,  false},
+    {conv3x3_wino_f32_h4_64x128_big,          256, WV_H4_64x128,             WE_GENERIC,  true,  true,  false, false},
+    {conv3x3_wino_f32_h4_64x128_unpool_big,   256, WV_H4_64x128,             WE_GENERIC,  true,  true,  true,  false},
+    {conv3x3_wino_f32_64x256,                 256, WV_64x256,                WE_GENERIC,  true,  false, false, false},
+    {conv3x3_wino_f32_64x256_anyw,            256, WV_64x256,                WE_GENERIC,  false, false, false, false},
+    {conv3x3_wino_f32_ps64x256,               256, WV_PS64x256,              WE_GENERIC,  true,  false, false, false},
+    {conv3x3_wino_f32_w8_128x128,             512, WV_W8_128x128,            WE_GENERIC,  true,  false, false, false},
+    {conv3x3_wino_f32_128x128_stamped,        256, WV_128x128_STAMPED,       WE_GENERIC,  true,  false, false, false},
+    {conv3x3_wino_f32_64x256_stamped,         256, WV_64x256_STAMPED,        WE_GENERIC,  true,  false, false, false},
+    {conv3x3_wino_f32_ps64x256_stamped,       256, WV_PS64x256_STAMPED,      WE_GENERIC,  true,  false, false, false},
+    {conv3x3_wino_f32_w8_128x128_stamped,     512, WV_W8_128x128_STAMPED,    WE_GENERIC,  true,  false, false, false},
+    {conv3x3_wino_f32_h4_64x128_stamped,      256, WV_H4_64x128_STAMPED,     WE_GENERIC,  true,  false, false, false},
+};
+}  // namespace
+
+// p.wpack = the Winograd pack (pack_wino_weights_*); p.bias may be any length >= M; variant < 0 = choose
 hipError_t launch_conv3x3_wino_cfg(const ConvProblem& p, int variant, hipStream_t s)
 {
-    if (!conv_wino_ok(p.K, p.M, p.H, p.W) || (reinterpret_cast<uintptr_t>(p.in) & 15) != 0) return hipErrorInvalidValue;
-    const bool quad = p.W % 4 == 0;                  // else the any-width kernels (dword staging, narrower epilogue accesses)
-    const bool forced_auto = variant < 0;           // split-K only on the automatic path
-    if (variant < 0) variant = wino_default_variant(p.M, p.W);
-    if (variant == 3 && !quad) variant = 1;
-    if (variant == 6 && !quad) variant = 0;
-    if ((variant == 8 || variant == 9) && !quad) variant = 1;
-    if (variant > 9) return hipErrorInvalidValue;
-    const bool small = wino_variant_small(variant), half = variant == 8 || variant == 9;
-    const int bm = (small || half) ? 64 : 128, prows = small ? 8 : 4;
+    const WinoLaunch w = wino_resolve(p.K, p.M, p.H, p.W, variant);
+    if (!w.ok || (reinterpret_cast<uintptr_t>(p.in) & 15) != 0) return hipErrorInvalidValue;
+    const WinoTraits t = wino_traits(w.variant);
+    const bool unpool = p.unpool_amap != nullptr, noout = !p.out;
     WinoKArgs k{};
     k.in = p.in; k.upack = reinterpret_cast<const float4*>(p.wpack); k.bias = p.bias; k.out = p.out;
     k.mask_src = p.mask_src; k.inject = p.inject;
     k.K = p.K; k.M = p.M; k.H = p.H; k.W = p.W; k.nch = p.K / WN_CH;
-    k.tiles_x = (p.W + 31) / 32; k.tiles_y = (p.H + prows - 1) / prows; k.n_mtiles = (p.M + bm - 1) / bm; k.relu = p.relu;
-    bool big = wino_needs_big(p.K, p.M, p.H, p.W);
-    if (big && (!wino_big_ok(p.K, p.M, p.H, p.W) || !(variant == 0 || variant == 8) || !quad)) return hipErrorInvalidValue;
-    {   // test hook: ST2_WINO_FORCE_BIG=1 runs the BIG builds on tensors of any size (tests/test_gpu_winograd.py compares them bit for bit)
-        const char* fb = getenv("ST2_WINO_FORCE_BIG");
-        if (fb && *fb == '1' && quad && (variant == 0 || variant == 8) && wino_big_ok(p.K, p.M, p.H, p.W)) big = true;
-    }
-    k.in_bytes = big ? (unsigned)(4ull * WN_CH * p.H * p.W) : (unsigned)(4ull * p.K * p.H * p.W);      // BIG: the bytes of one chunk
-    const bool unpool = p.unpool_amap != nullptr;
+    k.tiles_x = (p.W + 31) / 32; k.tiles_y = (p.H + w.prows - 1) / w.prows; k.n_mtiles = (p.M + w.bm - 1) / w.bm; k.relu = p.relu;
+    k.in_bytes = w.big ? (unsigned)(4ull * WN_CH * p.H * p.W) : (unsigned)(4ull * p.K * p.H * p.W);      // BIG: the bytes of one chunk
     if (unpool) {
-        if (!(variant == 0 || variant == 8) || !quad || p.W % 32 != 0 || p.H % 2 != 0 || p.pool_out) return hipErrorInvalidValue;
+        if (p.W % 32 != 0 || p.H % 2 != 0 || p.pool_out) return hipErrorInvalidValue;
         k.unpool_amap = p.unpool_amap; k.ph = p.H / 2; k.pw = p.W / 2;
-        k.in_bytes = big ? (unsigned)(4ull * WN_CH * k.ph * k.pw) : (unsigned)(4ull * p.K * k.ph * k.pw);
+        k.in_bytes = w.big ? (unsigned)(4ull * WN_CH * k.ph * k.pw) : (unsigned)(4ull * p.K * k.ph * k.pw);
         if ((unsigned long long)p.K * k.ph * k.pw >= 0xfffffff0ull) return hipErrorInvalidValue;
         k.amap_bytes = (unsigned)((unsigned long long)p.K * k.ph * k.pw);
     }
     k.u_bytes = (unsigned)(4ull * wino_pack_floats(p.K, p.M));
     k.stamps = p.stamps;
-    const long long nblk = (long long)k.tiles_x * k.tiles_y * k.n_mtiles;
-    if (nblk <= 0 || nblk > 0x7fffffffLL) return hipErrorInvalidValue;
+    if (w.nblk <= 0 || w.nblk > 0x7fffffffLL) return hipErrorInvalidValue;
     k.splits = 1; k.scratch = nullptr;
     k.pool_out = p.pool_out; k.pool_h = (p.H + 1) / 2; k.pool_w = (p.W + 1) / 2;
-    k.pool_amap = (p.pool_out && quad && (variant == 0 || variant == 6 || variant == 8)) ? p.pool_amap : nullptr;
-    if (forced_auto && p.scratch) {
-        const int sp = conv_wino_splits(p.K, p.M, p.H, p.W);
-        if (sp > 1 && p.scratch_floats >= (size_t)sp * p.M * p.H * p.W) { k.splits = sp; k.scratch = p.scratch; }
+    // quiet: pool_amap handed to a variant or a width whose fused pool writes no map, or without pool_out, is ignored
+    k.pool_amap = (p.pool_out && w.quad && t.amap) ? p.pool_amap : nullptr;
+    // quiet: without scratch, or with too little of it, the launch runs in one pass (a forced variant never splits: w.splits == 1)
+    if (w.splits > 1 && p.scratch && p.scratch_floats >= (size_t)w.splits * p.M * p.H * p.W) { k.splits = w.splits; k.scratch = p.scratch; }
+    if (k.splits > 1 && (p.pool_out || t.stamped)) return hipErrorInvalidValue;   // the planner reads can_pool first; the stamped builds run one pass
+    // out == nullptr: only with the fused pool AND its arg-max map, no mask / inject (and a build for it: one pass included, k.pool_out is set)
+    if (noout && (!k.pool_out || !k.pool_amap || p.mask_src || p.inject)) return hipErrorInvalidValue;
+    // the epilogue specialised for this launch's kind (ST2_WINO_EPI=0: the generic one; read per launch: the tests compare both bit for bit)
+    const bool fwd = p.bias && p.relu && !p.mask_src && !p.inject, dgr = !p.bias && !p.relu && !p.pool_out;
+    const WinoEpi epi = (k.splits > 1 || env_off("ST2_WINO_EPI")) ? WE_GENERIC
+                        : fwd ? (noout ? WE_POOLONLY : k.pool_out ? WE_FWD_POOL : WE_FWD)
+                        : dgr ? (p.mask_src ? WE_DGM : WE_DG) : WE_GENERIC;
+    for (const WinoBuild& b : kWinoBuilds) {
+        if (b.variant != w.variant || (b.epi != epi && b.epi != WE_GENERIC) || b.quad != w.quad || b.big != w.big || b.unpool != unpool || b.noout != noout) continue;
+        b.kernel<<<dim3((unsigned)(w.nblk * k.splits)), dim3(b.block), 0, s>>>(k);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess || k.splits == 1) return e;
+        return launch_wino_combine(k.scratch, k.splits, p.bias, p.relu, p.mask_src, p.inject, p.out, p.M, p.H, p.W, s);   // (w.splits > 1 only for planes that are a multiple of 4)
     }
-    const bool stamped = variant == 2 || variant == 4 || variant == 5 || variant == 7 || variant == 9;
-    if (stamped && (!quad || k.splits > 1)) return hipErrorInvalidValue;      // the stamped builds are quad-only, one pass
-    if (k.splits > 1 && p.pool_out) return hipErrorInvalidValue;              // the caller asks conv_wino_can_pool() first
-    // out == nullptr: only with the fused pool AND its arg-max map (variants 0 and 8 on aligned widths), one pass, no mask / inject
-    const bool noout = !p.out;
-    if (noout && (!k.pool_out || !k.pool_amap || k.splits > 1 || !quad || p.mask_src || p.inject || big || unpool || !(variant == 0 || variant == 8)))
-        return hipErrorInvalidValue;
-    const dim3 g((unsigned)(nblk * k.splits)), b(256);
-    {   // the epilogue specialised for this launch's kind, where there is one (ST2_WINO_EPI=0: the generic epilogue; read per launch: the
-        // tests compare both bit for bit)
-        const char* ee = getenv("ST2_WINO_EPI");
-        const bool fwd = p.bias && p.relu && !p.mask_src && !p.inject, dgr = !p.bias && !p.relu && !p.pool_out;
-        if (!(ee && *ee == '0') && (variant == 0 || variant == 8) && quad && !big && k.splits == 1 && (fwd || dgr) && (!k.pool_out || k.pool_amap || !p.pool_amap)) {
-            const bool v0 = variant == 0;
-            bool done = true;
-            if (noout) { if (v0) conv3x3_wino_f32_128x128_poolonly<<<g, b, 0, s>>>(k); else conv3x3_wino_f32_h4_64x128_poolonly<<<g, b, 0, s>>>(k); }
-            else if (unpool) {
-                if (dgr && p.mask_src) { if (v0) conv3x3_wino_f32_128x128_unpool_dgm<<<g, b, 0, s>>>(k); else conv3x3_wino_f32_h4_64x128_unpool_dgm<<<g, b, 0, s>>>(k); }
-                else done = false;
-            }
-            else if (fwd && k.pool_out) { if (v0) conv3x3_wino_f32_128x128_pool<<<g, b, 0, s>>>(k); else conv3x3_wino_f32_h4_64x128_pool<<<g, b, 0, s>>>(k); }
-            else if (fwd) { if (v0) conv3x3_wino_f32_128x128_fwd<<<g, b, 0, s>>>(k); else conv3x3_wino_f32_h4_64x128_fwd<<<g, b, 0, s>>>(k); }
-            else if (p.mask_src) { if (v0) conv3x3_wino_f32_128x128_dgm<<<g, b, 0, s>>>(k); else conv3x3_wino_f32_h4_64x128_dgm<<<g, b, 0, s>>>(k); }
-            else { if (v0) conv3x3_wino_f32_128x128_dg<<<g, b, 0, s>>>(k); else conv3x3_wino_f32_h4_64x128_dg<<<g, b, 0, s>>>(k); }
-            if (done) return hipGetLastError();
-        }
-    }
-    switch (variant) {
-    case 0: if (noout) conv3x3_wino_f32_128x128_noout<<<g, b, 0, s>>>(k);
-            else if (big) { if (unpool) conv3x3_wino_f32_128x128_unpool_big<<<g, b, 0, s>>>(k); else conv3x3_wino_f32_128x128_big<<<g, b, 0, s>>>(k); }
-            else if (unpool) conv3x3_wino_f32_128x128_unpool<<<g, b, 0, s>>>(k);
-            else if (quad) conv3x3_wino_f32_128x128<<<g, b, 0, s>>>(k); else conv3x3_wino_f32_128x128_anyw<<<g, b, 0, s>>>(k); break;
-    case 1: if (quad) conv3x3_wino_f32_64x256<<<g, b, 0, s>>>(k); else conv3x3_wino_f32_64x256_anyw<<<g, b, 0, s>>>(k); break;
-    case 3: conv3x3_wino_f32_ps64x256<<<g, b, 0, s>>>(k); break;
-    case 2: conv3x3_wino_f32_128x128_stamped<<<g, b, 0, s>>>(k); break;
-    case 4: conv3x3_wino_f32_ps64x256_stamped<<<g, b, 0, s>>>(k); break;
-    case 6: conv3x3_wino_f32_w8_128x128<<<g, dim3(512), 0, s>>>(k); break;
-    case 7: conv3x3_wino_f32_w8_128x128_stamped<<<g, dim3(512), 0, s>>>(k); break;
-    case 8: if (noout) conv3x3_wino_f32_h4_64x128_noout<<<g, b, 0, s>>>(k);
-            else if (big) { if (unpool) conv3x3_wino_f32_h4_64x128_unpool_big<<<g, b, 0, s>>>(k); else conv3x3_wino_f32_h4_64x128_big<<<g, b, 0, s>>>(k); }
-            else if (unpool) conv3x3_wino_f32_h4_64x128_unpool<<<g, b, 0, s>>>(k); else conv3x3_wino_f32_h4_64x128<<<g, b, 0, s>>>(k);
-            break;
-    case 9: conv3x3_wino_f32_h4_64x128_stamped<<<g, b, 0, s>>>(k); break;
-    default: conv3x3_wino_f32_64x256_stamped<<<g, b, 0, s>>>(k); break;
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess || k.splits == 1) return e;
-    return launch_wino_combine(k.scratch, k.splits, p.bias, p.relu, p.mask_src, p.inject, p.out, p.M, p.H, p.W, s);      // (conv_wino_splits() declines planes that are no multiple of 4)
+    return hipErrorInvalidValue;                    // no such build: a value that names no variant, a stamped build on an unaligned width, NOOUT / UNPOOL / BIG on a variant without them
 }
 
 hipError_t launch_conv3x3_wino(const ConvProblem& p, hipStream_t s) { return launch_conv3x3_wino_cfg(p, -1, s); }

@@ -62,11 +62,10 @@ void dfree16(unsigned short*& p)
     if (p && hipFree(p) != hipSuccess) (void)hipGetLastError();
     p = nullptr;
 }
-int wino_scratch(st_ctx* c, ConvProblem& p, bool split_kernel)
+int wino_scratch(st_ctx* c, ConvProblem& p, int splits)
 {
-    const int sp = split_kernel ? conv_wino_split_splits(p.K, p.M, p.H, p.W) : conv_wino_splits(p.K, p.M, p.H, p.W);
-    if (sp <= 1) return ST_OK;
-    const size_t need = (size_t)sp * p.M * p.H * p.W;
+    if (splits <= 1) return ST_OK;
+    const size_t need = (size_t)splits * p.M * p.H * p.W;
     if (need > c->conv_scratch_cap) {
         HIP_TRY(hipStreamSynchronize(c->stream));
         dfree(c->conv_scratch); c->conv_scratch_cap = 0;
@@ -188,10 +187,10 @@ int forward_range(st_ctx* c, ActSet& a, const float* x, int last, bool lean)
                 ProfScope ps(c, r.kind == F_WINO_SPLIT ? P_CONV_FWD_WSPLIT : r.kind == F_WINO ? P_CONV_FWD_WINO : P_CONV_FWD, conv_flops,
                              4.0 * px * (L.cin + L.cout));
                 if (r.kind == F_WINO_SPLIT) {
-                    p.wpack = reinterpret_cast<const float*>(L.us_fwd); ST_TRY(wino_scratch(c, p, true));
+                    p.wpack = reinterpret_cast<const float*>(L.us_fwd); ST_TRY(wino_scratch(c, p, wino_split_resolve(p.K, p.M, H, W).splits));
                     HIP_TRY(launch_conv3x3_wino_split(p, c->stream));
                 } else if (r.kind == F_WINO) {
-                    p.wpack = L.u_fwd; ST_TRY(wino_scratch(c, p, false));
+                    p.wpack = L.u_fwd; ST_TRY(wino_scratch(c, p, wino_resolve(p.K, p.M, H, W).splits));
                     HIP_TRY(launch_conv3x3_wino(p, c->stream));
                 } else if (r.kind == F_FIRST_SPLIT) {
                     HIP_TRY(launch_conv3x3_first_split(p.in, L.w_split, p.out, p.out16, p.K, p.M, H, W, p.relu, c->stream, r.bits ? a.bits[i] : nullptr));
@@ -345,8 +344,8 @@ int backward_chain(st_ctx* c, int top, const float* top_diff, const std::vector<
             p.unpool_amap = unpool_amap;
             ProfScope ps(c, r.kind == B_WINO_SPLIT ? P_CONV_DGRAD_WSPLIT : r.kind == B_WINO ? P_CONV_DGRAD_WINO : P_CONV_DGRAD, conv_flops,
                          4.0 * px * (L.cin + (r.unpool ? 0.3125 : 1.0) * L.cout));
-            if (r.kind == B_WINO_SPLIT) { p.wpack = reinterpret_cast<const float*>(L.us_bwd); ST_TRY(wino_scratch(c, p, true)); HIP_TRY(launch_conv3x3_wino_split(p, c->stream)); }
-            else if (r.kind == B_WINO) { p.wpack = L.u_bwd; ST_TRY(wino_scratch(c, p, false)); HIP_TRY(launch_conv3x3_wino(p, c->stream)); }
+            if (r.kind == B_WINO_SPLIT) { p.wpack = reinterpret_cast<const float*>(L.us_bwd); ST_TRY(wino_scratch(c, p, wino_split_resolve(p.K, p.M, H, W).splits)); HIP_TRY(launch_conv3x3_wino_split(p, c->stream)); }
+            else if (r.kind == B_WINO) { p.wpack = L.u_bwd; ST_TRY(wino_scratch(c, p, wino_resolve(p.K, p.M, H, W).splits)); HIP_TRY(launch_conv3x3_wino(p, c->stream)); }
             else HIP_TRY(launch_conv3x3(p, c->stream));
             break;
         }
@@ -519,9 +518,9 @@ int st_create(st_ctx** out, int device_id, const st_layer_desc* layers, int n_la
     HIP_TRY(hipSetDevice(device_id));
     st_ctx* c = new st_ctx();
     c->device = device_id;
-    { const char* e = getenv("ST2_WINO"); if (e && *e) c->wino = atoi(e) != 0; }
-    { const char* e = getenv("ST2_GRAPH"); if (e && *e) c->graphs = atoi(e) != 0; }
-    { const char* e = getenv("ST2_GRAPH_MAX_PX"); if (e && *e) c->graph_max_px = (size_t)atoll(e) * (size_t)atoll(e); }
+    c->wino = env_int("ST2_WINO", c->wino) != 0;
+    c->graphs = env_int("ST2_GRAPH", c->graphs) != 0;
+    { const size_t side = (size_t)env_int("ST2_GRAPH_MAX_PX", 768); c->graph_max_px = side * side; }
     if (n_layers <= 0) {
         for (const auto& l : kVgg19) {
             Layer L; L.is_conv = l.kind == 0; L.name = l.name; L.cin = l.cin; L.cout = l.cout;
@@ -628,7 +627,7 @@ static int make_split_packs(Layer& L, const float* w)
     for (int dir = 0; dir < 2; ++dir) {
         const int K = dir ? L.cout : L.cin, M = dir ? L.cin : L.cout;
         unsigned short** dst = dir ? &L.us_bwd : &L.us_fwd;
-        if (*dst || !conv_wino_split_ok(K, M, 4, 4)) continue;
+        if (*dst || !wino_split_resolve(K, M, 4, 4).ok) continue;
         std::vector<unsigned short> hu(wino_split_pack_elems(K, M), 0);
         if (dir) pack_wino_split_weights_dgrad(w, L.cout, L.cin, hu.data()); else pack_wino_split_weights_fwd(w, L.cout, L.cin, hu.data());
         ST_TRY(dmalloc16(dst, hu.size()));
@@ -652,7 +651,7 @@ int st_load_conv_weights(st_ctx* c, const char* layer, const float* w, const flo
         dfree(L.w_fwd); dfree(L.w_bwd); dfree(L.w_raw); dfree(L.w_raw_r); dfree(L.bias); dfree16(L.w16_fwd); dfree16(L.w16_bwd); dfree16(L.w_split); dfree(L.u_fwd); dfree(L.u_bwd); dfree16(L.us_fwd); dfree16(L.us_bwd);
         for (int dir = 0; dir < 2; ++dir) {   // Winograd packs for the directions the Winograd kernel can take (any image size)
             const int K = dir ? L.cout : L.cin, M = dir ? L.cin : L.cout;
-            if (!conv_wino_ok(K, M, 4, 4)) continue;
+            if (!wino_resolve(K, M, 4, 4).ok) continue;
             std::vector<float> hu(wino_pack_floats(K, M));
             if (dir) pack_wino_weights_dgrad(w, L.cout, L.cin, hu.data()); else pack_wino_weights_fwd(w, L.cout, L.cin, hu.data());
             float** dst = dir ? &L.u_bwd : &L.u_fwd;
@@ -754,8 +753,7 @@ int st_set_precision(st_ctx* c, int bf16_features)
     c->bf16 = bf16_features != 0;
     // 1: the lean data flow (objective evaluations write fp32 only where something reads fp32); 2: every fp32 blob and diff
     // as in round 1 (A/B reference of the tests); environment ST2_BF16_LEAN=0 forces 2
-    const char* e = getenv("ST2_BF16_LEAN");
-    c->lean = bf16_features == 1 && !(e && *e == '0');
+    c->lean = bf16_features == 1 && !env_off("ST2_BF16_LEAN");
     return ST_OK;
 }
 

@@ -3,6 +3,7 @@
 #pragma once
 #include "../../include/st2.h"
 #include "st2_kernels.h"
+#include "env.h"
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -259,7 +260,7 @@ int dmalloc16(unsigned short** p, size_t n);
 void dfree16(unsigned short*& p);
 inline size_t act16_elems(int C, size_t hw) { return (size_t)((C + 7) / 8) * hw * 8; }
 inline bool conv16_ok(const st_ctx* c, int K) { (void)c; return K >= 8 && K % 8 == 0; }
-int wino_scratch(st_ctx* c, ConvProblem& p, bool split_kernel = false);      // room for the split-K partial sums of a Winograd launch that would otherwise leave most CUs idle
+int wino_scratch(st_ctx* c, ConvProblem& p, int splits);      // room for the split-K partial sums (WinoLaunch::splits) of a Winograd launch that would otherwise leave most CUs idle
 
 struct ProfScope {
     st_ctx* c; int idx = -1;

@@ -245,8 +245,7 @@ int st_comm_init(st_ctx* c, const char id[ST_COMM_ID_BYTES], int rank, int world
             if (unreachable) {
                 // ST2_REQUIRE_PEER_ACCESS=1: a job that must not run through host staging fails here, on every rank that sees it, before the
                 // first collective (default: a line on stderr -- the job is correct either way)
-                const char* req = getenv("ST2_REQUIRE_PEER_ACCESS");
-                if (req && *req == '1') { (void)hipGetLastError(); return fail(ST_ERR_STATE, "device %d has no direct peer access to %d of the %d visible devices and ST2_REQUIRE_PEER_ACCESS=1", c->device, unreachable, ndev - 1); }
+                if (env_on("ST2_REQUIRE_PEER_ACCESS")) { (void)hipGetLastError(); return fail(ST_ERR_STATE, "device %d has no direct peer access to %d of the %d visible devices and ST2_REQUIRE_PEER_ACCESS=1", c->device, unreachable, ndev - 1); }
                 fprintf(stderr, "st_comm_init: device %d has no direct peer access to %d of the %d visible devices (RCCL will stage through host memory)\n", c->device, unreachable, ndev - 1);
             }
         }
@@ -258,7 +257,7 @@ int st_comm_init(st_ctx* c, const char id[ST_COMM_ID_BYTES], int rank, int world
     RCCL_TRY(g_rccl.init_rank(&c->comm.comm, world, uid, rank));
     c->comm.rank = rank; c->comm.world = world;
     c->comm.ar = nullptr; c->comm.ex = nullptr; c->comm.user = nullptr;
-    { const char* e = getenv("ST2_COMM_SELF_VIA_RCCL"); c->comm.self_via_rccl = e && *e == '1'; }
+    c->comm.self_via_rccl = env_on("ST2_COMM_SELF_VIA_RCCL");
     return ST_OK;
 }
 

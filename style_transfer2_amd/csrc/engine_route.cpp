@@ -3,8 +3,6 @@
 #include "engine.h"
 
 namespace st2e {
-static bool env_off(const char* name) { const char* e = getenv(name); return e && *e == '0'; }
-
 bool lean32_enabled() { return !env_off("ST2_LEAN32"); }
 
 static bool blob_active(const st_ctx* c, int b)
@@ -57,6 +55,20 @@ static Conv16Problem shape16(int K, int M, int H, int W)
     return p;
 }
 
+// The Winograd launch of a conv of this shape, resolved once: the fp32 kernel where it has its pack and takes the shape (else
+// w.ok is false), and in its place the split-operand kernel (st_set_conv_algo(ctx, 2): the same products as six bf16 partial
+// products of split operands) where that one does too
+struct WinoChoice { WinoLaunch w; bool split; };
+static WinoChoice wino_choice(const st_ctx* c, const float* pack, const unsigned short* split_pack, int K, int M, int H, int W)
+{
+    WinoChoice ch{};
+    if (!c->wino || !pack) return ch;
+    ch.w = wino_resolve(K, M, H, W);
+    if (ch.w.ok && c->wino_split && !c->bf16 && split_pack)
+        if (const WinoLaunch ws = wino_split_resolve(K, M, H, W); ws.ok) { ch.w = ws; ch.split = true; }
+    return ch;
+}
+
 // ------------------------------------------------------------------------------------------ forward
 // `lean`: a conv blob whose only consumers are bf16 convs / a fused pool is not written in fp32 at all, a pool that follows such a
 // conv is computed in that conv's epilogue (bf16 pooled copy + arg-max map); fp32 (inside an iteration): the full-resolution blob
@@ -104,7 +116,7 @@ void plan_forward(const st_ctx* c, const ActSet& a, int last, bool lean, std::ve
             r.out16 = next16;
             if (lean && !blob_needs32(c, a, i) && i < last) {
                 // (a weighted blob gets an injected diff: classic pool backward; an average pool always runs stand-alone on the fp32 blob)
-                if (next_max_pool && !blob_active(c, i) && conv16_can_pool(shape16(L.cin, L.cout, H, W))) {
+                if (next_max_pool && !blob_active(c, i) && conv16_resolve(shape16(L.cin, L.cout, H, W)).can_pool) {
                     // the pool rides on this launch: pooled bf16 copy for the conv after it, arg-max map for the backward
                     FwdRoute& pool = fwd[i + 1];
                     pool.kind = F_BY_CONV_BELOW;
@@ -118,26 +130,24 @@ void plan_forward(const st_ctx* c, const ActSet& a, int last, bool lean, std::ve
                 }
             }
             r.bits = bits_i && r.out16;
-        } else if (c->wino && L.u_fwd && conv_wino_ok(L.cin, L.cout, H, W)) {
-            // st_set_conv_algo(ctx, 2): the same products as six bf16 partial products of split operands where the shape allows
-            const bool split = c->wino_split && !c->bf16 && L.us_fwd && conv_wino_split_ok(L.cin, L.cout, H, W);
-            r.kind = split ? F_WINO_SPLIT : F_WINO;
+        } else if (const WinoChoice ch = wino_choice(c, L.u_fwd, L.us_fwd, L.cin, L.cout, H, W); ch.w.ok) {
+            const WinoLaunch& w = ch.w;
+            r.kind = ch.split ? F_WINO_SPLIT : F_WINO;
             r.out16 = r.pack16 = next16;
             // the max pool that follows rides on this launch's epilogue (the pooled blob is written beside the conv blob);
             // an average pool does not (avepool_fwd reads the fp32 blob)
-            if (next_max_pool && !c->bf16 && (split ? conv_wino_split_can_pool(L.cin, L.cout, H, W) : conv_wino_can_pool(L.cin, L.cout, H, W))) {
+            if (next_max_pool && !c->bf16 && w.can_pool) {
                 FwdRoute& pool = fwd[i + 1];
                 pool.kind = F_BY_CONV_BELOW;
                 pool.out32 = true;
                 r.pools_next = true;
                 // ... and a one-byte arg-max map for the pool's backward (maxpool_bwd_amap_k: neither blob is read again)
-                if (want_amap && (split ? conv_wino_split_pool_amap_ok(L.cin, L.cout, H, W) : conv_wino_pool_amap_ok(L.cin, L.cout, H, W))) {
+                if (want_amap && w.pool_amap) {
                     pool.amap = AMAP_PLANAR32;
                     // lean (inside an iteration): the full-resolution blob of a pooled, un-weighted layer is dead -- the next conv
                     // reads the pooled blob, the pool's backward the arg-max map (with the ReLU sign in it) -- so it is not
                     // written (conv1_2 at 1024^2: 268 MB and a quarter of the epilogue's instructions); same values everywhere else
-                    if (lean && !blob_active(c, i) && (split ? conv_wino_split_can_skip_out(L.cin, L.cout, H, W) : conv_wino_can_skip_out(L.cin, L.cout, H, W)))
-                        r.out32 = false;
+                    if (lean && !blob_active(c, i) && w.can_skip_out) r.out32 = false;
                 }
             }
         } else {
@@ -164,6 +174,10 @@ namespace {
 struct Dgrad {
     BwdKind kind;
     bool wants16;                                  // whatever produces its incoming diff writes the bf16 copy
+    // it may take the POOLED diff and expand it through the arg-max map of the max pool above its output: conv16_body's UNPOOL builds
+    // stage the pooled diff and expand it in LDS; the Winograd kernel unpools in its input transform (the split-operand kernel has
+    // no unpooling input transform: its launches keep maxpool_bwd_amap_k)
+    bool can_unpool;
     bool reads16() const { return kind == B_SMALLM16 || kind == B_CONV16; }      // (packed first where nobody made the copy)
 };
 
@@ -172,27 +186,18 @@ Dgrad dgrad_route(const st_ctx* c, const ActSet& a, int i)
     const Layer& L = c->topo[i - 1];
     const bool below_is_conv = i - 1 >= 1 && c->topo[i - 2].is_conv;
     const bool small_m = !below_is_conv && conv_dgrad_smallM_ok(L.cout, L.cin);
-    if (small_m) return (c->bf16 && L.w_raw_r) ? Dgrad{B_SMALLM16, true} : Dgrad{B_SMALLM, false};
+    if (small_m) return (c->bf16 && L.w_raw_r) ? Dgrad{B_SMALLM16, true, false} : Dgrad{B_SMALLM, false, false};
     // (a conv of few input channels ABOVE a conv keeps the bf16 kernel but is handed an fp32 diff, which it packs)
-    if (c->bf16 && conv16_ok(c, L.cout)) return Dgrad{B_CONV16, !conv_dgrad_smallM_ok(L.cout, L.cin)};
-    if (!(c->wino && L.u_bwd && conv_wino_ok(L.cout, L.cin, a.h[i], a.w[i]))) return Dgrad{B_DIRECT, false};
-    if (!(c->wino_split && !c->bf16 && L.us_bwd && conv_wino_split_ok(L.cout, L.cin, a.h[i], a.w[i]))) return Dgrad{B_WINO, false};
+    if (c->bf16 && conv16_ok(c, L.cout))
+        return Dgrad{B_CONV16, !conv_dgrad_smallM_ok(L.cout, L.cin), conv16_resolve(shape16(L.cout, L.cin, a.h[i], a.w[i])).can_unpool};
+    const WinoChoice ch = wino_choice(c, L.u_bwd, L.us_bwd, L.cout, L.cin, a.h[i], a.w[i]);
+    if (!ch.w.ok) return Dgrad{B_DIRECT, false, false};
+    if (!ch.split) return Dgrad{B_WINO, false, ch.w.can_unpool};
     // ST2_WS_DGRAD64=0: K <= 64 launches that the fp32 kernel could unpool (conv1_2's data gradient) stay on the fp32 matrix cores.  With
     // the first split epilogue that was the faster route (404 + 60 us of maxpool_bwd_amap_k against 429 us); since the branch-free
     // epilogue it is not (same-box A/B, profiles/r05_s_ab_split.txt: 177.4 against 176.1 it/s) -- kept as a switch for the A/B only
-    if (env_off("ST2_WS_DGRAD64") && L.cout <= 64 && conv_wino_can_unpool(L.cout, L.cin, a.h[i], a.w[i])) return Dgrad{B_WINO, false};
-    return Dgrad{B_WINO_SPLIT, false};
-}
-
-// may that data gradient take the POOLED diff and expand it through the arg-max map of the max pool above its output?
-bool dgrad_can_unpool(const st_ctx* c, const ActSet& a, int i, const Dgrad& d)
-{
-    const Layer& L = c->topo[i - 1];
-    // conv16_body's UNPOOL builds stage the pooled diff and expand it in LDS; the Winograd kernel unpools in its input transform
-    // (the split-operand kernel has no unpooling input transform: its launches keep maxpool_bwd_amap_k)
-    if (d.kind == B_CONV16) return conv16_can_unpool(shape16(L.cout, L.cin, a.h[i], a.w[i]));
-    if (d.kind == B_WINO) return conv_wino_can_unpool(L.cout, L.cin, a.h[i], a.w[i]);
-    return false;
+    if (env_off("ST2_WS_DGRAD64") && L.cout <= 64 && wino_resolve(L.cout, L.cin, a.h[i], a.w[i]).can_unpool) return Dgrad{B_WINO, false, true};
+    return Dgrad{B_WINO_SPLIT, false, false};
 }
 }  // namespace
 
@@ -211,7 +216,7 @@ void plan_backward(const st_ctx* c, const ActSet& a, int top, const std::vector<
         BwdRoute& r = bwd[i];
         const int below = i - 1;
         const bool below_is_conv = below >= 1 && c->topo[below - 1].is_conv;
-        const Dgrad next = below_is_conv ? dgrad_route(c, a, below) : Dgrad{B_NONE, false};      // the data gradient that runs after this layer's
+        const Dgrad next = below_is_conv ? dgrad_route(c, a, below) : Dgrad{B_NONE, false, false};      // the data gradient that runs after this layer's
         if (L.is_conv) {
             const Dgrad d = dgrad_route(c, a, i);
             r.kind = d.kind;
@@ -246,13 +251,13 @@ void plan_backward(const st_ctx* c, const ActSet& a, int top, const std::vector<
             have16 = true;
             // ... inside the data gradient of the conv below when it has the build (maxpool_bwd_idx16_k, its full-resolution
             // output and the conv's read of it are gone)
-            if (dgrad_can_unpool(c, a, below, next)) { r.kind = B_IN_DGRAD_BELOW; pooled = true; }
+            if (next.can_unpool) { r.kind = B_IN_DGRAD_BELOW; pooled = true; }
             else { r.kind = B_POOL_IDX16; r.out16 = true; have32 = false; }
         } else if (fwd[i].amap == AMAP_PLANAR32 && !inj[below] && below_is_conv && have32) {
             // pool fused into its producing Winograd conv (fp32): through the arg-max map, ReLU mask included, inside the data
             // gradient below (maxpool_bwd_amap_k, its full-resolution output and the conv's read of it are gone; same values bit
             // for bit) or stand-alone
-            if (!c->bf16 && dgrad_can_unpool(c, a, below, next)) { r.kind = B_IN_DGRAD_BELOW; pooled = true; }
+            if (!c->bf16 && next.can_unpool) { r.kind = B_IN_DGRAD_BELOW; pooled = true; }
             else { r.kind = B_POOL_AMAP; r.out32 = true; have32 = true; have16 = false; }
         } else {
             r.kind = B_POOL_CLASSIC;

@@ -25,8 +25,7 @@ int lbfgs_alloc(st_ctx* c)
 // history is empty: the two forms keep different state.
 static bool lbfgs_wants_gram(const st_ctx* c)
 {
-    const char* e = getenv("ST2_LBFGS_FORM");
-    if (e && *e) return e[0] == 'g' || e[0] == 'G';
+    if (const char* e = env_get("ST2_LBFGS_FORM")) return e[0] == 'g' || e[0] == 'G';
     return c->bf16;
 }
 

@@ -8,6 +8,7 @@
 // (up to 2^20), so it is split along K into slabs -> [splits][C][C] fp32 partials that a second
 // kernel sums in a fixed order (bitwise reproducible, no float atomics).
 #include "st2_kernels.h"
+#include "env.h"
 #include "wave_reduce.h"
 #include <stdint.h>
 #include <stdlib.h>
@@ -31,9 +32,7 @@ GramPlan gram_plan(int C, int hw)
     // left over ran a second round alone on an idle chip (conv3_1: 72 us for 41 us of matrix work).  64-row tiles (C <= 64) are
     // HBM-bound (conv1_1: 268 MB for 8.6 GFLOP) and small (32 KiB of LDS): more workgroups per CU keep more bytes in flight.
     // ST2_GRAM_BLOCKS / ST2_GRAM_BLOCKS64 override the two targets (read per call: A/B runs in one process).
-    const char* e128 = getenv("ST2_GRAM_BLOCKS");
-    const char* e64 = getenv("ST2_GRAM_BLOCKS64");
-    const int target128 = e128 && *e128 ? atoi(e128) : 512, target64 = e64 && *e64 ? atoi(e64) : 1024;
+    const int target128 = (int)env_int("ST2_GRAM_BLOCKS", 512), target64 = (int)env_int("ST2_GRAM_BLOCKS64", 1024);
     int want = p.bt == 128 ? target128 / p.tiles : (target64 + p.tiles - 1) / p.tiles;
     const int max_splits = (hw + 4 * GKT - 1) / (4 * GKT); // at least 128 K per slab
     if (want > max_splits) want = max_splits;
@@ -280,8 +279,7 @@ hipError_t launch_gram_partial(const float* F, float* slabs, int C, int hw, cons
     const unsigned grid = (unsigned)(pl.tiles * pl.splits);
     GramRoi roi = roi_in ? *roi_in : GramRoi{0, 0, hw, hw, (size_t)hw};   // default: one "row" of hw pixels
     // whole blob, 32-pixel steps, 16-byte aligned rows, 32-bit buffer offsets: the LDS-DMA pipeline
-    static const bool no_dma = [] { const char* e = getenv("ST2_GRAM_DMA"); return e && *e == '0'; }();
-    if (!roi_in && !no_dma && hw % 32 == 0 && pl.kslab % 32 == 0 && (reinterpret_cast<uintptr_t>(F) & 15) == 0 &&
+    if (!roi_in && !env_off("ST2_GRAM_DMA") && hw % 32 == 0 && pl.kslab % 32 == 0 && (reinterpret_cast<uintptr_t>(F) & 15) == 0 &&
         4ull * C * hw < 0xfffffff0ull) {
         const unsigned fb = (unsigned)(4ull * C * hw);
         if (pl.bt == 128) gram_partial_dma_128<<<grid, 256, 0, s>>>(F, fb, slabs, C, hw, t1, pl.kslab);
@@ -389,8 +387,7 @@ hipError_t launch_gram_reduce(const float* slabs, float* folded, const float* ta
     const int cc = C * C;
     int splits = pl.splits;
     // ST2_GRAM_REDUCE=2 keeps the two-stage reduction (read per launch)
-    const char* two = getenv("ST2_GRAM_REDUCE");
-    if (splits > 32 && C % 4 == 0 && pl.bt % 4 == 0 && !(two && *two == '2')) {
+    if (splits > 32 && C % 4 == 0 && pl.bt % 4 == 0 && env_int("ST2_GRAM_REDUCE", 1) != 2) {
         const bool small = cc <= 128 * 128;
         const int grid = reduce_grid((size_t)cc, small ? 32 : 128, kMaxPartials);
         if (n_partial) *n_partial = grid;

@@ -30,9 +30,9 @@ struct ConvProblem {
     int relu;               // forward epilogue
     unsigned long long* stamps = nullptr;   // diagnostic configs only
     unsigned short* out16 = nullptr;        // optional (direct kernel): bf16 channel-blocked copy of `out`, [M/8][H][W][8], M % 8 == 0
-    float* pool_out = nullptr;              // optional (Winograd forward, see conv_wino_can_pool): also write maxpool2x2/2 of `out`
+    float* pool_out = nullptr;              // optional (Winograd forward, see WinoLaunch::can_pool): also write maxpool2x2/2 of `out`
     unsigned char* pool_amap = nullptr;     // optional, with pool_out: [M][ph][pw] bytes = first-max slot | (max > 0) << 2 (launch_maxpool_bwd_amap)
-    // optional (Winograd data-gradient directly below a max-pool, conv_wino_can_unpool): `in` is then the POOLED diff [K][H/2][W/2] and
+    // optional (Winograd data-gradient directly below a max-pool, WinoLaunch::can_unpool): `in` is then the POOLED diff [K][H/2][W/2] and
     // unpool_amap the pool's arg-max map [K][H/2][W/2] (ConvProblem::pool_amap of the forward); the launch unpools while it stages
     const unsigned char* unpool_amap = nullptr;
     float* scratch = nullptr;               // optional: room for split-K partial sums (Winograd launches with few workgroups)
@@ -53,15 +53,32 @@ hipError_t launch_conv3x3_cfg(const ConvProblem& p, int cfg, hipStream_t s);
 size_t wino_pack_floats(int K, int M);
 void pack_wino_weights_fwd(const float* w, int Cout, int Cin, float* dst);
 void pack_wino_weights_dgrad(const float* w, int Cout, int Cin, float* dst);
-bool conv_wino_ok(int K, int M, int H, int W);
+// Everything the planner and the launcher know about a Winograd-type launch of shape (K, M, H, W), resolved in one place.
+// The variants: 128 channels x 4x32 pixels; 64 channels x 8x32 pixels (tile groups split over the waves); the same with the
+// POSITIONS split over the waves (half the U stream); 128 x 4x32 with EIGHT waves (two per SIMD, positions split between the
+// partners); 64 x 4x32, positions split between two waves, two workgroups per CU.  The values are those of ST2_WINO_CFG.
+enum WinoVariant {
+    WV_128x128 = 0, WV_64x256 = 1, WV_PS64x256 = 3, WV_W8_128x128 = 6, WV_H4_64x128 = 8,
+    // the same builds with cycle stamps (diagnostic; aligned widths, one pass)
+    WV_128x128_STAMPED = 2, WV_64x256_STAMPED = 5, WV_PS64x256_STAMPED = 4, WV_W8_128x128_STAMPED = 7, WV_H4_64x128_STAMPED = 9,
+};
+struct WinoLaunch {
+    bool ok;                 // the family takes this shape at all
+    WinoVariant variant;     // resolved: forced value, defaults and the fallbacks of widths that are no multiple of 4 applied
+    bool quad, big;          // W % 4 == 0; runs a BIG build (a tensor of 4 GiB or more)
+    int bm, prows;           // channels / pixel rows per workgroup
+    long long nblk;          // workgroups of one pass
+    int splits;              // split-K factor of the automatic path (1 = none); needs splits * M * H * W floats of scratch
+    bool can_pool;           // a forward launch may fuse the following max-pool (ConvProblem::pool_out) ...
+    bool pool_amap;          // ... and then fills ConvProblem::pool_amap ...
+    bool can_skip_out;       // ... and may then pass out == nullptr
+    bool can_unpool;         // a data-gradient launch may take ConvProblem::unpool_amap
+};
+WinoLaunch wino_resolve(int K, int M, int H, int W, int forced_variant = -1);      // forced_variant >= 0: that variant, one pass
+int wino_splitk(long long nblk, int nch);                    // the split-K rule of both Winograd families
 // dx = pool backward of dy through the arg-max map a Winograd forward wrote (ConvProblem::pool_amap), ReLU mask of the pooled-from conv
 // blob included (bit 2); H even, W % 4 == 0.  352 instead of 603 bytes moved per 64 outputs: neither the conv blob nor the pooled one is read.
 hipError_t launch_maxpool_bwd_amap(const float* dy, const unsigned char* amap, float* dx, int C, int H, int W, hipStream_t s);
-bool conv_wino_pool_amap_ok(int K, int M, int H, int W);   // ... and such a launch fills ConvProblem::pool_amap
-bool conv_wino_can_unpool(int K, int M, int H, int W);   // a data-gradient launch of this shape may take ConvProblem::unpool_amap
-bool conv_wino_can_skip_out(int K, int M, int H, int W);   // a forward launch with pool_out + pool_amap may pass out == nullptr
-bool conv_wino_can_pool(int K, int M, int H, int W);   // launch_conv3x3_wino may fuse the following max-pool (ConvProblem::pool_out)
-int conv_wino_splits(int K, int M, int H, int W);   // split-K factor the automatic path would use (1 = none); needs splits*M*H*W floats of scratch
 hipError_t launch_conv3x3_wino(const ConvProblem& p, hipStream_t s);
 hipError_t launch_conv3x3_wino_cfg(const ConvProblem& p, int variant, hipStream_t s);
 hipError_t launch_wino_combine(const float* scratch, int splits, const float* bias, int relu, const float* mask_src, const float* inject,
@@ -72,12 +89,8 @@ hipError_t launch_wino_combine(const float* scratch, int splits, const float* bi
 size_t wino_split_pack_elems(int K, int M);                  // bf16 elements
 void pack_wino_split_weights_fwd(const float* w, int Cout, int Cin, unsigned short* dst);
 void pack_wino_split_weights_dgrad(const float* w, int Cout, int Cin, unsigned short* dst);
-bool conv_wino_split_ok(int K, int M, int H, int W);
-int conv_wino_split_splits(int K, int M, int H, int W);
-bool conv_wino_split_can_pool(int K, int M, int H, int W);
-bool conv_wino_split_pool_amap_ok(int K, int M, int H, int W);
-bool conv_wino_split_can_skip_out(int K, int M, int H, int W);
-hipError_t launch_conv3x3_wino_split(const ConvProblem& p, hipStream_t s);   // 0: 128 ch x 4x32 px, 1: 64 ch x 8x32 px
+WinoLaunch wino_split_resolve(int K, int M, int H, int W);   // (64 channels x 8x32 pixels; can_unpool is always false)
+hipError_t launch_conv3x3_wino_split(const ConvProblem& p, hipStream_t s);
 // conv1_1-style dgrad (tiny M): direct VALU kernel, w is the ORIGINAL (Cout,Cin,3,3) layout
 // conv1_1's data gradient on the matrix cores (conv3x3_dgrad_first.hip): Z = A @ dy (1x1, 9 M rows) + 9 M shifted adds; Cin <= 3
 bool conv_dgrad_first_ok(int Cout, int Cin, int H, int W, bool bf16);
@@ -114,14 +127,14 @@ struct Conv16Problem {
     unsigned short* out16; const float* mask_src; const float* inject;
     int K, M, MPad, H, W, relu;
     const unsigned short* mask16 = nullptr; // dgrad: ReLU mask from the bf16 copy of the blob below (instead of mask_src)
-    // forward, optional (conv16_can_pool): max-pool 2x2/2 (Caffe ceil mode, first-max) of this launch's output
+    // forward, optional (Conv16Launch::can_pool): max-pool 2x2/2 (Caffe ceil mode, first-max) of this launch's output
     unsigned short* pool16 = nullptr;       // bf16 channel-blocked pooled copy [M/8][ph][pw][8]
     float* pool32 = nullptr;                // fp32 pooled blob [M][ph][pw]
     unsigned char* amap = nullptr;          // [M/8][ph][pw][8] bytes: bits 0-1 arg-max slot (row-major in the window), bit 2 maximum > 0
     // data-gradient, optional: the style gradient of the blob this launch differentiates rides on the launch,
     //     out = mask(conv) + D' @ F        (D' = sw / norm * c2 * D as hi + lo bf16 terms: launch_style_fuse_pack; F = s_in16, M channels)
     const unsigned short* s_in16 = nullptr; const unsigned short* s_wpack16 = nullptr;
-    // data-gradient directly below a max-pool, optional (conv16_can_unpool): in16 is the POOLED diff [K/8][H/2][W/2][8] and unpool_amap
+    // data-gradient directly below a max-pool, optional (Conv16Launch::can_unpool): in16 is the POOLED diff [K/8][H/2][W/2][8] and unpool_amap
     // the pool's arg-max map; the launch expands them in its staged tile (maxpool_bwd_idx16_k and its output are not needed)
     const unsigned char* unpool_amap = nullptr;
     // one bit per element of a post-ReLU blob, "its bf16 copy is non-zero", in the accumulator layout of the 32 x 32 MFMA tile:
@@ -139,8 +152,15 @@ hipError_t launch_style_fuse_pack(const float* D, int ld, int C, int MPad, float
 // style gradient without materialising it; *n_partial partials in `partial`
 int style_s2_trace_blocks(int C);
 hipError_t launch_style_s2_trace(const float* D, int ld, const float* A, int C, double n, float c2, float* partial, int* n_partial, hipStream_t s);
-bool conv16_can_pool(const Conv16Problem& p);
-bool conv16_can_unpool(const Conv16Problem& p);
+// the tile a bf16 launch runs and what it may fuse, resolved in one place for the planner and the launcher
+struct Conv16Launch {
+    int cfg;                 // 0: 64 channels x 256 pixels, 1: 128 x 128, 2: 64 x 128, 3: 64 x 512
+    bool sb;                 // the single-staging-buffer builds of tile 0 (short reductions)
+    int BM, ROWS;            // channels / pixel rows per workgroup
+    bool can_pool;           // a forward launch may pool its own output (Conv16Problem::pool16 / pool32 / amap)
+    bool can_unpool;         // a data-gradient launch may take the pooled diff + the pool's arg-max map (Conv16Problem::unpool_amap)
+};
+Conv16Launch conv16_resolve(const Conv16Problem& p);
 // dx16 = pool backward of dy16 through the arg-max map (all channel-blocked, C % 8 == 0), ReLU mask of the pooled-from blob included
 hipError_t launch_maxpool_bwd_idx16(const unsigned short* dy16, const unsigned char* amap, unsigned short* dx16, int C, int H, int W, hipStream_t s);
 size_t conv16_pack_elems(int K, int M);

@@ -375,6 +375,33 @@ def test_product_code_never_imports_the_oracle():
     assert 'oracle' not in open(os.path.join(REPO, 'tools', 'probes', 'probes.hip')).read()
 
 
+def test_every_environment_switch_the_engine_reads_is_in_the_readme_table():
+    """Every ST2_* switch of style_transfer2_amd/csrc is read through env.h's helpers (no getenv anywhere else), and the set of names
+    handed to them equals the set in README.md's environment table, bar the names only Python reads."""
+    python_only = {'ST2_HIP_LIB', 'ST2_WS_VAR'}        # capi.load_library, build.py
+    csrc = os.path.join(REPO, 'style_transfer2_amd', 'csrc')
+    read = set()
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith(('.cpp', '.hip', '.h')):
+            continue
+        text = open(os.path.join(csrc, f)).read()
+        if f != 'env.h':
+            assert 'getenv' not in text, f
+        calls = re.findall(r'\benv_(?:off|on|int|get)\(\s*([^,)]*)', text)
+        for arg in calls:
+            if f == 'env.h' and arg.strip() in ('const char* name', 'name'):
+                continue                                # the helpers' own definitions
+            m = re.fullmatch(r'"(ST2_[A-Z0-9_]+)"', arg.strip())
+            assert m, '%s: %s is not a literal switch name' % (f, arg)
+            read.add(m.group(1))
+    table = set()
+    for line in open(os.path.join(REPO, 'README.md')):
+        if line.startswith('|'):
+            table |= set(re.findall(r'ST2_[A-Z0-9_]+', line))
+    assert len(read) > 40
+    assert read | python_only == table, (sorted(read - table), sorted(table - read - python_only))
+
+
 def _code_object_kernels(lib):
     """{kernel name: metadata dict} of every gfx950 code object bundled in a shared library (llvm-objdump --offloading
     + llvm-readelf --notes on a scratch copy)."""

@@ -487,8 +487,9 @@ int st_bench_conv(int device_id, int K, int M, int H, int W, int cfg, int dgrad_
     const bool zero_in = getenv("ST2_BENCH_ZERO") && *getenv("ST2_BENCH_ZERO") == '1';
     for (auto& x : hin) x = zero_in ? 0.f : rnd();
     const bool wino = cfg >= 100;      // 100: choose, 101: 128 ch x 4x32 px, 102: 64 ch x 8x32 px, 104: 64 ch x 8x32 px position-split, 107: 128 ch x 4x32 px with 8 waves, 109: 64 ch x 4x32 px half tile (two workgroups per CU); 103/106/105/108/110: those stamped
+    const WinoLaunch wl = wino ? wino_resolve(K, M, H, W, cfg - 101) : WinoLaunch{};      // (cfg 100 = -1: the automatic path)
     if (wino) {
-        if (!conv_wino_ok(K, M, H, W)) return fail(ST_ERR_ARG, "shape not eligible for the Winograd kernel");
+        if (!wl.ok) return fail(ST_ERR_ARG, "shape not eligible for the Winograd kernel");
         pk.assign(wino_pack_floats(K, M), 0.f);
         pack_wino_weights_fwd(w.data(), M, K, pk.data());
     } else
@@ -513,8 +514,8 @@ int st_bench_conv(int device_id, int K, int M, int H, int W, int cfg, int dgrad_
     if (cfg < 0) cfg = conv_pick_config(p);
     if (cfg_used) *cfg_used = cfg;
     float* dscr = nullptr;
-    if (cfg == 100 && conv_wino_splits(K, M, H, W) > 1) {      // the automatic Winograd path may split K
-        p.scratch_floats = (size_t)conv_wino_splits(K, M, H, W) * n_out;
+    if (wl.splits > 1) {      // the automatic Winograd path may split K
+        p.scratch_floats = (size_t)wl.splits * n_out;
         ST_TRY(dmalloc(&dscr, p.scratch_floats));
         p.scratch = dscr;
     }

@@ -658,7 +658,7 @@ extern "C" int st_probe_wino_split_product(int device_id, int K, int M, int H, i
                                            double* loop_cycles, double* clock_mhz, double* pro_cycles, double* epi_cycles)
 {
     using namespace st2;
-    if (!conv_wino_split_ok(K, M, H, W) || iters <= 0) { snprintf(g_err, sizeof g_err, "shape not supported"); return 1; }
+    if (!wino_split_resolve(K, M, H, W).ok || iters <= 0) { snprintf(g_err, sizeof g_err, "shape not supported"); return 1; }
     WS_TRY(hipSetDevice(device_id));
     const size_t n_in = (size_t)K * H * W, n_out = (size_t)M * H * W;
     std::vector<float> w((size_t)M * K * 9), hin(n_in), hb(M);
