@@ -261,6 +261,38 @@ int st_tile_plan(st_ctx* ctx, int phase, int n_peers, const st_tile_peer* peers)
 int st_tile_step(st_ctx* ctx, double* trace);
 int st_tile_get_tile(st_ctx* ctx, float* out_hwc);                           /* this rank's tile of the current iterate, (th, tw, 3) deprocessed */
 
+/* ---- the style targets of a tile-sharded job, sharded as well -------------------------------------------------------------------
+ * st_set_style forwards the WHOLE style image on the context that calls it; in a sharded job every rank would repeat that pass, and the
+ * style image would have to fit one engine.  Here the style image has a tile grid of its own (tiling.style_grid: edges on multiples of
+ * the total stride of `last_blob`, the deepest blob whose Gram is wanted; apron = its receptive reach).  Each rank forwards only its
+ * window -- a feature inside the tile is then what the whole-image forward computes -- and contracts F F^T over the tile's region of
+ * blobs 0 .. last_blob; the raw sums are added over the ranks and divided by the GLOBAL C h w (worker.py:114).
+ *   hwc, H, W, is_u8: this rank's window of the gH x gW style image, as st_set_style takes an image; hwc == NULL: this rank has no style
+ *   tile and contributes zeros (H, W and the geometry after gW are ignored).  (wy0, wx0): origin of the window; [ty0, ty1) x [tx0, tx1): the
+ *   tile; global pixels.  ST_ERR_ARG: a window outside the image, a tile outside the window or empty, an origin or inner edge that is no
+ *   multiple of last_blob's total stride, a net with an average pool at or below last_blob.
+ * The window is forwarded (every fp32 blob written) in an activation set of its own unless it has the iterate's size, exactly as
+ * st_set_style does; the iterate, the content features and st_tile_configure's geometry are not touched, and none of them is needed.
+ * The Gram partials are the fp32 region-of-interest kernel on the fp32 blob under every st_set_precision and st_set_gram_algo -- the
+ * kernel of st_set_style's targets under bf16 operands, and the one the tile-sharded iteration keeps (see st_set_gram_algo). */
+/* raw sums of this rank into one flat device buffer owned by the context: blob 0's 3 x 3, blob 1's C x C, ... blob last_blob's, back to back
+ * (*n_floats = sum of C^2).  The caller all-reduces it over the ranks, then calls st_tile_style_commit.  Returns with the buffer in place. */
+int st_tile_style_partials(st_ctx* ctx, const void* hwc, int H, int W, int is_u8, int gH, int gW, int wy0, int wx0, int ty0, int tx0,
+                           int ty1, int tx1, int last_blob, float** dev_ptr, int* n_floats);
+/* targets of blobs 0 .. last_blob = reduced sums / (C gh gw), (gh, gw) the blob's size for the gH x gW image.  These blobs then have a
+ * target, the blobs above last_blob have none (st_set_style gives every blob one): an evaluation, whole-image or tiled, whose weight
+ * table puts a style weight on a blob without target fails with ST_ERR_STATE naming it.  ST_ERR_STATE without partials. */
+int st_tile_style_commit(st_ctx* ctx);
+/* partials -> all-reduce on the engine's stream (RCCL, or the caller's transport) -> commit.  COLLECTIVE: every rank of the communicator
+ * calls it, the ranks without a style tile with hwc == NULL.  ST_ERR_STATE before st_comm_init / st_comm_callbacks; an argument error is
+ * returned before the all-reduce, so the caller must then release the other ranks.  Across two or more devices the collective has not
+ * been exercised yet (like the rest of the RCCL path: the tests run the ranks on one GPU over a caller-supplied transport, and a
+ * one-rank RCCL communicator). */
+int st_tile_set_style(st_ctx* ctx, const void* hwc, int H, int W, int is_u8, int gH, int gW, int wy0, int wx0, int ty0, int tx0,
+                      int ty1, int tx1, int last_blob);
+/* test hook: the style target of `blob`, C x C.  ST_ERR_STATE when the context holds none for it. */
+int st_get_style_gram(st_ctx* ctx, int blob, float* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,10 @@ PROTOTYPES = {
     'st_tile_plan': (c_int, [c_void_p, c_int, c_int, POINTER(TilePeer)]),
     'st_tile_step': (c_int, [c_void_p, c_void_p]),
     'st_tile_get_tile': (c_int, [c_void_p, c_void_p]),
+    'st_tile_style_partials': (c_int, [c_void_p, c_void_p] + [c_int] * 12 + [POINTER(c_void_p), POINTER(c_int)]),
+    'st_tile_style_commit': (c_int, [c_void_p]),
+    'st_tile_set_style': (c_int, [c_void_p, c_void_p] + [c_int] * 12),
+    'st_get_style_gram': (c_int, [c_void_p, c_int, c_void_p]),
 }
 
 _lib = None

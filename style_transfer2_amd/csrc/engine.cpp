@@ -549,6 +549,7 @@ int st_create(st_ctx** out, int device_id, const st_layer_desc* layers, int n_la
     HIP_TRY(hipStreamCreate(&c->stream));
     c->content_feat.assign(c->nb, nullptr);
     c->style_gram.assign(c->nb, nullptr);
+    c->style_valid.assign(c->nb, 0);
     c->inject.assign(c->nb, nullptr);
     c->inject_roi_zero.assign(c->nb, 0);
     c->layer_part.assign(c->nb, nullptr);
@@ -595,7 +596,7 @@ int st_destroy(st_ctx* c)
     for (auto& p : c->sfuse_w) dfree16(p);
     dfree(c->diffA); dfree(c->diffB); dfree(c->stmp); dfree(c->gram_slabs); dfree(c->gram_fold); dfree(c->dbuf); dfree16(c->d16); dfree16(c->dsplit); dfree(c->conv_scratch);
     comm_free(c);
-    dfree(c->tile.p1); dfree(c->tile.p2); dfree(c->tile.p3); dfree(c->tile.pd); dfree(c->tile.wgrad); dfree(c->tile.lb_x); dfree(c->tile.lb_sums);
+    dfree(c->tile.p1); dfree(c->tile.p2); dfree(c->tile.p3); dfree(c->tile.pd); dfree(c->tile.wgrad); dfree(c->tile.lb_x); dfree(c->tile.lb_sums); dfree(c->tile.sp);
     dfree(c->norms); dfree(c->image_part); dfree(c->trace_dev); dfree(c->lb_part); dfree(c->hwc_dev);
     if (c->lb_dev) (void)hipFree(c->lb_dev);
     if (c->lb_gram) (void)hipFree(c->lb_gram);
@@ -942,7 +943,7 @@ int st_set_style(st_ctx* c, const void* hwc, int H, int W, int is_u8)
     if (!same) act_free(aux);
     else c->act.valid_to = -1;
     dfree(tmp);
-    if (r == ST_OK) c->have_style = true;
+    if (r == ST_OK) { c->have_style = true; std::fill(c->style_valid.begin(), c->style_valid.end(), 1); }
     return r;
 }
 

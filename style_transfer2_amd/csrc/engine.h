@@ -102,6 +102,9 @@ struct ActSet {                    // activations of one forward geometry
 struct ActiveLayer { int blob; float cw, sw, dw; bool c, s, d; };
 
 inline bool nonzero(float w) { return fabsf(w) > 1e-15f; }   // NaN compares false: worker.py:234
+
+// one rank's share of a tile-sharded image, in global pixels: the gH x gW image, the origin of the window this context holds, the tile
+struct TileGeom { int gH = 0, gW = 0, wy0 = 0, wx0 = 0, ty0 = 0, tx0 = 0, ty1 = 0, tx1 = 0; };
 }  // namespace st2e
 
 using namespace st2e;
@@ -133,6 +136,7 @@ struct st_ctx {
     std::vector<float*> content_feat;              // per blob
     float* content_x = nullptr;                    // preprocessed content image (for resample_content)
     std::vector<float*> style_gram;                // per blob, C*C
+    std::vector<char> style_valid;                 // per blob: style_gram holds a target (st_set_style: every blob; st_tile_style_commit: 0 .. last_blob)
     bool have_content = false, have_style = false;
     // objective
     std::vector<ActiveLayer> rows;                 // every row of the weights table, in order
@@ -216,9 +220,8 @@ struct st_ctx {
     bool have_cur = false;
     float last_loss = 0.f;
     // tile-sharded mode (BASELINE config 5): this context holds ONE window of a larger image
-    struct Tile {
+    struct Tile : TileGeom {
         bool on = false;
-        int gH = 0, gW = 0, wy0 = 0, wx0 = 0, ty0 = 0, tx0 = 0, ty1 = 0, tx1 = 0;
         float *p1 = nullptr, *p2 = nullptr, *p3 = nullptr, *pd = nullptr;    // reduce buffers (device)
         size_t p1_n = 0, p2_n = 0, p3_n = 0, pd_n = 0;
         bool s2_in_p2 = false;
@@ -227,12 +230,16 @@ struct st_ctx {
         // fused L-BFGS over the sharded image (engine_comm.cpp): this rank's tile of x as a compact (3, th, tw) vector, the sums of
         // one inner-product pass (all-reduced), and the global image size the unit-RMS first direction divides by
         float* lb_x = nullptr; float* lb_sums = nullptr; size_t lb_n = 0;
+        // the sharded style pass (st_tile_style_partials -> all-reduce -> st_tile_style_commit): raw Gram sums of blobs 0 .. sp_last over
+        // this rank's tile of the sp_gH x sp_gW style image, back to back; sp_last < 0: no partials wait for a commit
+        float* sp = nullptr; size_t sp_cap = 0; int sp_n = 0, sp_last = -1, sp_gH = 0, sp_gW = 0;
     } tile;
     // communicator of the tile-sharded mode (engine_comm.cpp): RCCL over xGMI, or caller-supplied transport functions (tests)
     struct Comm {
         void* lib = nullptr;                       // librccl.so, loaded on first use
         void* comm = nullptr;                      // ncclComm_t
         int rank = 0, world = 1;
+        bool set = false;                          // st_comm_init / st_comm_callbacks has run (a fresh context looks like world 1 otherwise)
         st_allreduce_fn ar = nullptr; st_exchange_fn ex = nullptr; void* user = nullptr;
         struct Peer { int peer = 0; std::vector<int> send, recv; float *sbuf = nullptr, *rbuf = nullptr; size_t sn = 0, rn = 0; };
         std::vector<Peer> plan[3];                 // per phase (ST_TILE_PLAN_*): the peers this rank exchanges strips with
@@ -250,6 +257,11 @@ struct st_ctx {
     size_t ev_used = 0;
 
     int blob_c(int i) const { return act.C[i]; }
+    int blob_c_topo(int i) const                   // channels of blob i from the topology alone (no activation set needed)
+    {
+        for (int k = i; k >= 1; --k) if (topo[k - 1].is_conv) return topo[k - 1].cout;
+        return 3;
+    }
 };
 
 namespace st2e {
@@ -332,4 +344,5 @@ int lbfgs_alloc(st_ctx* c);
 LbfgsArgs lbfgs_args(st_ctx* c, int apply);
 // ---------------------------------------------------------------------------------------- engine_comm.cpp
 void comm_free(st_ctx* c);
+int comm_allreduce(st_ctx* c, float* buf, int n);  // in-place sum of n floats over the ranks, ordered on the engine's stream
 }  // namespace st2e

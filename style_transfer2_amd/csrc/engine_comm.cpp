@@ -68,13 +68,13 @@ void comm_free(st_ctx* c)
     if (m.comm && g_rccl.destroy) (void)g_rccl.destroy(m.comm);
     m.comm = nullptr;
     m.ar = nullptr; m.ex = nullptr; m.user = nullptr;
-    m.world = 1; m.rank = 0;
+    m.world = 1; m.rank = 0; m.set = false;
 }
 
 static bool comm_ready(const st_ctx* c) { return c->comm.world == 1 || c->comm.comm || (c->comm.ar && c->comm.ex); }
 
 // in-place sum of n floats over the ranks, ordered on the engine's stream
-static int comm_allreduce(st_ctx* c, float* buf, int n)
+int comm_allreduce(st_ctx* c, float* buf, int n)
 {
     st_ctx::Comm& m = c->comm;
     if ((m.world == 1 && !m.comm) || n <= 0 || !buf) return ST_OK;         // (a one-rank RCCL communicator still runs the collective)
@@ -258,6 +258,7 @@ int st_comm_init(st_ctx* c, const char id[ST_COMM_ID_BYTES], int rank, int world
     c->comm.rank = rank; c->comm.world = world;
     c->comm.ar = nullptr; c->comm.ex = nullptr; c->comm.user = nullptr;
     c->comm.self_via_rccl = env_on("ST2_COMM_SELF_VIA_RCCL");
+    c->comm.set = true;
     return ST_OK;
 }
 
@@ -267,6 +268,7 @@ int st_comm_callbacks(st_ctx* c, int rank, int world, st_allreduce_fn allreduce,
     if (c->comm.comm && g_rccl.destroy) { (void)g_rccl.destroy(c->comm.comm); c->comm.comm = nullptr; }
     c->comm.rank = rank; c->comm.world = world;
     c->comm.ar = allreduce; c->comm.ex = exchange; c->comm.user = user;
+    c->comm.set = true;
     return ST_OK;
 }
 
@@ -467,6 +469,19 @@ int st_tile_step(st_ctx* c, double* trace)
     }
     c->comm.steps += 1;
     return ST_OK;
+}
+
+// The style targets of the sharded job from the sharded style image: this rank's raw Gram sums (st_tile_style_partials; zeros without a
+// tile), summed over the ranks on the engine's stream, normalised by the global sizes (st_tile_style_commit).  Collective.
+int st_tile_set_style(st_ctx* c, const void* hwc, int H, int W, int is_u8, int gH, int gW, int wy0, int wx0, int ty0, int tx0, int ty1, int tx1, int last_blob)
+{
+    if (!c) return fail(ST_ERR_ARG, "ctx is NULL");
+    if (!c->comm.set) return fail(ST_ERR_STATE, "st_comm_init / st_comm_callbacks first: st_tile_set_style is a collective");
+    float* buf = nullptr;
+    int n = 0;
+    ST_TRY(st_tile_style_partials(c, hwc, H, W, is_u8, gH, gW, wy0, wx0, ty0, tx0, ty1, tx1, last_blob, &buf, &n));
+    ST_TRY(comm_allreduce(c, buf, n));
+    return st_tile_style_commit(c);
 }
 
 int st_tile_get_tile(st_ctx* c, float* out_hwc)

@@ -14,6 +14,8 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
         if (al.c && (!c->have_content || c->cH != c->H || c->cW != c->W))
             return fail(ST_ERR_STATE, "content features missing or of a different size than the input");
         if (al.s && !c->have_style) return fail(ST_ERR_STATE, "style Gram matrices missing");
+        if (al.s && !c->style_valid[al.blob])
+            return fail(ST_ERR_STATE, "blob %d (%s) carries a style weight but has no style target: the sharded style pass (st_tile_set_style) stopped below it", al.blob, c->blob_names[al.blob].c_str());
     }
     // lean data flow: tensors nothing reads are not written.  bf16: the whole evaluation (st_set_precision(ctx, 1)); fp32: inside an
     // iteration (st_step / st_step_begin), where no caller can ask for a blob afterwards -- st_opfunc keeps every blob for the test hooks.

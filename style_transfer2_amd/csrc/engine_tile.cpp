@@ -7,13 +7,13 @@
 namespace st2e {
 struct BlobRoi { int y0, x0, y1, x1; double n_global; };
 
-BlobRoi tile_roi(const st_ctx* c, int b)
+// the tile's region in blob b of the activation set `a` that holds the window (geometry `t`: the iterate's c->tile, or the style
+// image's of st_tile_style_partials)
+BlobRoi tile_roi(const st_ctx* c, const ActSet& a, const TileGeom& t, int b)
 {
-    const st_ctx::Tile& t = c->tile;
     int s = 1, gh = t.gH, gw = t.gW;
     for (int i = 1; i <= b; ++i)
         if (!c->topo[i - 1].is_conv) { s *= 2; gh = pooled_size(gh); gw = pooled_size(gw); }
-    const ActSet& a = c->act;
     BlobRoi r;
     r.y0 = (t.ty0 - t.wy0) / s; r.x0 = (t.tx0 - t.wx0) / s;
     r.y1 = t.ty1 == t.gH ? a.h[b] : (t.ty1 - t.wy0) / s;
@@ -21,6 +21,7 @@ BlobRoi tile_roi(const st_ctx* c, int b)
     r.n_global = (double)a.C[b] * gh * gw;
     return r;
 }
+BlobRoi tile_roi(const st_ctx* c, int b) { return tile_roi(c, c->act, c->tile, b); }
 int tile_ensure(float** p, size_t* cap, size_t n)
 {
     if (n > *cap) { dfree(*p); ST_TRY(dmalloc(p, n)); *cap = n; }
@@ -113,6 +114,8 @@ int st_tile_forward(st_ctx* c, float** dev_ptr, int* n_floats)
         n1 += 4 + (al.s ? (size_t)a.C[al.blob] * a.C[al.blob] : 0);
         if (al.c && (!c->have_content || c->cH != c->H || c->cW != c->W)) return fail(ST_ERR_STATE, "content features missing");
         if (al.s && !c->have_style) return fail(ST_ERR_STATE, "style Gram matrices missing");
+        if (al.s && !c->style_valid[al.blob])
+            return fail(ST_ERR_STATE, "blob %d (%s) carries a style weight but has no style target: the sharded style pass (st_tile_set_style) stopped below it", al.blob, c->blob_names[al.blob].c_str());
     }
     ST_TRY(ensure_content_features(c));
     ST_TRY(tile_ensure(&c->tile.p1, &c->tile.p1_n, std::max<size_t>(n1, 1)));
@@ -426,6 +429,130 @@ int st_tile_strips(st_ctx* c, void* tensor_dev, int C, int wh, int ww, int n, co
     t.total = total;
     HIP_TRY(launch_strip_copy((float*)tensor_dev, (float*)buf_dev, t, C, wh, ww, mode, c->stream));
     if (!c->tile.fused) HIP_TRY(hipStreamSynchronize(c->stream));
+    return ST_OK;
+}
+
+// ---- the style targets of a sharded job, sharded as well -------------------------------------------------------------------------
+// The style image has a tile grid of its own (tiling.style_grid).  Each rank forwards ITS window of the style image -- a feature inside
+// the tile is what the whole-image forward computes, the apron argument of tiling.py -- and sums F F^T over the tile's region of every
+// blob up to last_blob, un-normalised; the caller (or st_tile_set_style) all-reduces the buffer; the commit divides by the global C h w
+// (worker.py:114).  Nothing here reads or writes c->tile's geometry: the pass neither needs st_tile_configure nor disturbs it.
+int st_tile_style_partials(st_ctx* c, const void* hwc, int H, int W, int is_u8, int gH, int gW, int wy0, int wx0, int ty0, int tx0, int ty1, int tx1,
+                           int last_blob, float** dev_ptr, int* n_floats)
+{
+    if (c) c->epoch++;
+    if (!c) return fail(ST_ERR_ARG, "ctx is NULL");
+    if (last_blob < 0 || last_blob >= c->nb) return fail(ST_ERR_ARG, "last_blob %d is not a blob of this net (0 .. %d)", last_blob, c->nb - 1);
+    if (gH <= 0 || gW <= 0) return fail(ST_ERR_ARG, "bad style image size %d x %d", gH, gW);
+    for (int i = 0; i < last_blob; ++i)
+        if (c->topo[i].ave) return fail(ST_ERR_ARG, "tile-sharded mode does not run average pools (layer %s); use st_set_style", c->topo[i].name.c_str());
+    int stride = 1;
+    for (int i = 0; i < last_blob; ++i) if (!c->topo[i].is_conv) stride *= 2;
+    if (hwc) {
+        if (H <= 0 || W <= 0 || wy0 < 0 || wx0 < 0 || wy0 + H > gH || wx0 + W > gW || ty0 < wy0 || tx0 < wx0 || ty1 > wy0 + H || tx1 > wx0 + W ||
+            ty1 <= ty0 || tx1 <= tx0)
+            return fail(ST_ERR_ARG, "style tile/window geometry is inconsistent with the %dx%d window of the %dx%d style image", H, W, gH, gW);
+        // the pooling windows of the window must be the global ones, and a tile must own whole cells of the deepest blob: origins and
+        // inner edges on multiples of its total stride (tiling.TileGrid cuts so)
+        if (wy0 % stride || wx0 % stride || ty0 % stride || tx0 % stride || (ty1 != gH && ty1 % stride) || (tx1 != gW && tx1 % stride))
+            return fail(ST_ERR_ARG, "style tile/window edges must be multiples of the total stride %d of blob %d (or the image's far edge)", stride, last_blob);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    size_t total = 0;
+    for (int b = 0; b <= last_blob; ++b) { const size_t C = c->blob_c_topo(b); total += C * C; }
+    if (total > 0x7fffffffu) return fail(ST_ERR_ARG, "the style partials exceed 2^31 floats");
+    c->tile.sp_last = -1;
+    ST_TRY(tile_ensure(&c->tile.sp, &c->tile.sp_cap, total));
+    HIP_TRY(hipMemsetAsync(c->tile.sp, 0, total * sizeof(float), c->stream));
+    int r = ST_OK;
+    if (hwc) {
+        float* tmp = nullptr;
+        ST_TRY(dmalloc(&tmp, (size_t)3 * H * W));
+        ActSet aux;
+        ActSet* a = &aux;
+        const bool same = c->act.H == H && c->act.W == W && !c->act.data.empty();
+        if (same) a = &c->act;
+        r = preprocess_into(c, hwc, H, W, is_u8, tmp);
+        if (r == ST_OK) r = act_ensure(c, *a, H, W);
+        if (r == ST_OK) r = forward_range(c, *a, tmp, last_blob);
+        TileGeom g;
+        g.gH = gH; g.gW = gW; g.wy0 = wy0; g.wx0 = wx0; g.ty0 = ty0; g.tx0 = tx0; g.ty1 = ty1; g.tx1 = tx1;
+        size_t pos = 0;
+        for (int b = 0; b <= last_blob && r == ST_OK; ++b) {
+            const int C = a->C[b];
+            const BlobRoi roi = tile_roi(c, *a, g, b);
+            const int rw = roi.x1 - roi.x0, rh = roi.y1 - roi.y0;
+            if (roi.y0 < 0 || roi.x0 < 0 || roi.y1 > a->h[b] || roi.x1 > a->w[b] || rw <= 0 || rh <= 0) {
+                r = fail(ST_ERR_ARG, "the style tile has no region in blob %d of its window", b);
+                break;
+            }
+            if (!a->plan.fwd[b].out32) { r = fail(ST_ERR_STATE, "internal: style blob %d has no fp32 copy", b); break; }
+            const int hw = rw * rh;
+            // the fp32 region-of-interest kernel on the fp32 blob under every precision and gram_algo, as st_set_style's targets under bf16
+            GramPlan pl;
+            r = ensure_gram_bufs(c, C, hw, pl);
+            if (r != ST_OK) break;
+            GramRoi gr{roi.y0, roi.x0, rw, a->w[b], (size_t)a->h[b] * a->w[b]};
+            hipError_t e;
+            { ProfScope ps(c, P_GRAM, 2.0 * C * C * (double)hw, 4.0 * C * (double)hw);
+              e = launch_gram_partial(a->data[b], c->gram_slabs, C, hw, pl, c->stream, &gr); }
+            if (e == hipSuccess) {
+                ProfScope ps(c, P_GRAM_REDUCE, 0, 4.0 * (double)pl.slab_floats);
+                e = launch_gram_reduce(c->gram_slabs, c->gram_fold, nullptr, c->tile.sp + pos, C, nullptr, nullptr, C, 1.0, pl, c->stream);
+            }
+            if (e != hipSuccess) { r = fail(ST_ERR_HIP, "style Gram partials of blob %d: %s", b, hipGetErrorString(e)); break; }
+            pos += (size_t)C * C;
+        }
+        (void)hipStreamSynchronize(c->stream);
+        if (!same) act_free(aux);
+        else c->act.valid_to = -1;
+        dfree(tmp);
+    } else {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    if (r != ST_OK) return r;
+    c->tile.sp_n = (int)total; c->tile.sp_last = last_blob; c->tile.sp_gH = gH; c->tile.sp_gW = gW;
+    if (dev_ptr) *dev_ptr = c->tile.sp;
+    if (n_floats) *n_floats = (int)total;
+    return ST_OK;
+}
+
+// after the all-reduce of the partials: style_gram[b] = sums / (C gh gw) for b <= last_blob (np.dot(x, x.T) / np.float32(x.size) with the
+// GLOBAL size, worker.py:114); the blobs above have no target from now on
+int st_tile_style_commit(st_ctx* c)
+{
+    if (c) c->epoch++;
+    if (!c) return fail(ST_ERR_ARG, "ctx is NULL");
+    if (c->tile.sp_last < 0 || !c->tile.sp) return fail(ST_ERR_STATE, "st_tile_style_partials first");
+    HIP_TRY(hipSetDevice(c->device));
+    int gh = c->tile.sp_gH, gw = c->tile.sp_gW;
+    size_t pos = 0;
+    GramPlan one{}; one.bt = 128; one.splits = 1;          // the reduced sums are ONE full C x C slab
+    for (int b = 0; b <= c->tile.sp_last; ++b) {
+        if (b > 0 && !c->topo[b - 1].is_conv) { gh = pooled_size(gh); gw = pooled_size(gw); }
+        const int C = c->blob_c_topo(b);
+        if (!c->style_gram[b]) ST_TRY(dmalloc(&c->style_gram[b], (size_t)C * C));
+        ProfScope ps(c, P_GRAM_REDUCE, 0, 8.0 * C * C);
+        HIP_TRY(launch_gram_reduce(c->tile.sp + pos, nullptr, nullptr, c->style_gram[b], C, nullptr, nullptr, C, (double)C * gh * gw, one, c->stream));
+        pos += (size_t)C * C;
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int b = 0; b < c->nb; ++b) c->style_valid[b] = b <= c->tile.sp_last;
+    c->have_style = true;
+    c->tile.sp_last = -1;
+    return ST_OK;
+}
+
+// test hook: the style target of a blob, C x C
+int st_get_style_gram(st_ctx* c, int blob, float* out)
+{
+    if (!c || blob < 0 || blob >= c->nb || !out) return fail(ST_ERR_ARG, "bad argument");
+    if (!c->have_style || !c->style_valid[blob] || !c->style_gram[blob])
+        return fail(ST_ERR_STATE, "blob %d (%s) has no style target", blob, c->blob_names[blob].c_str());
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t C = c->blob_c_topo(blob);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(out, c->style_gram[blob], C * C * sizeof(float), hipMemcpyDeviceToHost));
     return ST_OK;
 }
 

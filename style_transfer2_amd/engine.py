@@ -180,6 +180,49 @@ class Engine:
         arr, u8 = _image_arg(image)
         check(self.lib.st_set_style(self._ctx, _ptr(arr), arr.shape[0], arr.shape[1], u8))
 
+    # -- the style targets of a tile-sharded job, sharded as well (st_tile_set_style; tiling.style_grid has the geometry) ------
+    def _style_tile_args(self, window_image, grid_hw, window, tile, last):
+        """(image pointer or NULL, the 12 integers of the C ABI, the array kept alive).  window_image None: this rank has no style tile."""
+        last_i = self._index[last] if isinstance(last, str) else int(last)
+        if window_image is None:
+            return None, [0, 0, 0, int(grid_hw[0]), int(grid_hw[1]), 0, 0, 0, 0, 0, 0, last_i], None
+        arr, u8 = _image_arg(window_image)
+        geo = [arr.shape[0], arr.shape[1], u8, int(grid_hw[0]), int(grid_hw[1]), int(window[0]), int(window[1])] + [int(v) for v in tile]
+        return _ptr(arr), geo + [last_i], arr
+
+    def tile_set_style(self, window_image, grid_hw, window=(0, 0), tile=None, last=None):
+        """Collective over the communicator of this context (every rank calls it, after st_comm_init / st_comm_callbacks): the style
+        targets of blobs 0 .. `last` from the raw Gram sums of every rank's tile of the style image, all-reduced.  window_image is this
+        rank's window (tile + apron) of the grid_hw = (gH, gW) style image, window = (wy0, wx0) its origin, tile = (ty0, tx0, ty1, tx1)
+        in global pixels (default: the window is the whole image); None: this rank has no tile and contributes zeros."""
+        last = len(self.blob_names) - 1 if last is None else last
+        if tile is None and window_image is not None:
+            tile = (0, 0, int(grid_hw[0]), int(grid_hw[1]))
+        p, ints, keep = self._style_tile_args(window_image, grid_hw, window, tile, last)
+        check(self.lib.st_tile_set_style(self._ctx, p, *ints))
+
+    def tile_style_partials(self, window_image, grid_hw, window=(0, 0), tile=None, last=None):
+        """The first half of tile_set_style for a caller that all-reduces itself: (device pointer, number of floats) of this rank's
+        raw Gram sums, blobs 0 .. `last` back to back; tile_style_commit() after the all-reduce."""
+        last = len(self.blob_names) - 1 if last is None else last
+        if tile is None and window_image is not None:
+            tile = (0, 0, int(grid_hw[0]), int(grid_hw[1]))
+        p, ints, keep = self._style_tile_args(window_image, grid_hw, window, tile, last)
+        dev, n = c_void_p(), c_int()
+        check(self.lib.st_tile_style_partials(self._ctx, p, *ints, byref(dev), byref(n)))
+        return dev.value, n.value
+
+    def tile_style_commit(self):
+        check(self.lib.st_tile_style_commit(self._ctx))
+
+    def style_gram(self, name):
+        """Host copy of the style target (C x C) of a blob; an error if the context holds none for it."""
+        i = self._index[name]
+        c = self.blob_shape(name, 16, 16)[0]
+        out = np.empty((c, c), F32)
+        check(self.lib.st_get_style_gram(self._ctx, i, _ptr(out)))
+        return out
+
     def set_input_nchw(self, x):
         x = np.ascontiguousarray(x, F32)
         check(self.lib.st_set_input_nchw(self._ctx, _ptr(x), x.shape[2], x.shape[3]))

@@ -71,13 +71,15 @@ def run_job(transfer, content, style, iterations, size=None, style_size=None, op
 
 
 def run_tiled_job(net_params, content, style, iterations, grid, size=None, style_size=None, weights=None, params=None, init=None,
-                  seed=0, device=0, precision='fp32', topology=None, callback=None, optimizer='adam', step_size=None):
+                  seed=0, device=0, precision='fp32', topology=None, callback=None, optimizer='adam', step_size=None, shard_style=False):
     """The same job for an image no single engine holds (an 8192 x 8192 image has conv1 blobs of 17 GB each): the image is cut into
     grid = (rows, cols) tiles, every tile + apron is an engine context of THIS process on the one GPU (tiled.InProcessFabric: one
     thread per rank, the all-reduces and strip exchanges are device-to-device copies); one st_tile_step per rank and iteration, Adam or
     L-BFGS (the Gram form: one all-reduce of the new inner products per step).
     Same result as run_job where both can run (tests/test_gpu_jobs.py).  Image edges must be multiples of 16 * rows / cols
-    (tiling.TileGrid).  Returns the stitched HxWx3 float32 image; callback(i, trace values) after every iteration."""
+    (tiling.TileGrid).  shard_style: the style image is cut as well (tiling.style_grid over the same ranks, up to the deepest
+    style-weighted blob) and every rank forwards one window of it, instead of every rank forwarding all of it.
+    Returns the stitched HxWx3 float32 image; callback(i, trace values) after every iteration."""
     from . import tiled, tiling
     from .engine import VGG19_TOPOLOGY
     from .tile_backend import HipTileBackend
@@ -97,12 +99,16 @@ def run_tiled_job(net_params, content, style, iterations, grid, size=None, style
     fabric = tiled.InProcessFabric(world, timeout=600.0)
     ranks, backends = [], []
     for r in range(world):
-        b = HipTileBackend(net_params, tg, r, content, style, init, weights, params, step_size=step_size or {'adam': 10, 'lbfgs': 1}[optimizer],
+        b = HipTileBackend(net_params, tg, r, content, None if shard_style else style, init, weights, params, step_size=step_size or {'adam': 10, 'lbfgs': 1}[optimizer],
                            topology=topology, device=device, precision=precision, optimizer=optimizer)
         backends.append(b)
         b.comm_init_local(r, world, fabric)
         ranks.append(tiled.FusedTiledTransfer(tg, r, b))
     try:
+        if shard_style:
+            styled = [i for i, layer in enumerate(topology) if weights.get('style', {}).get(layer[1])]
+            sg = tiling.style_grid(style.shape[0], style.shape[1], world, topology, max(styled) + 1 if styled else 0)
+            tiled.run_collective([lambda b=b: b.shard_style(style, sg) for b in backends], fabric, in_turns=True)
         for i in range(iterations):
             vals = tiled.run_in_process(ranks, 1, fabric)[0][0]
             if callback is not None:

@@ -60,7 +60,8 @@ class HipTileBackend:
         crop = lambda im, r: np.ascontiguousarray(im[r.y0:r.y1, r.x0:r.x1])
         self.engine.set_input(crop(init, w))
         self.engine.set_content(crop(content, w))
-        self.engine.set_style(style)
+        if style is not None:            # None: the targets come from the sharded style pass (shard_style, after comm_init_*)
+            self.engine.set_style(style)
         rows, cells = weight_table(weights)
         cols = [[cells[k][r] for r in rows] for k in LOSS_NAMES]
         self.engine.set_weights(rows, cols[0], cols[1], cols[2], [params[k] for k in SCALAR_LOSS_NAMES])
@@ -180,6 +181,35 @@ class HipTileBackend:
         timed update runs on finite data."""
         self._callbacks = (capi.ALLREDUCE_FN(lambda user, ptr, n: 0), capi.EXCHANGE_FN(lambda *a: 0))
         check(self.lib.st_comm_callbacks(self.ctx, int(rank), int(world), self._callbacks[0], self._callbacks[1], None))
+
+    # ---- the style targets from the sharded style image (st_tile_set_style; tiling.style_grid) ---------------------------------
+    def _style_share(self, style, style_grid):
+        """(this rank's window of the style image or None, window origin, tile) for the C ABI."""
+        style = np.asarray(style)
+        if style.shape[:2] != (style_grid.gH, style_grid.gW):
+            raise ValueError('the style grid is cut for %d x %d, the image is %d x %d' % ((style_grid.gH, style_grid.gW) + style.shape[:2]))
+        if self.rank >= style_grid.world:
+            return None, (0, 0), None
+        w, t = style_grid.windows[self.rank], style_grid.tiles[self.rank]
+        return np.ascontiguousarray(style[w.y0:w.y1, w.x0:w.x1]), (w.y0, w.x0), (t.y0, t.x0, t.y1, t.x1)
+
+    def shard_style(self, style, style_grid):
+        """Collective (every rank calls it, after comm_init_*): the style targets of blobs 0 .. style_grid.last_blob from the ranks'
+        tiles of the style image; a rank beyond the style grid contributes nothing but takes part in the all-reduce."""
+        image, origin, tile = self._style_share(style, style_grid)
+        self.engine.tile_set_style(image, (style_grid.gH, style_grid.gW), origin, tile, style_grid.last_blob)
+
+    def style_partials(self, style, style_grid):
+        """The same in two halves for the phase-by-phase driver (tiled.TiledTransfer.shard_style): this rank's raw Gram sums as a 1-D
+        device tensor, to be all-reduced; then style_commit()."""
+        image, origin, tile = self._style_share(style, style_grid)
+        torch.cuda.synchronize(self.device)
+        ptr, n = self.engine.tile_style_partials(image, (style_grid.gH, style_grid.gW), origin, tile, style_grid.last_blob)
+        return dev_tensor(ptr, (n,), self.device)
+
+    def style_commit(self):
+        torch.cuda.synchronize(self.device)
+        self.engine.tile_style_commit()
 
     def set_plan(self, phase, peers):
         """peers: {peer rank: (send rects, recv rects)}, rects = [(y0, x0, h, w), ...] (tiled.fused_plans)."""

@@ -178,6 +178,14 @@ class TiledTransfer:
         self._exchange(x, sends, ring, recvs, add=False)
         return ring
 
+    # -- the style targets from the sharded style image ---------------------------------------------------------
+    def shard_style(self, style, style_grid):
+        """Every rank forwards its window of the style image (style_grid: tiling.style_grid; ranks beyond it hold no tile) and sums
+        F F^T over its tile's region of blobs 0 .. style_grid.last_blob; ONE all-reduce of the raw sums; every rank then divides by the
+        global element counts (worker.py:114).  Replaces the whole-image style pass each backend would otherwise repeat."""
+        self.comm.all_reduce(self.backend.style_partials(style, style_grid))
+        self.backend.style_commit()
+
     # -- L-BFGS over the sharded image ----------------------------------------------------------------------
     def _evaluate(self):
         """opfunc at the current image: the trace values; the backend's grad_tile() then holds this rank's part of the gradient."""
@@ -345,6 +353,8 @@ class InProcessFabric:
         self.pending = [0] * world                 # messages of rank r not yet consumed (device mode)
         self.reduces = self.messages = 0
         self.aborted = False                       # a rank failed: every wait of the others ends at once (abort())
+        self.turn = threading.Lock()               # take_turn(): one rank at a time works towards its next all-reduce
+        self.turn_of = None
 
     def abort(self):
         """A rank raised: wake every rank that waits for it (barrier and mailboxes) instead of letting them run into the timeout."""
@@ -357,8 +367,21 @@ class InProcessFabric:
         if self.aborted:
             raise RuntimeError('rank %d: another rank failed, the exchange was abandoned' % rank)
 
+    def take_turn(self, rank):
+        """Blocks until no other rank holds the turn; the holder gives it up when it arrives at its next all-reduce (or through
+        end_turn).  On one GPU the ranks' kernels run one after another anyway: taking turns keeps the transient buffers of a set-up
+        pass (the style pass: one activation set per rank) from being alive on all ranks at once."""
+        self.turn.acquire()
+        self.turn_of = rank
+
+    def end_turn(self, rank):
+        if self.turn_of == rank:
+            self.turn_of = None
+            self.turn.release()
+
     def allreduce(self, rank, values):
         """values: numpy array or torch tensor, summed over the ranks in place."""
+        self.end_turn(rank)
         is_numpy = isinstance(values, np.ndarray)
         self.slots[rank] = values.copy() if is_numpy else values.clone()
         self.barrier.wait(self.timeout)
@@ -460,6 +483,45 @@ def run_in_process(ranks, steps, fabric, on_step=None):
             t.join(30.0)
         alive = [r for r, t in enumerate(threads) if t.is_alive()]
     if errors or alive or any(o is None for o in out):
+        err = RuntimeError('in-process ranks failed: %s' % (errors or ('rank(s) %s did not finish' % alive)))
+        err.still_running = bool(alive)
+        raise err
+    return out
+
+
+def run_collective(calls, fabric, in_turns=False):
+    """One collective call per rank (calls[r]: a callable that ends in the fabric, e.g. HipTileBackend.shard_style), one thread each, as
+    run_in_process runs the iterations: a rank that raises aborts the fabric; ``still_running`` on the RuntimeError means a rank thread
+    is still inside the engine and the caller must NOT free the engine contexts.  in_turns: a rank starts when the one before it has
+    reached its all-reduce (InProcessFabric.take_turn).  Returns what the calls returned."""
+    import threading
+    world = len(calls)
+    out, done, errors = [None] * world, [False] * world, []
+
+    def run(r):
+        try:
+            if in_turns:
+                fabric.take_turn(r)
+            out[r] = calls[r]()
+            done[r] = True
+        except Exception as e:          # noqa: BLE001
+            errors.append((r, repr(e)))
+            fabric.abort()
+        finally:
+            if in_turns:
+                fabric.end_turn(r)
+    threads = [threading.Thread(target=run, args=(r,), daemon=True) for r in range(world)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(max(300.0, 4 * fabric.timeout))
+    alive = [r for r, t in enumerate(threads) if t.is_alive()]
+    if alive:
+        fabric.abort()
+        for t in threads:
+            t.join(30.0)
+        alive = [r for r, t in enumerate(threads) if t.is_alive()]
+    if errors or alive or not all(done):
         err = RuntimeError('in-process ranks failed: %s' % (errors or ('rank(s) %s did not finish' % alive)))
         err.still_running = bool(alive)
         raise err

@@ -74,6 +74,7 @@ class TileGrid:
             raise ValueError('tile-sharded mode does not run average pools (%s)' %
                              ', '.join(layer[1] for layer in topology if layer[0] == 'pool' and len(layer) > 2))
         self.gH, self.gW, self.rows, self.cols = gH, gW, rows, cols
+        self.last_blob = last_blob
         self.stride = total_stride(topology, last_blob)
         self.apron = receptive_apron(topology, last_blob) if apron is None else apron
         if self.apron % self.stride:
@@ -149,6 +150,35 @@ class TileGrid:
         y1 = blob_hw[0] if t.y1 == self.gH else (t.y1 - w.y0) // s
         x1 = blob_hw[1] if t.x1 == self.gW else (t.x1 - w.x0) // s
         return Rect(y0, x0, y1, x1)
+
+
+def style_grid(sH, sW, world, topology, last_blob):
+    """The TileGrid of the STYLE image of a tile-sharded job (the style pass of tiled.py: every rank forwards one window of the
+    style image and the raw Gram sums of the tiles' regions are all-reduced).  `last_blob` is the deepest blob whose Gram is wanted:
+    tile edges, and with them the window origins, are multiples of its total stride; the apron is receptive_apron(topology, last_blob).
+
+    Of the R' x C' cuts with R' * C' <= world that split_edges accepts, the one whose LARGEST window is smallest (the pass's transient
+    memory on a rank, and its critical path across devices); among those the smallest summed window area (the work all ranks do
+    together: cutting further only adds apron), then the fewest tiles.  Ranks >= R' * C' have no style tile (grid.world <= world).
+    An image too small for any cut gives the 1 x 1 grid, whose window is the image."""
+    if world < 1:
+        raise ValueError('world must be >= 1')
+    best = None
+    for rows in range(1, world + 1):
+        for cols in range(1, world // rows + 1):
+            try:
+                g = TileGrid(sH, sW, rows, cols, topology, last_blob)
+            except ValueError as err:
+                if rows == cols == 1:
+                    raise                              # (an average pool: no cut helps)
+                if 'cannot be cut' not in str(err):
+                    raise
+                continue
+            areas = [(w.y1 - w.y0) * (w.x1 - w.x0) for w in g.windows]
+            key = (max(areas), sum(areas), rows * cols, rows)
+            if best is None or key < best[0]:
+                best = (key, g)
+    return best[1]
 
 
 def _wrap_1d(start, length, n):

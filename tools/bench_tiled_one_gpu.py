@@ -25,6 +25,7 @@ ap.add_argument('--precision', default='fp32', choices=('fp32', 'bf16'))
 ap.add_argument('--transport', default='device', choices=('device', 'host'))
 ap.add_argument('--optimizer', default='adam', choices=('adam', 'lbfgs'), help='lbfgs: the fused Gram-form step (one all-reduce of the new inner products per step)')
 ap.add_argument('--driver', default='engine', choices=('engine', 'phases'), help='phases: tiled.TiledTransfer between the st_tile_* phases (chain-form L-BFGS with scalar all-reduces)')
+ap.add_argument('--shard-style', action='store_true', help='the style image is cut over the ranks as well (tiling.style_grid; st_tile_set_style) instead of every rank forwarding all of it')
 ap.add_argument('--need-free-gib', type=float, default=0.0, help='print {"skipped": ...} and exit 0 unless this much HBM is free')
 args = ap.parse_args()
 sys.stdout.flush()
@@ -56,8 +57,32 @@ net = st2_weights.he_normal(topo, seed=0)
 free0, total = torch.cuda.mem_get_info()
 fabric = tiled.InProcessFabric(world, timeout=600.0)
 ranks, backends = [], []
+
+
+class FreeSampler:
+    """Lowest free HBM (hipMemGetInfo) seen while the set-up runs, sampled every few milliseconds from a thread of its own: the
+    set-up's transient (the style pass's blobs) is freed again before it returns."""
+    def __init__(self):
+        import threading
+        self.low, self.stop = torch.cuda.mem_get_info()[0], False
+        self.thread = threading.Thread(target=self.run, daemon=True)
+        self.thread.start()
+
+    def run(self):
+        while not self.stop:
+            self.low = min(self.low, torch.cuda.mem_get_info()[0])
+            time.sleep(0.005)
+
+    def close(self):
+        self.stop = True
+        self.thread.join()
+        return self.low
+
+
+sampler = FreeSampler()
+t_setup = time.perf_counter()
 for r in range(world):
-    b = HipTileBackend(net, grid, r, content, style, init, WEIGHTS, PARAMS, step_size={'adam': 10, 'lbfgs': 1}[args.optimizer],
+    b = HipTileBackend(net, grid, r, content, None if args.shard_style else style, init, WEIGHTS, PARAMS, step_size={'adam': 10, 'lbfgs': 1}[args.optimizer],
                        precision=args.precision, optimizer=args.optimizer)
     backends.append(b)
     if args.driver == 'phases':                  # the phase-by-phase driver (torch tensors between the st_tile_* phases): the A/B reference
@@ -68,6 +93,16 @@ for r in range(world):
     else:
         b.comm_init_host(r, world, lambda v, r=r: fabric.allreduce(r, v), lambda s, rc, r=r: fabric.exchange(r, s, rc))
     ranks.append(tiled.FusedTiledTransfer(grid, r, b))
+style_grid = None
+if args.shard_style:
+    style_grid = tiling.style_grid(args.style_size, args.style_size, world, topo, 17)
+    calls = [lambda t=t: t.shard_style(style, style_grid) for t in (ranks if args.driver == 'phases' else backends)]
+    tiled.run_collective(calls, fabric, in_turns=True)
+for b in backends:
+    b.engine.sync()
+setup_s = time.perf_counter() - t_setup
+free_low = sampler.close()
+free1 = torch.cuda.mem_get_info()[0]
 tiled.run_in_process(ranks, args.warmup, fabric)
 for b in backends:
     b.engine.sync()
@@ -85,6 +120,11 @@ json_out.write(json.dumps({
         gH, gW, args.grid, sorted({(w.y1 - w.y0, w.x1 - w.x0) for w in grid.windows}), args.optimizer, args.precision),
                'transport': 'in-process, %s' % ('device-to-device copies' if args.transport == 'device' else 'staged through host arrays'),
                'driver': 'st_tile_step (fused)' if args.driver == 'engine' else 'phase by phase (tiled.TiledTransfer)'},
+    'style': {'size': args.style_size, 'sharded': bool(args.shard_style),
+              'grid': '%dx%d' % (style_grid.rows, style_grid.cols) if style_grid else None,
+              'windows': sorted({(w.y1 - w.y0, w.x1 - w.x0) for w in style_grid.windows}) if style_grid else None},
+    'setup_s': setup_s, 'free_before_setup_GiB': free0 / 2 ** 30, 'free_after_setup_GiB': free1 / 2 ** 30,
+    'lowest_free_during_setup_GiB': free_low / 2 ** 30, 'setup_transient_GiB': (free1 - free_low) / 2 ** 30,
     'hbm_in_use_GiB': used, 'loss': float(out[0][-1][-2]), 'all_reduces_per_step': fabric.reduces / max(1, args.steps + args.warmup),
     'messages_per_step': fabric.messages / max(1, args.steps + args.warmup),
     'dtype': 'f32' if args.precision == 'fp32' else 'bf16 conv operands, f32 accumulate/Gram/optimizer', 'data': 'synthetic'}) + '\n')

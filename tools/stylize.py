@@ -24,6 +24,7 @@ ap.add_argument('--gpu', type=int, default=0)
 ap.add_argument('--conv-algo', type=int, default=None, choices=[0, 1, 2], help='st_set_conv_algo (default: the engine\'s, 1)')
 ap.add_argument('--gram-algo', type=int, default=None, choices=[0, 1], help='st_set_gram_algo (default: the engine\'s, 0)')
 ap.add_argument('--grid', default='', help='RxC: tile-shard the image over this one GPU (large images)')
+ap.add_argument('--shard-style', action='store_true', help='with --grid: cut the style image over the ranks as well (every rank forwards one window of it)')
 args = ap.parse_args()
 
 if args.weights.endswith('.npz'):
@@ -36,7 +37,7 @@ else:
 if args.grid:
     rows, cols = (int(v) for v in args.grid.split('x'))
     image = jobs.run_tiled_job(params, jobs.load_rgb(args.content), jobs.load_rgb(args.style), args.iters, (rows, cols), size=args.size,
-                               style_size=args.style_size or None, device=args.gpu, optimizer=args.optimizer)
+                               style_size=args.style_size or None, device=args.gpu, optimizer=args.optimizer, shard_style=args.shard_style)
 else:
     job = st2.StyleTransfer(st2.HipModel(params, device=args.gpu, conv_algo=args.conv_algo, gram_algo=args.gram_algo))
     image = jobs.run_job(job, jobs.load_rgb(args.content), jobs.load_rgb(args.style), args.iters, size=args.size,
