@@ -68,6 +68,20 @@ int st_set_conv_algo(st_ctx* ctx, int winograd);
 int st_set_gram_algo(st_ctx* ctx, int algo);
 /* the algorithms in force: *conv = 0 | 1 | 2 (st_set_conv_algo), *gram = 0 | 1 (st_set_gram_algo); either pointer may be NULL */
 int st_get_algos(st_ctx* ctx, int* conv, int* gram);
+/* Average pools (ST_LAYER_AVEPOOL).  0 (default): every average pool is a stand-alone pass over the fp32 conv blob below it, forward
+ * and backward.  1 (opt-in): an average pool rides on the conv launches around it wherever a fused build exists -- the lean bf16 flow
+ * of st_set_precision(ctx, 1): the epilogue of the bf16 conv below writes the pooled bf16 copy (and the fp32 pooled blob where
+ * something reads it) plus one byte per window with the ReLU signs of its four elements, and does not write the fp32 conv blob; the
+ * backward expands the pooled bf16 diff through that byte inside the data gradient of the same conv (at most 128 output channels,
+ * even height and width) or in a pass of its own.  Same additions in the same order and power-of-two factors: loss, gradient, trace
+ * and iterates are those of 0 bit for bit unless an element of a diff is smaller than 2^-124.  A pool whose conv blob carries a weight,
+ * fp32 features, st_set_precision(ctx, 2) and every evaluation that writes all blobs (st_forward, st_set_content, st_set_style) route exactly as
+ * under 0; tile-sharded mode refuses average pools either way.  After a lean evaluation under 1 the conv blob below a fused pool is not
+ * materialised in fp32 (st_get_blob / st_gram say so), as below a fused max pool.  Anything else is ST_ERR_ARG.  The call leaves the
+ * activations as they are: a backward that follows reads the map the last forward wrote, whatever the option says by then. */
+int st_set_pool_algo(st_ctx* ctx, int algo);
+/* the value in force: *algo = 0 | 1 */
+int st_get_pool_algo(st_ctx* ctx, int* algo);
 /* 0 (default): fp32 throughout.  1: bf16 feature path (BASELINE config 3) -- conv operands (activations, weights,
  * backward diffs) in bf16 on v_mfma_f32_32x32x16_bf16, fp32 accumulate; Gram, losses, optimizer stay fp32.  Objective
  * evaluations then write an fp32 blob / diff only where something reads fp32 (weighted layers, pools without a fused

@@ -47,6 +47,8 @@ PROTOTYPES = {
     'st_set_conv_algo': (c_int, [c_void_p, c_int]),
     'st_set_gram_algo': (c_int, [c_void_p, c_int]),
     'st_get_algos': (c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
+    'st_set_pool_algo': (c_int, [c_void_p, c_int]),
+    'st_get_pool_algo': (c_int, [c_void_p, POINTER(c_int)]),
     'st_set_precision': (c_int, [c_void_p, c_int]),
     'st_num_blobs': (c_int, [c_void_p]),
     'st_blob_name': (c_char_p, [c_void_p, c_int]),

@@ -9,6 +9,9 @@
 // of the backward pass is read from the bf16 copy (mask16: 2 bytes instead of 4), and the forward epilogue can pool its
 // own output (Caffe MAX 2x2/2, ceil mode, first-max) into the bf16 copy the next conv reads plus a one-byte-per-element
 // arg-max map (bits 0-1 = window slot, bit 2 = the maximum is positive) that replaces the blob in the pool backward.
+// An AVERAGE pool (Caffe AVE 2x2/2, st_set_pool_algo(ctx, 1)) rides on the same launches: the epilogue averages instead, the map's byte
+// holds the four ReLU signs of the window (bit e = element e, row-major, is inside the blob and > 0), and the backward hands every
+// element dy / window size where its bit is set -- in the UNPOOL builds' staged tile or in avepool_bwd_map16_k.
 // Round 4: forward and data-gradient epilogues are separate builds (conv16_body<..., DG, MB>); forward launches also write a 1-bit
 // sign map of their post-ReLU output (bits_out) that the data gradient above masks with (mask_bits); the data gradient below a
 // pool can take the POOLED diff and expand it in its staged tile (UNPOOL); K <= 64 launches use one staging buffer (SB).
@@ -83,6 +86,7 @@ struct Conv16KArgs {
     const unsigned short* in16; const unsigned short* wpack; const float* bias; float* out; unsigned short* out16;
     const float* mask_src; const float* inject; const unsigned short* mask16;
     unsigned short* pool16; float* pool32; unsigned char* amap; int pool_h, pool_w;
+    int pool_ave;                        // the fused pool is Caffe AVE: amap takes the window's sign bits (Conv16Problem::pool_ave)
     int K, M, MPad, H, W, nch, tiles_x, tiles_y, n_mtiles, relu;
     unsigned in_bytes, w_bytes;
     // fused style term (data-gradient launches): out = mask(conv) + D' @ F, F = the bf16 copy of the blob this launch differentiates
@@ -129,7 +133,10 @@ __device__ __forceinline__ unsigned nonzero_halves16(uint2 u0, uint2 u1)
 // MB (data-gradient builds): the ReLU mask comes as a sign map (mask_bits) -- the other two forms have their own build, for the same reason
 // EPI (round 5): 0 = the epilogue with every option of its direction behind run-time flags; 1 .. 3 = the epilogue of ONE launch kind of
 // the lean flow (see "one epilogue per launch kind" below) -- at K = 64 the general epilogue ran as long as the main loop
-template <int BM, int ROWS, int WAVES_M, int WAVES_N, bool SB = false, bool UNPOOL = false, bool DG = UNPOOL, bool MB = false, bool DIAG = false, int EPI = 0>
+// AVE (UNPOOL builds): the pool above is an average pool and up_amap its sign map: a staged value becomes dy * 0.25 where the bit of its
+// window position is set, else 0 (whole windows only -- can_unpool asks for even H and W -- so the divisor is always 4)
+template <int BM, int ROWS, int WAVES_M, int WAVES_N, bool SB = false, bool UNPOOL = false, bool DG = UNPOOL, bool MB = false, bool DIAG = false, int EPI = 0,
+          bool AVE = false>
 __device__ __forceinline__ void conv16_body(const Conv16KArgs& a)
 {
     // BR (round 5): the four-rows-per-wave tile walks a chunk column by column of the 3x3 stencil and keeps the activation fragments of its
@@ -146,6 +153,7 @@ __device__ __forceinline__ void conv16_body(const Conv16KArgs& a)
     static_assert(DG || !MB, "sign-map masks are a data-gradient option");
     static_assert(!(SB && UNPOOL), "the unpooling build uses the double-buffered pipeline");
     static_assert(DG || !UNPOOL, "unpooling is a data-gradient option");
+    static_assert(UNPOOL || !AVE, "the average-pool expansion is an option of the unpooling builds");
     constexpr int TM = BM / WAVES_M / 32;
     constexpr int TN = ROWS / WAVES_N;
     static_assert(WAVES_M * WAVES_N == 4 && TM >= 1 && TN >= 1, "tile");
@@ -260,6 +268,21 @@ __device__ __forceinline__ void conv16_body(const Conv16KArgs& a)
             if ((I_INSTR % 4 == 0 || j < I_INSTR) && ioff[u] != kOOB16) {          // (quads outside the image are zero already)
                 const unsigned here = ((up_here >> (3 * u)) & 7u) * 0x01010101u;
                 const uint4 d = img[j * 64 + lane];
+                if constexpr (AVE) {
+                    // bit `pos` of a channel's byte: this window position was positive.  dy is bf16 and the factor a power of two: the
+                    // product, formed in fp32 and truncated back, is exact (for every normal result)
+                    const unsigned pos = (up_here >> (3 * u)) & 3u;
+                    auto quarter = [&](unsigned word, unsigned b0, unsigned b1) {      // two bf16 values; b0 / b1: their sign bytes
+                        const float lo = __builtin_bit_cast(float, word << 16) * 0.25f, hi = __builtin_bit_cast(float, word & 0xffff0000u) * 0.25f;
+                        const unsigned k = (0u - ((b0 >> pos) & 1u)) >> 16 | (0u - ((b1 >> pos) & 1u)) << 16;
+                        return ((__builtin_bit_cast(unsigned, lo) >> 16) | (__builtin_bit_cast(unsigned, hi) & 0xffff0000u)) & k;
+                    };
+                    uint4 o;
+                    o.x = quarter(d.x, mm[u].x, mm[u].x >> 8); o.y = quarter(d.y, mm[u].x >> 16, mm[u].x >> 24);
+                    o.z = quarter(d.z, mm[u].y, mm[u].y >> 8); o.w = quarter(d.w, mm[u].y >> 16, mm[u].y >> 24);
+                    img[j * 64 + lane] = o;
+                    return;
+                }
                 auto keep = [&](unsigned bytes) {                // 0xff per byte whose low three bits equal `here`
                     const unsigned t = (bytes ^ here) & 0x07070707u;
                     return ((((t + 0x07070707u) >> 3) & 0x01010101u) ^ 0x01010101u) * 0xffu;
@@ -743,6 +766,23 @@ __device__ __forceinline__ void conv16_body(const Conv16KArgs& a)
                             const size_t ppix = writer ? (size_t)(gy0 >> 1) * a.pool_w + (gx >> 1) : 0;
                             float best[8];
                             unsigned code[8];
+                            if (a.pool_ave) {
+                                // Caffe AVE: the in-image elements added in row-major order onto 0, times 1 / (clipped window size) --
+                                // avepool_fwd_k's operations in its order; the byte: which of them are positive (avepool_bwd_k's mask test)
+                                const float scale = (row1 && col1) ? 0.25f : (row1 || col1) ? 0.5f : 1.0f;
+#pragma unroll
+                                for (int e = 0; e < 8; ++e) {
+                                    const float p0 = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v[jp][e]), 0xB1, 0xf, 0xf, true));
+                                    const float p1 = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v[jp + 1][e]), 0xB1, 0xf, 0xf, true));
+                                    float t = 0.0f + v[jp][e];
+                                    unsigned sg = v[jp][e] > 0.0f ? 1u : 0u;
+                                    if (col1) { t += p0; sg |= p0 > 0.0f ? 2u : 0u; }
+                                    if (row1) { t += v[jp + 1][e]; sg |= v[jp + 1][e] > 0.0f ? 4u : 0u; }
+                                    if (row1 && col1) { t += p1; sg |= p1 > 0.0f ? 8u : 0u; }
+                                    best[e] = t * scale;
+                                    code[e] = sg;
+                                }
+                            } else {
 #pragma unroll
                             for (int e = 0; e < 8; ++e) {
                                 const float p0 = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v[jp][e]), 0xB1, 0xf, 0xf, true));
@@ -754,6 +794,7 @@ __device__ __forceinline__ void conv16_body(const Conv16KArgs& a)
                                 if (row1 && col1 && p1 > bb) { bb = p1; sl = 3; }
                                 best[e] = bb;
                                 code[e] = sl | (bb > 0.0f ? 4u : 0u);
+                            }
                             }
                             if (writer) {
 #pragma unroll
@@ -796,6 +837,7 @@ __device__ __forceinline__ void conv16_body(const Conv16KArgs& a)
         //   EPI 1  forward build:        (bias, ReLU) -> bf16 copy (+ sign map)         -- also the data gradients with no option at all
         //   EPI 2  forward build:        (bias, ReLU) -> 2x2 max-pool -> pooled bf16 copy + arg-max map (whole windows: H, W even)
         //   EPI 3  data-gradient build:  sign-map ReLU mask (here, or before the fused style chunks) -> bf16 copy
+        //   EPI 6  forward build:        as 2 with the AVERAGE of the window (x 0.25) and its four ReLU signs in the map's byte
         // and two more once per step, at the blob that carries a content / deep-dream term:
         //   EPI 4  = 1 + the fp32 blob (the loss reads fp32)        EPI 5  = 3 + the injected fp32 diff of that term, added after the mask
         // every tile whole in M (M % BM == 0, checked at launch).  Same arithmetic on every value as the general epilogue below (the
@@ -805,7 +847,7 @@ __device__ __forceinline__ void conv16_body(const Conv16KArgs& a)
         // (16 channels x 32 pixels) instead of ~300.  ReLU is an integer maximum of the bit pattern with 0 (off: with INT_MIN): v > 0 ? v : +0
         // for every v that is not a NaN.
         constexpr bool E_F = EPI == 1 || EPI == 4, E_D = EPI == 3 || EPI == 5;
-        static_assert(!DIAG && E_D == (DG && MB) && (EPI != 2 || TN % 2 == 0), "launch kinds");
+        static_assert(!DIAG && E_D == (DG && MB) && ((EPI != 2 && EPI != 6) || TN % 2 == 0), "launch kinds");
         typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
         typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
         const unsigned mrow0 = (unsigned)(m0 + wave_m * (TM * 32));
@@ -947,6 +989,11 @@ __device__ __forceinline__ void conv16_body(const Conv16KArgs& a)
                         for (int e = 0; e < 8; ++e) {
                             const float p0 = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v[jp][e]), 0xB1, 0xf, 0xf, true));
                             const float p1 = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v[jp + 1][e]), 0xB1, 0xf, 0xf, true));
+                            if constexpr (EPI == 6) {       // Caffe AVE on a whole window: avepool_fwd_k's sum in its order, x 0.25; the four signs
+                                best[e] = ((((0.0f + v[jp][e]) + p0) + v[jp + 1][e]) + p1) * 0.25f;
+                                code[e] = (v[jp][e] > 0.0f ? 1u : 0u) | (p0 > 0.0f ? 2u : 0u) | (v[jp + 1][e] > 0.0f ? 4u : 0u) | (p1 > 0.0f ? 8u : 0u);
+                                continue;
+                            }
                             float bb = v[jp][e];
                             unsigned sl = 0;
                             if (p0 > bb) { bb = p0; sl = 1; }
@@ -1014,6 +1061,14 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_mfma_bf16_64x512_f16o(const Con
 __global__ __launch_bounds__(NT, 2) void conv3x3_mfma_bf16_64x512_dgb16i(const Conv16KArgs a) { conv16_body<64, 16, 1, 4, false, false, true, true, false, 5>(a); }
 __global__ __launch_bounds__(NT, 2) void conv3x3_mfma_bf16_64x256_f16(const Conv16KArgs a) { conv16_body<64, 8, 1, 4, false, false, false, false, false, 1>(a); }
 __global__ __launch_bounds__(NT, 2) void conv3x3_mfma_bf16_64x256_dgb16(const Conv16KArgs a) { conv16_body<64, 8, 1, 4, false, false, true, true, false, 3>(a); }
+// the average pool on the same launches (st_set_pool_algo(ctx, 1)): forward kind 6, and the unpooling builds that read its sign map
+__global__ __launch_bounds__(NT, SB_WPE) void conv3x3_mfma_bf16_64x256_sb_avepool(const Conv16KArgs a) { conv16_body<64, 8, 1, 4, true, false, false, false, false, 6>(a); }
+__global__ __launch_bounds__(NT, 2) void conv3x3_mfma_bf16_64x512_avepool(const Conv16KArgs a) { conv16_body<64, 16, 1, 4, false, false, false, false, false, 6>(a); }
+__global__ __launch_bounds__(NT, 2) void conv3x3_mfma_bf16_64x512_unpool_ave(const Conv16KArgs a) { conv16_body<64, 16, 1, 4, false, true, true, false, false, 0, true>(a); }
+__global__ __launch_bounds__(NT, 2) void conv3x3_mfma_bf16_64x256_unpool_ave(const Conv16KArgs a) { conv16_body<64, 8, 1, 4, false, true, true, false, false, 0, true>(a); }
+__global__ __launch_bounds__(NT, 2) void conv3x3_mfma_bf16_64x512_unpool_ave_b(const Conv16KArgs a) { conv16_body<64, 16, 1, 4, false, true, true, true, false, 0, true>(a); }
+__global__ __launch_bounds__(NT, 2) void conv3x3_mfma_bf16_64x256_unpool_ave_b(const Conv16KArgs a) { conv16_body<64, 8, 1, 4, false, true, true, true, false, 0, true>(a); }
+__global__ __launch_bounds__(NT, 2) void conv3x3_mfma_bf16_64x512_unpool_ave_b16(const Conv16KArgs a) { conv16_body<64, 16, 1, 4, false, true, true, true, false, 3, true>(a); }
 
 Conv16Launch conv16_resolve(const Conv16Problem& p)
 {
@@ -1047,7 +1102,7 @@ Conv16Launch conv16_resolve(const Conv16Problem& p)
 
 namespace {
 enum Conv16Form { C16_FWD, C16_DG, C16_DGB, C16_DIAG };      // plain epilogue; data gradient; ... masked by a sign map; stamped forward (tools/probes)
-struct Conv16Build { void (*kernel)(const Conv16KArgs); int cfg; bool sb; Conv16Form form; bool unpool; int epi; };   // epi 0: the general epilogue (any kind), 1..5: that kind's (conv16_body, EPI)
+struct Conv16Build { void (*kernel)(const Conv16KArgs); int cfg; bool sb; Conv16Form form; bool unpool; int epi; bool ave; };   // epi 0: the general epilogue (any kind), 1..6: that kind's (conv16_body, EPI); ave: an unpooling build that reads an average pool's sign map
 // every build, the specialised epilogues first: the first row whose facts are the launch's runs, and a launch without a row has no build
 #define ST2_CONV16_ROWS3(NAME, CFG, SB) {NAME, CFG, SB, C16_FWD, false, 0}, {NAME##_dg, CFG, SB, C16_DG, false, 0}, {NAME##_dgb, CFG, SB, C16_DGB, false, 0}
 const Conv16Build kConv16Builds[] = {
@@ -1060,6 +1115,9 @@ const Conv16Build kConv16Builds[] = {
     {conv3x3_mfma_bf16_64x512_pool,       3, false, C16_FWD,  false, 2},
     {conv3x3_mfma_bf16_64x512_dgb16,      3, false, C16_DGB,  false, 3},
     {conv3x3_mfma_bf16_64x512_unpool_b16, 3, false, C16_DGB,  true,  3},
+    {conv3x3_mfma_bf16_64x256_sb_avepool, 0, true,  C16_FWD,  false, 6},
+    {conv3x3_mfma_bf16_64x512_avepool,    3, false, C16_FWD,  false, 6},
+    {conv3x3_mfma_bf16_64x512_unpool_ave_b16, 3, false, C16_DGB, true, 3, true},
     {conv3x3_mfma_bf16_64x256_f16,        0, false, C16_FWD,  false, 1},
     {conv3x3_mfma_bf16_64x256_dgb16,      0, false, C16_DGB,  false, 3},
     ST2_CONV16_ROWS3(conv3x3_mfma_bf16_64x256_sb, 0, true ),
@@ -1067,10 +1125,14 @@ const Conv16Build kConv16Builds[] = {
     ST2_CONV16_ROWS3(conv3x3_mfma_bf16_64x512, 3, false),
     {conv3x3_mfma_bf16_64x512_unpool,     3, false, C16_DG,   true,  0},
     {conv3x3_mfma_bf16_64x512_unpool_b,   3, false, C16_DGB,  true,  0},
+    {conv3x3_mfma_bf16_64x512_unpool_ave, 3, false, C16_DG,   true,  0, true},
+    {conv3x3_mfma_bf16_64x512_unpool_ave_b, 3, false, C16_DGB, true, 0, true},
     {conv3x3_mfma_bf16_64x512_diag,       3, false, C16_DIAG, false, 0},
     ST2_CONV16_ROWS3(conv3x3_mfma_bf16_64x256, 0, false),
     {conv3x3_mfma_bf16_64x256_unpool,     0, false, C16_DG,   true,  0},
     {conv3x3_mfma_bf16_64x256_unpool_b,   0, false, C16_DGB,  true,  0},
+    {conv3x3_mfma_bf16_64x256_unpool_ave, 0, false, C16_DG,   true,  0, true},
+    {conv3x3_mfma_bf16_64x256_unpool_ave_b, 0, false, C16_DGB, true, 0, true},
     ST2_CONV16_ROWS3(conv3x3_mfma_bf16_128x128, 1, false),
     ST2_CONV16_ROWS3(conv3x3_mfma_bf16_64x128, 2, false),
 };
@@ -1084,11 +1146,13 @@ hipError_t launch_conv3x3_bf16(const Conv16Problem& p, hipStream_t s)
     const Conv16Launch c = conv16_resolve(p);
     const bool pools = p.pool16 || p.pool32 || p.amap;
     if (pools && !c.can_pool) return hipErrorInvalidValue;
+    if ((p.pool_ave && !pools) || (p.unpool_ave && !p.unpool_amap)) return hipErrorInvalidValue;
     if (!p.out && !p.out16 && !pools) return hipErrorInvalidValue;          // nothing to write
     Conv16KArgs k{};
     k.in16 = p.in16; k.wpack = p.wpack16; k.bias = p.bias; k.out = p.out; k.out16 = p.out16;
     k.mask_src = p.mask_src; k.inject = p.inject; k.mask16 = p.mask16;
     k.pool16 = p.pool16; k.pool32 = p.pool32; k.amap = p.amap; k.pool_h = (p.H + 1) / 2; k.pool_w = (p.W + 1) / 2;
+    k.pool_ave = p.pool_ave;
     k.K = p.K; k.M = p.M; k.MPad = p.MPad; k.H = p.H; k.W = p.W;
     k.nch = (p.K + 15) / 16;
     k.tiles_x = (p.W + 31) / 32; k.tiles_y = (p.H + c.ROWS - 1) / c.ROWS; k.n_mtiles = p.MPad / c.BM; k.relu = p.relu;
@@ -1128,15 +1192,16 @@ hipError_t launch_conv3x3_bf16(const Conv16Problem& p, hipStream_t s)
         const bool kinds = p.M % c.BM == 0 && !p.mask_src && !p.mask16 && !p.pool32 && !env_off("ST2_CONV16_EPI");
         const bool lean16 = kinds && !p.out && !p.inject;
         if (lean16 && !dg && p.out16 && !pools) epi = 1;
-        else if (lean16 && !dg && pools && p.pool16 && p.amap && !p.out16 && !p.bits_out && p.H % 2 == 0 && p.W % 2 == 0) epi = 2;
+        else if (lean16 && !dg && pools && p.pool16 && p.amap && !p.out16 && !p.bits_out && p.H % 2 == 0 && p.W % 2 == 0) epi = p.pool_ave ? 6 : 2;
         else if (lean16 && dg && mb && p.out16) epi = 3;
         else if (kinds && !dg && p.out && p.out16 && !pools && !p.inject && c.cfg == 3) epi = 4;
         else if (kinds && dg && mb && p.out16 && !p.out && p.inject && c.cfg == 3 && !unpool) epi = 5;
         // ST2_CONV16_EPI_KINDS: bit (kind - 1): that kind may run (default: all five)
-        if (epi && !((env_int("ST2_CONV16_EPI_KINDS", 31) >> (epi - 1)) & 1)) epi = 0;
+        // (kind 6, the average pool, goes with kind 2's bit)
+        if (epi && !((env_int("ST2_CONV16_EPI_KINDS", 31) >> ((epi == 6 ? 2 : epi) - 1)) & 1)) epi = 0;
     }
     for (const Conv16Build& b : kConv16Builds) {
-        if (b.cfg != c.cfg || b.sb != c.sb || b.form != form || b.unpool != unpool || (b.epi != epi && b.epi != 0)) continue;
+        if (b.cfg != c.cfg || b.sb != c.sb || b.form != form || b.unpool != unpool || (b.epi != epi && b.epi != 0) || b.ave != (unpool && p.unpool_ave)) continue;
         b.kernel<<<dim3((unsigned)nblk), dim3(NT), 0, s>>>(k);
         return hipGetLastError();
     }
@@ -1177,6 +1242,48 @@ hipError_t launch_maxpool_bwd_idx16(const unsigned short* dy16, const unsigned c
     size_t grid = (total + 255) / 256;
     if (grid > 16384) grid = 16384;
     maxpool_bwd_idx16_k<<<(unsigned)grid, 256, 0, s>>>(reinterpret_cast<const uint4*>(dy16), reinterpret_cast<const uint2*>(amap),
+                                                        reinterpret_cast<uint4*>(dx16), CB, H, W);
+    return hipGetLastError();
+}
+
+// Average-pool backward from the sign map of the fused forward pool (Conv16Problem::pool_ave), all operands channel-blocked:
+//   dx16[cb][y][x][8] = bit (2 (y & 1) + (x & 1)) of map[cb][y/2][x/2][j] ? dy16[cb][y/2][x/2][j] / window size : 0
+// The bit is the ReLU mask of the conv blob the pool reads; the window is clipped at an odd edge (size 4, 2 or 1).  dy is bf16 and
+// 1 / size a power of two: the product, formed in fp32 and truncated back, is exact.  One thread per 8-channel block of a pixel.
+__global__ __launch_bounds__(256) void avepool_bwd_map16_k(const uint4* __restrict__ dy16, const uint2* __restrict__ map,
+                                                           uint4* __restrict__ dx16, int CB, int H, int W)
+{
+    const int ph = (H + 1) / 2, pw = (W + 1) / 2;
+    const size_t total = (size_t)CB * H * W;
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+        const int x = (int)(idx % W);
+        const size_t r = idx / W;
+        const int y = (int)(r % H), cb = (int)(r / H);
+        const size_t pi = ((size_t)cb * ph + (y >> 1)) * pw + (x >> 1);
+        const uint4 d = dy16[pi];
+        const uint2 m = map[pi];
+        const unsigned pos = 2u * (y & 1) + (x & 1);
+        const int n = (((y | 1) < H) ? 2 : 1) * (((x | 1) < W) ? 2 : 1);           // elements of the window inside the blob
+        const float scale = n == 4 ? 0.25f : n == 2 ? 0.5f : 1.0f;
+        auto part = [&](unsigned word, unsigned b0, unsigned b1) {              // two bf16 values; b0 / b1: their sign bytes
+            const float lo = __builtin_bit_cast(float, word << 16) * scale, hi = __builtin_bit_cast(float, word & 0xffff0000u) * scale;
+            return (((b0 >> pos) & 1u) ? __builtin_bit_cast(unsigned, lo) >> 16 : 0u) | (((b1 >> pos) & 1u) ? __builtin_bit_cast(unsigned, hi) & 0xffff0000u : 0u);
+        };
+        uint4 o;
+        o.x = part(d.x, m.x, m.x >> 8); o.y = part(d.y, m.x >> 16, m.x >> 24);
+        o.z = part(d.z, m.y, m.y >> 8); o.w = part(d.w, m.y >> 16, m.y >> 24);
+        dx16[idx] = o;
+    }
+}
+
+hipError_t launch_avepool_bwd_map16(const unsigned short* dy16, const unsigned char* map, unsigned short* dx16, int C, int H, int W, hipStream_t s)
+{
+    const int CB = (C + 7) / 8;
+    const size_t total = (size_t)CB * H * W;
+    if (total == 0) return hipErrorInvalidValue;
+    size_t grid = (total + 255) / 256;
+    if (grid > 16384) grid = 16384;
+    avepool_bwd_map16_k<<<(unsigned)grid, 256, 0, s>>>(reinterpret_cast<const uint4*>(dy16), reinterpret_cast<const uint2*>(map),
                                                         reinterpret_cast<uint4*>(dx16), CB, H, W);
     return hipGetLastError();
 }

@@ -23,7 +23,7 @@ const char* const kProfNames[P_COUNT] = {"conv3x3_fwd_mfma_f32", "conv3x3_dgrad_
                                           "conv3x3_fwd_mfma_bf16", "conv3x3_dgrad_mfma_bf16", "tile_comm",
                                           "gram_partial_mfma_bf16", "style_grad_mfma_bf16", "conv3x3_fwd_wino_split_bf16x6", "conv3x3_dgrad_wino_split_bf16x6",
                                           "style_grad_fused_in_conv_dgrad_bf16", "avepool_fwd", "avepool_bwd",
-                                          "gram_partial_split_bf16x6", "style_grad_split_bf16x6"};
+                                          "gram_partial_split_bf16x6", "style_grad_split_bf16x6", "avepool_bwd_map16"};
 
 static const struct { int kind; const char* name; int cin, cout; } kVgg19[] = {
     {0, "conv1_1", 3, 64}, {0, "conv1_2", 64, 64}, {1, "pool1", 0, 0},
@@ -166,7 +166,8 @@ int forward_range(st_ctx* c, ActSet& a, const float* x, int last, bool lean)
             p.bits_out = r.bits ? a.bits[i] : nullptr;
             p.K = L.cin; p.M = L.cout; p.MPad = conv_mpad(L.cout); p.H = H; p.W = W; p.relu = 1;
             double bytes = px * (2.0 * L.cin + (r.out32 ? 4.0 : 0.0) * L.cout + (r.out16 ? 2.0 : 0.0) * L.cout + (r.bits ? 0.125 : 0.0) * L.cout);
-            if (r.pools_next) {         // pooled bf16 copy for the conv after it, arg-max map for the backward
+            if (r.pools_next) {         // pooled bf16 copy for the conv after it, arg-max map (average pool: sign map) for the backward
+                p.pool_ave = pool.amap == AMAP_BLOCKED16_AVE;
                 p.pool16 = pool.out16 ? a.data16[i + 1] : nullptr;
                 p.pool32 = pool.out32 ? a.data[i + 1] : nullptr;
                 p.amap = a.amap[i + 1];
@@ -301,8 +302,10 @@ int backward_chain(st_ctx* c, int top, const float* top_diff, const std::vector<
         unsigned short* dst16 = (cur16 == c->diff16A) ? c->diff16B : c->diff16A;
         if ((r.mask == MASK_F32 || r.kind == B_POOL_CLASSIC) && !fwd[below].out32)
             return fail(ST_ERR_STATE, "internal: blob %d, which the backward of %s reads, is not materialised in fp32", below, L.name.c_str());
-        // conv: the diff above is still the POOLED one, expanded through the map of the max pool above (r.unpool)
+        // conv: the diff above is still the POOLED one, expanded through the map of the pool above (r.unpool) -- read as what the
+        // forward wrote into it
         const unsigned char* unpool_amap = r.unpool ? a.amap[i + 1] : nullptr;
+        const bool unpool_ave = r.unpool && fwd[i + 1].amap == AMAP_BLOCKED16_AVE;
         const double conv_flops = 2.0 * 9 * L.cin * L.cout * px;
         switch (r.kind) {
         case B_SMALLM16: {
@@ -330,6 +333,7 @@ int backward_chain(st_ctx* c, int top, const float* top_diff, const std::vector<
             }
             p.K = L.cout; p.M = L.cin; p.MPad = conv_mpad(L.cin); p.H = H; p.W = W; p.relu = 0;
             p.unpool_amap = unpool_amap;               // (3/4 byte per pooled channel value more, 1.5 less per full one)
+            p.unpool_ave = unpool_ave;
             const double mask_bytes = r.mask == MASK_BITS ? 0.125 : r.mask == MASK_BF16 ? 2.0 : r.mask == MASK_F32 ? 4.0 : 0.0;
             ProfScope ps(c, P_CONV_DGRAD_BF16, conv_flops,
                          px * ((r.unpool ? 0.75 : 2.0) * L.cout + (r.style ? 2.0 : 0.0) * L.cin + (r.out32 ? 4.0 : 0.0) * L.cin + (r.out16 ? 2.0 : 0.0) * L.cin + mask_bytes * L.cin));
@@ -358,6 +362,12 @@ int backward_chain(st_ctx* c, int top, const float* top_diff, const std::vector<
         case B_POOL_IDX16: {
             ProfScope ps(c, P_POOL_BWD, 0, (double)Cb * (hw * 3.0 + (size_t)Hb * Wb * 2.0));
             HIP_TRY(launch_maxpool_bwd_idx16(cur16, a.amap[i], dst16, Cb, Hb, Wb, c->stream));
+            break;
+        }
+        case B_AVEPOOL_MAP16: {
+            if (fwd[i].amap != AMAP_BLOCKED16_AVE) return fail(ST_ERR_STATE, "internal: the forward of %s wrote no sign map", L.name.c_str());
+            ProfScope ps(c, P_AVEPOOL_BWD_MAP16, 0, (double)Cb * (hw * 3.0 + (size_t)Hb * Wb * 2.0));
+            HIP_TRY(launch_avepool_bwd_map16(cur16, a.amap[i], dst16, Cb, Hb, Wb, c->stream));
             break;
         }
         case B_POOL_AMAP: {
@@ -736,6 +746,23 @@ int st_set_gram_algo(st_ctx* c, int algo)
     }
     c->epoch++;                // anything but st_step may change what a step launches: captured step graphs are stale
     c->gram_split = algo == 1;
+    return ST_OK;
+}
+
+int st_set_pool_algo(st_ctx* c, int algo)
+{
+    if (!c) return fail(ST_ERR_ARG, "ctx is NULL");
+    if (algo != 0 && algo != 1) return fail(ST_ERR_ARG, "pool algorithm %d: 0 every average pool a stand-alone pass, 1 fused into the bf16 conv launches around it where a build exists", algo);
+    c->epoch++;                // anything but st_step may change what a step launches: captured step graphs are stale
+    // (the activations stay as they are: FwdRoute::amap says which map their forward wrote, and the backward reads that record)
+    c->pool_algo = algo;
+    return ST_OK;
+}
+
+int st_get_pool_algo(st_ctx* c, int* algo)
+{
+    if (!c || !algo) return fail(ST_ERR_ARG, "NULL argument");
+    *algo = c->pool_algo;
     return ST_OK;
 }
 

@@ -37,7 +37,7 @@ int fail(int code, const char* fmt, ...);
 enum ProfClass { P_CONV_FWD, P_CONV_DGRAD, P_POOL_FWD, P_POOL_BWD, P_GRAM, P_GRAM_REDUCE, P_STYLE_GRAD,
                  P_LAYER_ELEM, P_IMAGE_PASS, P_FINALIZE, P_VECTOR, P_MISC, P_CONV_FWD_WINO, P_CONV_DGRAD_WINO,
                  P_CONV_FWD_BF16, P_CONV_DGRAD_BF16, P_COMM, P_GRAM_BF16, P_STYLE_GRAD_BF16, P_CONV_FWD_WSPLIT, P_CONV_DGRAD_WSPLIT, P_STYLE_FUSED_BF16,
-                 P_AVEPOOL_FWD, P_AVEPOOL_BWD, P_GRAM_SPLIT, P_STYLE_GRAD_SPLIT, P_COUNT };
+                 P_AVEPOOL_FWD, P_AVEPOOL_BWD, P_GRAM_SPLIT, P_STYLE_GRAD_SPLIT, P_AVEPOOL_BWD_MAP16, P_COUNT };
 extern const char* const kProfNames[P_COUNT];
 struct ProfRec { int cls; hipEvent_t a, b; double flops, bytes; };
 
@@ -59,21 +59,23 @@ struct Layer {
 // What every layer of one evaluation does, decided before the first launch (engine_route.cpp); forward_range and
 // backward_chain only execute it.  Entry i describes layer i (topo[i - 1]) and the blob it produces; entry 0 is the image.
 enum FwdKind : unsigned char { F_NONE, F_CONV16, F_WINO, F_WINO_SPLIT, F_DIRECT, F_FIRST_SPLIT, F_MAXPOOL, F_AVEPOOL,
-                               F_BY_CONV_BELOW };          // F_BY_CONV_BELOW: a max pool written by the epilogue of the conv below it
+                               F_BY_CONV_BELOW };          // F_BY_CONV_BELOW: a pool (max, or average under st_set_pool_algo 1) written by the epilogue of the conv below it
 enum AmapLayout : unsigned char { AMAP_NONE, AMAP_BLOCKED16,      // channel-blocked like the bf16 copies (bf16 conv epilogue)
-                                  AMAP_PLANAR32 };               // [C][ph][pw] (Winograd epilogues)
+                                  AMAP_PLANAR32,                 // [C][ph][pw] (Winograd epilogues)
+                                  AMAP_BLOCKED16_AVE };          // the buffer and layout of AMAP_BLOCKED16 holding an AVERAGE pool's sign bytes (bit e: window element e is inside the blob and > 0)
 enum BwdKind : unsigned char { B_NONE, B_SMALLM, B_SMALLM16, B_CONV16, B_WINO, B_WINO_SPLIT, B_DIRECT, B_AVEPOOL, B_POOL_IDX16,
                                B_POOL_AMAP, B_POOL_CLASSIC,
-                               B_IN_DGRAD_BELOW };         // a max pool expanded inside the data gradient of the conv below it
+                               B_IN_DGRAD_BELOW,           // a pool expanded inside the data gradient of the conv below it (through the map its forward wrote)
+                               B_AVEPOOL_MAP16 };          // an average pool through its sign map, as a pass (avepool_bwd_map16_k)
 enum MaskSrc : unsigned char { MASK_NONE, MASK_F32, MASK_BF16, MASK_BITS };
 
 struct FwdRoute {
     FwdKind kind = F_NONE;
     // what the forward leaves of blob i, whichever launch writes it
     bool out32 = false, out16 = false, bits = false;       // fp32 blob, bf16 copy, sign map
-    AmapLayout amap = AMAP_NONE;                           // arg-max map of a pool blob
+    AmapLayout amap = AMAP_NONE;                           // arg-max map (average pool: sign map) of a pool blob: what THIS forward wrote, whatever the switches say later
     bool pack16 = false;                                   // the bf16 copy comes from a pack_act16 pass after the launch
-    bool pools_next = false;                               // conv: the max pool above rides on this launch (entry i + 1 says what it writes)
+    bool pools_next = false;                               // conv: the pool above rides on this launch (entry i + 1 says what it writes)
     bool style16 = false;                                  // the Gram / style gradient of this blob take their F operand from the bf16 copy
     bool style_all16 = false;                              // ... and nothing of the style term reads the fp32 blob (style_runs16)
 };
@@ -83,7 +85,7 @@ struct BwdRoute {
     bool pack_in16 = false;                                // ... which nobody made: pack_act16 first
     bool out32 = false, out16 = false;                     // forms of the diff it produces
     MaskSrc mask = MASK_NONE;                              // ReLU mask of the blob below
-    bool unpool = false;                                   // conv: the incoming diff is the POOLED one, expanded through the map of the pool above
+    bool unpool = false;                                   // conv: the incoming diff is the POOLED one, expanded through the map of the pool above (either kind: FwdRoute::amap of that pool)
     bool style = false;                                    // conv: the style gradient of the blob below rides on the launch
 };
 struct RoutePlan { std::vector<FwdRoute> fwd; std::vector<BwdRoute> bwd; };
@@ -117,6 +119,7 @@ struct st_ctx {
     bool in_step = false;                          // inside step_enqueue: objective evaluations may skip fp32 blobs nothing reads (lean fp32)
     bool wino = true;                              // Winograd F(2x2,3x3) for the eligible fp32 convs (ST2_WINO=0 disables)
     bool wino_split = false;                       // ... on the bf16 matrix cores with three-way split operands where the shape allows (st_set_conv_algo(ctx, 2))
+    int pool_algo = 0;                             // 1: an average pool rides on the bf16 conv launches around it in the lean flow (st_set_pool_algo)
     bool gram_split = false;                       // fp32 features: Gram partials and style gradients on the bf16 matrix cores with three-way split operands where the shape allows (st_set_gram_algo(ctx, 1))
     unsigned short* dsplit = nullptr; size_t dsplit_cap = 0;      // ... and the three-term operand image of D (gram_split.hip), sized for the widest blob when the option is set
     unsigned short *diff16A = nullptr, *diff16B = nullptr;

@@ -69,9 +69,15 @@ static WinoChoice wino_choice(const st_ctx* c, const float* pack, const unsigned
     return ch;
 }
 
+namespace {
+struct Dgrad;
+Dgrad dgrad_route(const st_ctx* c, const ActSet& a, int i);
+}
+static bool ave_pool_fuse_ok(const st_ctx* c, const ActSet& a, int i);
+
 // ------------------------------------------------------------------------------------------ forward
 // `lean`: a conv blob whose only consumers are bf16 convs / a fused pool is not written in fp32 at all, a pool that follows such a
-// conv is computed in that conv's epilogue (bf16 pooled copy + arg-max map); fp32 (inside an iteration): the full-resolution blob
+// conv is computed in that conv's epilogue (bf16 pooled copy + arg-max map; an average pool under st_set_pool_algo(ctx, 1): + sign map); fp32 (inside an iteration): the full-resolution blob
 // of a pooled, un-weighted layer is not written when the Winograd epilogue pools it and writes the arg-max map.
 void plan_forward(const st_ctx* c, const ActSet& a, int last, bool lean, std::vector<FwdRoute>& fwd)
 {
@@ -110,19 +116,21 @@ void plan_forward(const st_ctx* c, const ActSet& a, int last, bool lean, std::ve
         // this launch's epilogue) instead of the bf16 copy (16 bits)
         const bool bits_i = want_bits && conv_next16 && L.cout % 32 == 0;
         const bool next_max_pool = i < last && !c->topo[i].is_conv && !c->topo[i].ave;
+        const bool next_ave_pool = i < last && !c->topo[i].is_conv && c->topo[i].ave;
         r.out32 = true;
         if (c->bf16 && conv16_ok(c, L.cin) && fwd[i - 1].out16) {
             r.kind = F_CONV16;
             r.out16 = next16;
             if (lean && !blob_needs32(c, a, i) && i < last) {
-                // (a weighted blob gets an injected diff: classic pool backward; an average pool always runs stand-alone on the fp32 blob)
-                if (next_max_pool && !blob_active(c, i) && conv16_resolve(shape16(L.cin, L.cout, H, W)).can_pool) {
-                    // the pool rides on this launch: pooled bf16 copy for the conv after it, arg-max map for the backward
+                // (a weighted blob gets an injected diff: classic pool backward; an average pool runs stand-alone on the fp32 blob
+                // unless st_set_pool_algo(ctx, 1) and its backward can go through the sign map: ave_pool_fuse_ok)
+                if ((next_max_pool || (next_ave_pool && ave_pool_fuse_ok(c, a, i))) && !blob_active(c, i) && conv16_resolve(shape16(L.cin, L.cout, H, W)).can_pool) {
+                    // the pool rides on this launch: pooled bf16 copy for the conv after it, arg-max / sign map for the backward
                     FwdRoute& pool = fwd[i + 1];
                     pool.kind = F_BY_CONV_BELOW;
                     pool.out16 = feeds_conv16(c, a, i + 1, last);
                     pool.out32 = !pool.out16 || blob_active(c, i + 1) || i + 1 == last;
-                    pool.amap = AMAP_BLOCKED16;
+                    pool.amap = next_ave_pool ? AMAP_BLOCKED16_AVE : AMAP_BLOCKED16;
                     r.pools_next = true;
                     r.out32 = false;
                 } else if (conv_next16) {
@@ -174,7 +182,8 @@ namespace {
 struct Dgrad {
     BwdKind kind;
     bool wants16;                                  // whatever produces its incoming diff writes the bf16 copy
-    // it may take the POOLED diff and expand it through the arg-max map of the max pool above its output: conv16_body's UNPOOL builds
+    // it may take the POOLED diff and expand it through the map of the pool above its output (arg-max map of a max pool, sign map of a
+    // fused average pool): conv16_body's UNPOOL builds
     // stage the pooled diff and expand it in LDS; the Winograd kernel unpools in its input transform (the split-operand kernel has
     // no unpooling input transform: its launches keep maxpool_bwd_amap_k)
     bool can_unpool;
@@ -201,6 +210,15 @@ Dgrad dgrad_route(const st_ctx* c, const ActSet& a, int i)
 }
 }  // namespace
 
+// The one predicate of "the average pool above conv layer i rides on the bf16 conv launches around it" that is not the max pool's too:
+// the switch, and a data gradient of conv i that reads a bf16 diff -- in its staged tile (can_unpool) or from avepool_bwd_map16_k.
+// plan_forward fuses only where this holds and records AMAP_BLOCKED16_AVE; plan_backward goes through the map where the record says so
+// and the same dgrad_route answer (next.wants16) still holds: the fp32 conv blob the forward skipped is never asked for.
+static bool ave_pool_fuse_ok(const st_ctx* c, const ActSet& a, int i)
+{
+    return c->pool_algo == 1 && dgrad_route(c, a, i).wants16;
+}
+
 // `lean` must be what the forward that filled `a` ran with: the fp32 diff of a layer is then written only when its consumer needs
 // fp32 (a pool without arg-max map, the 3-channel conv1_1 kernel, a non-bf16 conv), ReLU masks come from the bf16 copies or sign
 // maps, and pools fused into their producing conv are back-propagated through their arg-max maps in bf16.
@@ -210,7 +228,7 @@ void plan_backward(const st_ctx* c, const ActSet& a, int top, const std::vector<
     const std::vector<FwdRoute>& fwd = a.plan.fwd;
     bwd.assign(c->nb, BwdRoute{});
     bool have32 = true, have16 = false;            // forms of the running diff (the top diff arrives in fp32)
-    bool pooled = false;                           // ... which is still the POOLED diff of the max pool just passed
+    bool pooled = false;                           // ... which is still the POOLED diff of the pool just passed
     for (int i = top; i >= 1; --i) {
         const Layer& L = c->topo[i - 1];
         BwdRoute& r = bwd[i];
@@ -236,7 +254,7 @@ void plan_backward(const st_ctx* c, const ActSet& a, int top, const std::vector<
                 if (below_is_conv && lean && fwd[below].bits) r.mask = MASK_BITS;
             }
             have32 = r.out32; have16 = r.out16;
-        } else if (L.ave) {
+        } else if (L.ave && !(lean && fwd[i].amap == AMAP_BLOCKED16_AVE && !inj[below] && next.wants16)) {
             // dx = mask(dy / window size) + inject in one pass; the bf16 copy for a bf16 dgrad conv below comes out of the same pass
             // (no pack_act16), the fp32 diff where the consumer below reads fp32 (or every diff is materialised)
             r.kind = B_AVEPOOL;
@@ -251,8 +269,10 @@ void plan_backward(const st_ctx* c, const ActSet& a, int top, const std::vector<
             have16 = true;
             // ... inside the data gradient of the conv below when it has the build (maxpool_bwd_idx16_k, its full-resolution
             // output and the conv's read of it are gone)
+            // (an average pool whose forward wrote the sign map -- the record of that forward, not the switch's value now -- likewise:
+            // inside the data gradient below, or avepool_bwd_map16_k)
             if (next.can_unpool) { r.kind = B_IN_DGRAD_BELOW; pooled = true; }
-            else { r.kind = B_POOL_IDX16; r.out16 = true; have32 = false; }
+            else { r.kind = L.ave ? B_AVEPOOL_MAP16 : B_POOL_IDX16; r.out16 = true; have32 = false; }
         } else if (fwd[i].amap == AMAP_PLANAR32 && !inj[below] && below_is_conv && have32) {
             // pool fused into its producing Winograd conv (fp32): through the arg-max map, ReLU mask included, inside the data
             // gradient below (maxpool_bwd_amap_k, its full-resolution output and the conv's read of it are gone; same values bit

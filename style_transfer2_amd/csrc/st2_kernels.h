@@ -131,12 +131,18 @@ struct Conv16Problem {
     unsigned short* pool16 = nullptr;       // bf16 channel-blocked pooled copy [M/8][ph][pw][8]
     float* pool32 = nullptr;                // fp32 pooled blob [M][ph][pw]
     unsigned char* amap = nullptr;          // [M/8][ph][pw][8] bytes: bits 0-1 arg-max slot (row-major in the window), bit 2 maximum > 0
+    // ... or (pool_ave) the Caffe AVE pool of it: (((0 + v00) + v01) + v10) + v11 over the in-image elements times 0.25 / 0.5 / 1 (the
+    // arithmetic of launch_avepool_fwd, bit for bit), and amap becomes the SIGN map of the window: bit e (row-major in the window) =
+    // element e lies inside the blob and its fp32 post-ReLU value is > 0, bits 4-7 zero
+    bool pool_ave = false;
     // data-gradient, optional: the style gradient of the blob this launch differentiates rides on the launch,
     //     out = mask(conv) + D' @ F        (D' = sw / norm * c2 * D as hi + lo bf16 terms: launch_style_fuse_pack; F = s_in16, M channels)
     const unsigned short* s_in16 = nullptr; const unsigned short* s_wpack16 = nullptr;
     // data-gradient directly below a max-pool, optional (Conv16Launch::can_unpool): in16 is the POOLED diff [K/8][H/2][W/2][8] and unpool_amap
     // the pool's arg-max map; the launch expands them in its staged tile (maxpool_bwd_idx16_k and its output are not needed)
     const unsigned char* unpool_amap = nullptr;
+    // ... or (unpool_ave) below an average pool whose forward wrote the sign map (pool_ave): every element takes dy * 0.25 where its bit is set
+    bool unpool_ave = false;
     // one bit per element of a post-ReLU blob, "its bf16 copy is non-zero", in the accumulator layout of the 32 x 32 MFMA tile:
     //     [M / 32][H * W][2] 16-bit words; word (blk, pixel, half), bit 8 h + e  <->  channel 32 blk + 4 half + 16 h + (e & 3) + 8 (e >> 2)
     // (conv16_bits_elems words, M % 32 == 0).  bits_out: written by a forward launch next to out16; mask_bits: read by the data
@@ -163,6 +169,9 @@ struct Conv16Launch {
 Conv16Launch conv16_resolve(const Conv16Problem& p);
 // dx16 = pool backward of dy16 through the arg-max map (all channel-blocked, C % 8 == 0), ReLU mask of the pooled-from blob included
 hipError_t launch_maxpool_bwd_idx16(const unsigned short* dy16, const unsigned char* amap, unsigned short* dx16, int C, int H, int W, hipStream_t s);
+// the same for an average pool fused into its producing conv (Conv16Problem::pool_ave): dx16 = bit (y & 1, x & 1) of the window's sign
+// byte ? dy16 / window size : 0, the window clipped at an odd edge (divisor 4, 2 or 1); H, W = the full-resolution size, any parity
+hipError_t launch_avepool_bwd_map16(const unsigned short* dy16, const unsigned char* map, unsigned short* dx16, int C, int H, int W, hipStream_t s);
 size_t conv16_pack_elems(int K, int M);
 void pack_conv_weights16_fwd(const float* w, int Cout, int Cin, unsigned short* dst);
 void pack_conv_weights16_dgrad(const float* w, int Cout, int Cin, unsigned short* dst);

@@ -101,6 +101,20 @@ class Engine:
         check(self.lib.st_get_algos(self._ctx, byref(conv), byref(gram)))
         return conv.value, gram.value
 
+    def set_pool_algo(self, algo):
+        """0 (default): every average pool is a stand-alone pass; 1: an average pool rides on the bf16 conv launches around it in the lean
+        'bf16' flow (same results bit for bit; every other precision and evaluation routes as under 0).  Takes effect from the next
+        evaluation."""
+        if algo not in (0, 1):
+            raise ValueError('pool_algo must be 0 (stand-alone passes) or 1 (fused into the bf16 conv launches), not %r' % (algo,))
+        check(self.lib.st_set_pool_algo(self._ctx, int(algo)))
+
+    def pool_algo(self):
+        """The pool_algo in force."""
+        algo = c_int()
+        check(self.lib.st_get_pool_algo(self._ctx, byref(algo)))
+        return algo.value
+
     # -- lifecycle -------------------------------------------------------------------------------
     def close(self):
         if self._ctx:

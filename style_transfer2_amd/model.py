@@ -18,13 +18,15 @@ F32 = np.float32
 class HipModel:
     mean = np.array((123.68, 116.779, 103.939), F32).reshape(3, 1, 1)   # reference worker.py:34
 
-    def __init__(self, params, topology=None, device=0, engine=None, precision='fp32', conv_algo=None, gram_algo=None):
+    def __init__(self, params, topology=None, device=0, engine=None, precision='fp32', conv_algo=None, gram_algo=None, pool_algo=None):
         self.engine = engine if engine is not None else Engine(topology, device, precision)
-        # None: the engine's default stays; otherwise Engine.set_conv_algo / set_gram_algo (ValueError outside their sets)
+        # None: the engine's default stays; otherwise Engine.set_conv_algo / set_gram_algo / set_pool_algo (ValueError outside their sets)
         if conv_algo is not None:
             self.engine.set_conv_algo(conv_algo)
         if gram_algo is not None:
             self.engine.set_gram_algo(gram_algo)
+        if pool_algo is not None:
+            self.engine.set_pool_algo(pool_algo)
         if params is not None:
             self.engine.load_weights(params)
 

@@ -9,10 +9,6 @@ import sys
 import numpy as np
 from PIL import Image
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import style_transfer2_amd as st2                                   # noqa: E402
-from style_transfer2_amd import jobs, weights as st2_weights         # noqa: E402
-
 ap = argparse.ArgumentParser()
 ap.add_argument('content'); ap.add_argument('style'); ap.add_argument('out')
 ap.add_argument('--size', type=int, default=512)
@@ -21,11 +17,24 @@ ap.add_argument('--iters', type=int, default=500)
 ap.add_argument('--optimizer', default='adam', choices=['adam', 'lbfgs'])
 ap.add_argument('--weights', default='', help='.npz or .caffemodel; default: seeded synthetic weights')
 ap.add_argument('--gpu', type=int, default=0)
+ap.add_argument('--precision', default='fp32', choices=['fp32', 'bf16', 'bf16-full'], help='st_set_precision: conv operands in fp32 or bf16')
 ap.add_argument('--conv-algo', type=int, default=None, choices=[0, 1, 2], help='st_set_conv_algo (default: the engine\'s, 1)')
 ap.add_argument('--gram-algo', type=int, default=None, choices=[0, 1], help='st_set_gram_algo (default: the engine\'s, 0)')
+ap.add_argument('--ave-pools', action='store_true', help='VGG19 with every pool an average pool (Caffe `pool: AVE`; the pooling of vgg_normalised-style weights)')
+ap.add_argument('--pool-algo', type=int, default=None, choices=[0, 1], help='st_set_pool_algo (default: the engine\'s, 0); 1 fuses average pools into the bf16 conv launches (--precision bf16)')
 ap.add_argument('--grid', default='', help='RxC: tile-shard the image over this one GPU (large images)')
 ap.add_argument('--shard-style', action='store_true', help='with --grid: cut the style image over the ranks as well (every rank forwards one window of it)')
 args = ap.parse_args()
+if args.ave_pools and args.grid:
+    ap.error('--ave-pools with --grid: tile-sharded mode does not run average pools')
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import style_transfer2_amd as st2                                   # noqa: E402
+from style_transfer2_amd import jobs, weights as st2_weights         # noqa: E402
+
+topology = st2.VGG19_TOPOLOGY
+if args.ave_pools:
+    topology = tuple(('pool', layer[1], 'ave') if layer[0] == 'pool' else layer for layer in topology)
 
 if args.weights.endswith('.npz'):
     params = st2_weights.load_npz(args.weights, st2.VGG19_TOPOLOGY)
@@ -39,7 +48,8 @@ if args.grid:
     image = jobs.run_tiled_job(params, jobs.load_rgb(args.content), jobs.load_rgb(args.style), args.iters, (rows, cols), size=args.size,
                                style_size=args.style_size or None, device=args.gpu, optimizer=args.optimizer, shard_style=args.shard_style)
 else:
-    job = st2.StyleTransfer(st2.HipModel(params, device=args.gpu, conv_algo=args.conv_algo, gram_algo=args.gram_algo))
+    job = st2.StyleTransfer(st2.HipModel(params, topology=None if topology is st2.VGG19_TOPOLOGY else topology, device=args.gpu, precision=args.precision,
+                                         conv_algo=args.conv_algo, gram_algo=args.gram_algo, pool_algo=args.pool_algo))
     image = jobs.run_job(job, jobs.load_rgb(args.content), jobs.load_rgb(args.style), args.iters, size=args.size,
                          style_size=args.style_size or None, optimizer=args.optimizer)
 Image.fromarray(np.uint8(np.clip(image, 0, 255))).save(args.out)

@@ -69,12 +69,13 @@ def setup_signals():
 
 
 # ---------------------------------------------------------------------------------------------------
-ALGO_KEYS = {'conv_algo': (0, 1, 2), 'gram_algo': (0, 1)}
+ALGO_KEYS = {'conv_algo': (0, 1, 2), 'gram_algo': (0, 1), 'pool_algo': (0, 1)}
 
 
 def read_algo_keys(config):
     """The optional integer config keys that select the engine's arithmetic: ``conv_algo`` (0 direct, 1 Winograd on the fp32 matrix
-    cores, 2 split-operand Winograd) and ``gram_algo`` (0 fp32 matrix cores, 1 split operands).  Returns the HipModel keyword
+    cores, 2 split-operand Winograd), ``gram_algo`` (0 fp32 matrix cores, 1 split operands) and ``pool_algo`` (0 average pools as
+    stand-alone passes, 1 fused into the bf16 conv launches around them).  Returns the HipModel keyword
     arguments of the keys that are present (an absent key makes no call: the engine's default stays); a value outside a key's set is
     a ValueError that names the key.  Pure: any mapping with ``get`` will do."""
     kwargs = {}
