@@ -174,6 +174,10 @@ int st_graph_replays(st_ctx* ctx, long long* n);
  * s.y > 1e-10; nothing is applied to the iterate.  Replaces the optimizer's history (the next step starts empty). */
 int st_lbfgs_inv_hv(st_ctx* ctx, int n_pairs, const float* const* s, const float* const* y, const float* g, float* out_p);
 int st_sync(st_ctx* ctx);
+/* Test hook: device and pinned host memory the engine holds right now, in requested bytes, over EVERY context of the process
+ * (no context argument).  Every allocation of the engine passes one funnel that counts it; after st_destroy of all contexts
+ * both figures are what they were before the first st_create.  Either pointer may be NULL. */
+int st_live_bytes(long long* device, long long* pinned);
 
 /* ---- measurement ----------------------------------------------------------------------------------- */
 /* per-kernel-class HIP-event timing on the engine's own stream */

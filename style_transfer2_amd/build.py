@@ -38,7 +38,7 @@ SOURCES = (
     ('engine_tile.cpp', ('-x', 'hip')),
     ('engine_comm.cpp', ('-x', 'hip')),
 )
-HEADERS = ('st2_kernels.h', 'env.h', 'wave_reduce.h', 'engine.h', os.path.join('..', '..', 'include', 'st2.h'))
+HEADERS = ('st2_kernels.h', 'env.h', 'wave_reduce.h', 'engine.h', 'devbuf.h', os.path.join('..', '..', 'include', 'st2.h'))
 
 
 def _hipcc():

@@ -81,6 +81,7 @@ PROTOTYPES = {
     'st_step_pending': (c_int, [c_void_p]),
     'st_step_frame_room': (c_int, [c_void_p, c_size_t, c_size_t]),
     'st_graph_replays': (c_int, [c_void_p, POINTER(c_longlong)]),
+    'st_live_bytes': (c_int, [POINTER(c_longlong), POINTER(c_longlong)]),
     'st_lbfgs_inv_hv': (c_int, [c_void_p, c_int, POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_void_p]),
     'st_sync': (c_int, [c_void_p]),
     'st_profile_enable': (c_int, [c_void_p, c_int]),

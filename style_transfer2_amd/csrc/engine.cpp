@@ -7,6 +7,8 @@
 // engine_resample.cpp, the tile-sharded phases in engine_tile.cpp.
 #include "engine.h"
 
+#include <atomic>
+
 namespace st2e {
 static thread_local char g_err[1024] = "";
 int fail(int code, const char* fmt, ...)
@@ -34,45 +36,48 @@ static const struct { int kind; const char* name; int cin, cout; } kVgg19[] = {
 };
 
 // ---------------------------------------------------------------------------------------- helpers
-int dmalloc(float** p, size_t nfloats)
+// The funnel of devbuf.h: the only place that allocates or frees device / pinned memory, and the two process-wide counters of what
+// is live (requested bytes) behind st_live_bytes.
+static std::atomic<long long> g_live_dev{0}, g_live_pin{0};
+int raw_alloc(void** p, size_t bytes)
 {
     void* q = nullptr;
-    hipError_t e = hipMalloc(&q, std::max<size_t>(nfloats, 1) * sizeof(float));
-    if (e != hipSuccess) return fail(ST_ERR_HIP, "hipMalloc(%zu floats): %s", nfloats, hipGetErrorString(e));
-    *p = (float*)q;
+    hipError_t e = hipMalloc(&q, bytes);
+    if (e != hipSuccess) return fail(ST_ERR_HIP, "hipMalloc of %zu bytes: %s", bytes, hipGetErrorString(e));
+    g_live_dev += (long long)bytes;
+    *p = q;
     return ST_OK;
 }
-void dfree(float*& p)
+void raw_free(void* p, size_t bytes)
 {
-    if (p && hipFree(p) != hipSuccess) (void)hipGetLastError();   // never leave a sticky error behind
-    p = nullptr;
+    if (hipFree(p) != hipSuccess) (void)hipGetLastError();   // never leave a sticky error behind
+    g_live_dev -= (long long)bytes;
+}
+int raw_pin_alloc(void** p, size_t bytes)
+{
+    void* q = nullptr;
+    hipError_t e = hipHostMalloc(&q, bytes, 0);
+    if (e != hipSuccess) return fail(ST_ERR_HIP, "hipHostMalloc of %zu bytes: %s", bytes, hipGetErrorString(e));
+    g_live_pin += (long long)bytes;
+    *p = q;
+    return ST_OK;
+}
+void raw_pin_free(void* p, size_t bytes)
+{
+    if (hipHostFree(p) != hipSuccess) (void)hipGetLastError();
+    g_live_pin -= (long long)bytes;
 }
 
 // room for the split-K partial sums of a Winograd launch that would otherwise leave most CUs idle
-int dmalloc16(unsigned short** p, size_t n)
-{
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, std::max<size_t>(n, 8) * sizeof(unsigned short));
-    if (e != hipSuccess) return fail(ST_ERR_HIP, "hipMalloc(%zu bf16): %s", n, hipGetErrorString(e));
-    *p = (unsigned short*)q;
-    return ST_OK;
-}
-void dfree16(unsigned short*& p)
-{
-    if (p && hipFree(p) != hipSuccess) (void)hipGetLastError();
-    p = nullptr;
-}
 int wino_scratch(st_ctx* c, ConvProblem& p, int splits)
 {
     if (splits <= 1) return ST_OK;
     const size_t need = (size_t)splits * p.M * p.H * p.W;
-    if (need > c->conv_scratch_cap) {
+    if (need > c->conv_scratch.cap()) {
         HIP_TRY(hipStreamSynchronize(c->stream));
-        dfree(c->conv_scratch); c->conv_scratch_cap = 0;
-        ST_TRY(dmalloc(&c->conv_scratch, need));
-        c->conv_scratch_cap = need;
+        ST_TRY(c->conv_scratch.reserve(need));
     }
-    p.scratch = c->conv_scratch; p.scratch_floats = c->conv_scratch_cap;
+    p.scratch = c->conv_scratch; p.scratch_floats = c->conv_scratch.cap();
     return ST_OK;
 }
 
@@ -87,48 +92,26 @@ void shapes_for(const st_ctx* c, int H, int W, std::vector<int>& C, std::vector<
     }
 }
 
-void act_free(ActSet& a)
-{
-    for (size_t i = 1; i < a.data.size(); ++i) dfree(a.data[i]);
-    for (size_t i = 0; i < a.data16.size(); ++i) dfree16(a.data16[i]);
-    for (size_t i = 0; i < a.amap.size(); ++i) if (a.amap[i]) { (void)hipFree(a.amap[i]); a.amap[i] = nullptr; }
-    for (size_t i = 0; i < a.bits.size(); ++i) dfree16(a.bits[i]);
-    a.bits.clear();
-    a.data.clear();
-    a.data16.clear();
-    a.amap.clear();
-    a.H = a.W = 0;
-    a.valid_to = -1;
-}
-
 int act_ensure(st_ctx* c, ActSet& a, int H, int W)
 {
     if (a.H == H && a.W == W && !a.data.empty()) return ST_OK;
-    act_free(a);
+    a = ActSet{};
     shapes_for(c, H, W, a.C, a.h, a.w);
+    a.own.resize(c->nb);
     a.data.assign(c->nb, nullptr);
-    a.data16.assign(c->nb, nullptr);
-    a.amap.assign(c->nb, nullptr);
-    a.bits.assign(c->nb, nullptr);
+    a.data16.resize(c->nb);
+    a.amap.resize(c->nb);
+    a.bits.resize(c->nb);
     a.plan.fwd.assign(c->nb, FwdRoute{});
     a.plan.bwd.assign(c->nb, BwdRoute{});
-    for (int i = 1; i < c->nb; ++i) ST_TRY(dmalloc(&a.data[i], (size_t)a.C[i] * a.h[i] * a.w[i]));
+    for (int i = 1; i < c->nb; ++i) { ST_TRY(a.own[i].alloc((size_t)a.C[i] * a.h[i] * a.w[i])); a.data[i] = a.own[i]; }
     a.H = H; a.W = W;
     return ST_OK;
 }
 
-// the buffers of blob b beyond the fp32 one, made when a plan first names them
-static int ensure16(ActSet& a, int b)
-{
-    if (!a.data16[b]) ST_TRY(dmalloc16(&a.data16[b], act16_elems(a.C[b], (size_t)a.h[b] * a.w[b])));
-    return ST_OK;
-}
-static int ensure_amap(ActSet& a, int b)
-{
-    // (one size for both layouts: the buffer is shared when the precision is switched)
-    if (!a.amap[b]) HIP_TRY(hipMalloc((void**)&a.amap[b], act16_elems(a.C[b], (size_t)a.h[b] * a.w[b])));
-    return ST_OK;
-}
+// the buffers of blob b beyond the fp32 one are made when a plan first names them; bf16 copy and map have one size (the map also for
+// both of its layouts: the buffer is shared when the precision is switched)
+static size_t elems16(const ActSet& a, int b) { return act16_elems(a.C[b], (size_t)a.h[b] * a.w[b]); }
 static int pack16(st_ctx* c, const float* src, unsigned short* dst, int C, size_t hw)
 {
     ProfScope ps(c, P_MISC, 0, hw * 6.0 * C);
@@ -152,10 +135,10 @@ int forward_range(st_ctx* c, ActSet& a, const float* x, int last, bool lean)
         const size_t hw = (size_t)H * W;
         const double px = (double)hw, n_in = (double)a.C[i - 1] * a.h[i - 1] * a.w[i - 1];
         if (L.is_conv && !L.loaded) return fail(ST_ERR_STATE, "weights of %s were never loaded", L.name.c_str());
-        if (r.out16) ST_TRY(ensure16(a, i));
-        if (r.bits && !a.bits[i]) ST_TRY(dmalloc16(&a.bits[i], conv16_bits_elems(C, hw)));
-        if (r.pools_next && pool.out16) ST_TRY(ensure16(a, i + 1));
-        if (r.pools_next && pool.amap != AMAP_NONE) ST_TRY(ensure_amap(a, i + 1));
+        if (r.out16) ST_TRY(a.data16[i].reserve(elems16(a, i)));
+        if (r.bits) ST_TRY(a.bits[i].reserve(conv16_bits_elems(C, hw)));
+        if (r.pools_next && pool.out16) ST_TRY(a.data16[i + 1].reserve(elems16(a, i + 1)));
+        if (r.pools_next && pool.amap != AMAP_NONE) ST_TRY(a.amap[i + 1].reserve(elems16(a, i + 1)));
         const double conv_flops = 2.0 * 9 * L.cin * L.cout * px;
         switch (r.kind) {
         case F_CONV16: {
@@ -188,7 +171,7 @@ int forward_range(st_ctx* c, ActSet& a, const float* x, int last, bool lean)
                 ProfScope ps(c, r.kind == F_WINO_SPLIT ? P_CONV_FWD_WSPLIT : r.kind == F_WINO ? P_CONV_FWD_WINO : P_CONV_FWD, conv_flops,
                              4.0 * px * (L.cin + L.cout));
                 if (r.kind == F_WINO_SPLIT) {
-                    p.wpack = reinterpret_cast<const float*>(L.us_fwd); ST_TRY(wino_scratch(c, p, wino_split_resolve(p.K, p.M, H, W).splits));
+                    p.wpack = reinterpret_cast<const float*>(L.us_fwd.get()); ST_TRY(wino_scratch(c, p, wino_split_resolve(p.K, p.M, H, W).splits));
                     HIP_TRY(launch_conv3x3_wino_split(p, c->stream));
                 } else if (r.kind == F_WINO) {
                     p.wpack = L.u_fwd; ST_TRY(wino_scratch(c, p, wino_resolve(p.K, p.M, H, W).splits));
@@ -227,18 +210,8 @@ int forward_range(st_ctx* c, ActSet& a, const float* x, int last, bool lean)
 int ensure_gram_bufs(st_ctx* c, int C, int hw, GramPlan& pl, bool plan16)
 {
     pl = plan16 ? gram_plan16(C, hw) : gram_plan(C, hw);
-    if (pl.slab_floats > c->gram_slab_cap) {
-        dfree(c->gram_slabs);
-        ST_TRY(dmalloc(&c->gram_slabs, pl.slab_floats));
-        c->gram_slab_cap = pl.slab_floats;
-    }
-    const size_t fold = (size_t)gram_fold_groups(pl) * C * C;
-    if (fold > c->gram_fold_cap) {
-        dfree(c->gram_fold);
-        ST_TRY(dmalloc(&c->gram_fold, fold));
-        c->gram_fold_cap = fold;
-    }
-    return ST_OK;
+    ST_TRY(c->gram_slabs.reserve(pl.slab_floats));
+    return c->gram_fold.reserve((size_t)gram_fold_groups(pl) * C * C);
 }
 
 // fp32 features, not tile-sharded (the ROI Grams of that mode and their all-reduced raw sums keep the fp32 kernels), a shape the
@@ -281,7 +254,7 @@ int backward_chain(st_ctx* c, int top, const float* top_diff, const std::vector<
     const unsigned short* cur16 = nullptr;             // bf16 copy of the running diff, when a producer already made it
     if (c->bf16 && !c->diff16A) {
         const size_t cap = c->max_blob + 8 * (size_t)a.h[0] * a.w[0];
-        ST_TRY(dmalloc16(&c->diff16A, cap)); ST_TRY(dmalloc16(&c->diff16B, cap));
+        ST_TRY(c->diff16A.alloc(cap)); ST_TRY(c->diff16B.alloc(cap));
     }
     for (int i = top; i >= 1; --i) {
         const Layer& L = c->topo[i - 1];
@@ -348,7 +321,7 @@ int backward_chain(st_ctx* c, int top, const float* top_diff, const std::vector<
             p.unpool_amap = unpool_amap;
             ProfScope ps(c, r.kind == B_WINO_SPLIT ? P_CONV_DGRAD_WSPLIT : r.kind == B_WINO ? P_CONV_DGRAD_WINO : P_CONV_DGRAD, conv_flops,
                          4.0 * px * (L.cin + (r.unpool ? 0.3125 : 1.0) * L.cout));
-            if (r.kind == B_WINO_SPLIT) { p.wpack = reinterpret_cast<const float*>(L.us_bwd); ST_TRY(wino_scratch(c, p, wino_split_resolve(p.K, p.M, H, W).splits)); HIP_TRY(launch_conv3x3_wino_split(p, c->stream)); }
+            if (r.kind == B_WINO_SPLIT) { p.wpack = reinterpret_cast<const float*>(L.us_bwd.get()); ST_TRY(wino_scratch(c, p, wino_split_resolve(p.K, p.M, H, W).splits)); HIP_TRY(launch_conv3x3_wino_split(p, c->stream)); }
             else if (r.kind == B_WINO) { p.wpack = L.u_bwd; ST_TRY(wino_scratch(c, p, wino_resolve(p.K, p.M, H, W).splits)); HIP_TRY(launch_conv3x3_wino(p, c->stream)); }
             else HIP_TRY(launch_conv3x3(p, c->stream));
             break;
@@ -400,18 +373,18 @@ int ensure_input_buffers(st_ctx* c, int H, int W)
     // work buffers by the new one): the hooks refuse until the next forward
     c->act.valid_to = -1;
     const size_t n3 = (size_t)3 * H * W;
-    for (int i = 0; i < 2; ++i) { dfree(c->x[i]); ST_TRY(dmalloc(&c->x[i], n3)); }
-    dfree(c->grad); ST_TRY(dmalloc(&c->grad, n3));
-    dfree(c->m); dfree(c->v);
-    ST_TRY(dmalloc(&c->m, n3)); ST_TRY(dmalloc(&c->v, n3));
-    dfree(c->g_cur); dfree(c->pvec);
-    for (int i = 0; i <= st_ctx::kCorr; ++i) { dfree(c->hs[i]); dfree(c->hy[i]); }
-    dfree(c->hwc_dev); ST_TRY(dmalloc(&c->hwc_dev, n3));
+    for (int i = 0; i < 2; ++i) ST_TRY(c->x[i].alloc(n3));
+    ST_TRY(c->grad.alloc(n3));
+    c->m.reset(); c->v.reset();
+    ST_TRY(c->m.alloc(n3)); ST_TRY(c->v.alloc(n3));
+    c->g_cur.reset(); c->pvec.reset();
+    for (int i = 0; i <= st_ctx::kCorr; ++i) { c->hs[i].reset(); c->hy[i].reset(); }
+    ST_TRY(c->hwc_dev.alloc(n3));
     c->H = H; c->W = W; c->cur = 0;
     // work buffers that follow the input geometry
-    for (auto& p : c->inject) dfree(p);
+    for (auto& p : c->inject) p.reset();
     std::fill(c->inject_roi_zero.begin(), c->inject_roi_zero.end(), 0);
-    dfree(c->diffA); dfree(c->diffB); dfree(c->stmp); dfree16(c->diff16A); dfree16(c->diff16B);
+    c->diffA.reset(); c->diffB.reset(); c->stmp.reset(); c->diff16A.reset(); c->diff16B.reset();
     std::vector<int> C, h, w;
     shapes_for(c, H, W, C, h, w);
     c->max_blob = 0;
@@ -421,12 +394,7 @@ int ensure_input_buffers(st_ctx* c, int H, int W)
 
 int stage_upload(st_ctx* c, const void* host, size_t bytes)
 {
-    if (bytes > c->stage_cap) {
-        if (c->stage_dev) (void)hipFree(c->stage_dev);
-        c->stage_dev = nullptr;
-        HIP_TRY(hipMalloc(&c->stage_dev, bytes));
-        c->stage_cap = bytes;
-    }
+    ST_TRY(c->stage_dev.reserve(bytes));
     HIP_TRY(hipMemcpyAsync(c->stage_dev, host, bytes, hipMemcpyHostToDevice, c->stream));
     return ST_OK;
 }
@@ -437,8 +405,8 @@ int preprocess_into(st_ctx* c, const void* hwc, int H, int W, int is_u8, float* 
     const size_t n = (size_t)H * W * 3;
     ST_TRY(stage_upload(c, hwc, n * (is_u8 ? 1 : 4)));
     ProfScope ps(c, P_MISC, 0, 0);
-    if (is_u8) HIP_TRY(launch_preprocess_u8((const uint8_t*)c->stage_dev, dst, H, W, c->stream));
-    else HIP_TRY(launch_preprocess_f32((const float*)c->stage_dev, dst, H, W, c->stream));
+    if (is_u8) HIP_TRY(launch_preprocess_u8(c->stage_dev, dst, H, W, c->stream));
+    else HIP_TRY(launch_preprocess_f32((const float*)c->stage_dev.get(), dst, H, W, c->stream));
     return ST_OK;
 }
 
@@ -473,14 +441,14 @@ int content_from_device(st_ctx* c, const float* xdev, int H, int W)
     for (const ActiveLayer& al : c->active) if (al.c) { used[al.blob] = 1; deepest = std::max(deepest, al.blob); }
     if (deepest > 0) ST_TRY(forward_range(c, c->act, xdev, deepest));
     for (int i = 0; i < c->nb; ++i) {
-        if (!used[i]) { dfree(c->content_feat[i]); continue; }
+        if (!used[i]) { c->content_feat[i].reset(); continue; }
         const size_t n = (size_t)c->act.C[i] * c->act.h[i] * c->act.w[i];
-        if (c->cH != H || c->cW != W || !c->content_feat[i]) { dfree(c->content_feat[i]); ST_TRY(dmalloc(&c->content_feat[i], n)); }
+        if (c->cH != H || c->cW != W || !c->content_feat[i]) ST_TRY(c->content_feat[i].alloc(n));
         HIP_TRY(hipMemcpyAsync(c->content_feat[i], i == 0 ? xdev : c->act.data[i], n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     }
     c->act.valid_to = -1;
     if (xdev != c->content_x) {                 // keep the preprocessed image itself (== blob "data")
-        if (c->cH != H || c->cW != W || !c->content_x) { dfree(c->content_x); ST_TRY(dmalloc(&c->content_x, (size_t)3 * H * W)); }
+        if (c->cH != H || c->cW != W || !c->content_x) ST_TRY(c->content_x.alloc((size_t)3 * H * W));
         HIP_TRY(hipMemcpyAsync(c->content_x, xdev, (size_t)3 * H * W * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     }
     c->cH = H; c->cW = W;
@@ -505,7 +473,7 @@ int ensure_content_features(st_ctx* c)
         const int b = al.blob;
         if (!al.c || c->content_feat[b]) continue;
         const size_t n = (size_t)c->act.C[b] * c->act.h[b] * c->act.w[b];
-        ST_TRY(dmalloc(&c->content_feat[b], n));
+        ST_TRY(c->content_feat[b].alloc(n));
         HIP_TRY(hipMemcpyAsync(c->content_feat[b], b == 0 ? c->content_x : c->act.data[b], n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     }
     c->act.valid_to = -1;                      // (the activations are the content image's now)
@@ -526,7 +494,7 @@ int st_create(st_ctx** out, int device_id, const st_layer_desc* layers, int n_la
     if (ndev <= 0) return fail(ST_ERR_HIP, "no HIP device visible");
     if (device_id < 0 || device_id >= ndev) return fail(ST_ERR_ARG, "device %d out of range (%d visible)", device_id, ndev);
     HIP_TRY(hipSetDevice(device_id));
-    st_ctx* c = new st_ctx();
+    std::unique_ptr<st_ctx, int (*)(st_ctx*)> c(new st_ctx(), st_destroy);      // every early return tears down what exists so far
     c->device = device_id;
     c->wino = env_int("ST2_WINO", c->wino) != 0;
     c->graphs = env_int("ST2_GRAPH", c->graphs) != 0;
@@ -534,52 +502,50 @@ int st_create(st_ctx** out, int device_id, const st_layer_desc* layers, int n_la
     if (n_layers <= 0) {
         for (const auto& l : kVgg19) {
             Layer L; L.is_conv = l.kind == 0; L.name = l.name; L.cin = l.cin; L.cout = l.cout;
-            c->topo.push_back(L);
+            c->topo.push_back(std::move(L));
         }
     } else {
         int cprev = 3;
         for (int i = 0; i < n_layers; ++i) {
             const int kind = layers[i].kind;
-            if (kind != ST_LAYER_CONV && kind != ST_LAYER_POOL && kind != ST_LAYER_AVEPOOL) {
-                delete c; return fail(ST_ERR_ARG, "layer %d (%s): unknown kind %d", i, layers[i].name ? layers[i].name : "", kind);
-            }
+            if (kind != ST_LAYER_CONV && kind != ST_LAYER_POOL && kind != ST_LAYER_AVEPOOL)
+                return fail(ST_ERR_ARG, "layer %d (%s): unknown kind %d", i, layers[i].name ? layers[i].name : "", kind);
             Layer L; L.is_conv = kind == ST_LAYER_CONV; L.ave = kind == ST_LAYER_AVEPOOL; L.name = layers[i].name ? layers[i].name : "";
             if (L.is_conv) {
                 L.cin = layers[i].cin; L.cout = layers[i].cout;
-                if (L.cin != cprev || L.cout <= 0) { delete c; return fail(ST_ERR_ARG, "layer %s: cin %d does not follow %d", L.name.c_str(), L.cin, cprev); }
+                if (L.cin != cprev || L.cout <= 0) return fail(ST_ERR_ARG, "layer %s: cin %d does not follow %d", L.name.c_str(), L.cin, cprev);
                 cprev = L.cout;
             }
-            c->topo.push_back(L);
+            c->topo.push_back(std::move(L));
         }
     }
-    if ((int)c->topo.size() + 1 > kMaxTraceLayers) { delete c; return fail(ST_ERR_ARG, "too many layers"); }
+    if ((int)c->topo.size() + 1 > kMaxTraceLayers) return fail(ST_ERR_ARG, "too many layers");
     c->blob_names.push_back("data");
     for (const Layer& L : c->topo) c->blob_names.push_back(L.name);
     c->nb = (int)c->blob_names.size();
     HIP_TRY(hipStreamCreate(&c->stream));
-    c->content_feat.assign(c->nb, nullptr);
-    c->style_gram.assign(c->nb, nullptr);
+    c->content_feat.resize(c->nb);
+    c->style_gram.resize(c->nb);
     c->style_valid.assign(c->nb, 0);
-    c->inject.assign(c->nb, nullptr);
+    c->inject.resize(c->nb);
     c->inject_roi_zero.assign(c->nb, 0);
-    c->layer_part.assign(c->nb, nullptr);
-    c->s2_part.assign(c->nb, nullptr);
-    c->sfuse_w.assign(c->nb, nullptr); c->sfuse_cap.assign(c->nb, 0);
-    c->s2_cap.assign(c->nb, 0);
+    c->layer_part.resize(c->nb);
+    c->s2_part.resize(c->nb);
+    c->sfuse_w.resize(c->nb);
     c->cnt.assign(c->nb * 6, 0);
     c->norm_valid.assign(c->nb * 3, 0);
-    ST_TRY(dmalloc(&c->norms, c->nb * 3));
-    ST_TRY(dmalloc(&c->image_part, 6 * kMaxPartials));
-    ST_TRY(dmalloc(&c->trace_dev, kMaxTraceLayers * 6 + 8));
-    HIP_TRY(hipMalloc((void**)&c->trace_sums, (kMaxTraceLayers * kLayerSlots + kImageSlots) * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&c->lb_dev, sizeof(LbfgsDev)));
+    ST_TRY(c->norms.alloc(c->nb * 3));
+    ST_TRY(c->image_part.alloc(6 * kMaxPartials));
+    ST_TRY(c->trace_dev.alloc(kMaxTraceLayers * 6 + 8));
+    ST_TRY(c->trace_sums.alloc(kMaxTraceLayers * kLayerSlots + kImageSlots));
+    ST_TRY(c->lb_dev.alloc(1));
     HIP_TRY(hipMemset(c->lb_dev, 0, sizeof(LbfgsDev)));
-    ST_TRY(dmalloc(&c->lb_part, 4 * kMaxPartials));
-    HIP_TRY(hipHostMalloc((void**)&c->trace_host, (kMaxTraceLayers * 6 + 8) * sizeof(float), 0));
+    ST_TRY(c->lb_part.alloc(4 * kMaxPartials));
+    ST_TRY(c->trace_host.alloc(kMaxTraceLayers * 6 + 8));
     // worker.py:129-133: all-ones weights over every blob until SetWeights arrives
     for (int b = 0; b < c->nb; ++b) c->rows.push_back(ActiveLayer{b, 1.f, 1.f, 1.f, true, true, true});
     c->active = c->rows;
-    *out = c;
+    *out = c.release();
     return ST_OK;
 }
 
@@ -587,48 +553,20 @@ int st_destroy(st_ctx* c)
 {
     if (!c) return ST_OK;
     (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    for (int i = 0; i < 2; ++i) if (c->gexec[i]) { (void)hipGraphExecDestroy(c->gexec[i]); c->gexec[i] = nullptr; }
-    dfree(c->adam_dyn);
-    for (Layer& L : c->topo) { dfree(L.w_fwd); dfree(L.w_bwd); dfree(L.w_raw); dfree(L.w_raw_r); dfree(L.bias); dfree16(L.w16_fwd); dfree16(L.w16_bwd); dfree16(L.w_split); dfree(L.u_fwd); dfree(L.u_bwd); dfree16(L.us_fwd); dfree16(L.us_bwd); }
-    dfree16(c->diff16A); dfree16(c->diff16B);
-    act_free(c->act);
-    for (int i = 0; i < 2; ++i) dfree(c->x[i]);
-    dfree(c->fwd_x);
-    dfree(c->grad); dfree(c->m); dfree(c->v); dfree(c->g_cur); dfree(c->pvec);
-    for (int i = 0; i <= st_ctx::kCorr; ++i) { dfree(c->hs[i]); dfree(c->hy[i]); }
-    for (auto& p : c->content_feat) dfree(p);
-    dfree(c->content_x);
-    for (auto& p : c->style_gram) dfree(p);
-    for (auto& p : c->inject) dfree(p);
-    for (auto& p : c->layer_part) dfree(p);
-    for (auto& p : c->s2_part) dfree(p);
-    for (auto& p : c->sfuse_w) dfree16(p);
-    dfree(c->diffA); dfree(c->diffB); dfree(c->stmp); dfree(c->gram_slabs); dfree(c->gram_fold); dfree(c->dbuf); dfree16(c->d16); dfree16(c->dsplit); dfree(c->conv_scratch);
-    comm_free(c);
-    dfree(c->tile.p1); dfree(c->tile.p2); dfree(c->tile.p3); dfree(c->tile.pd); dfree(c->tile.wgrad); dfree(c->tile.lb_x); dfree(c->tile.lb_sums); dfree(c->tile.sp);
-    dfree(c->norms); dfree(c->image_part); dfree(c->trace_dev); dfree(c->lb_part); dfree(c->hwc_dev);
-    if (c->lb_dev) (void)hipFree(c->lb_dev);
-    if (c->lb_gram) (void)hipFree(c->lb_gram);
-    dfree(c->lb_gpart); dfree(c->lb_dots);
-    if (c->stage_dev) (void)hipFree(c->stage_dev);
-    if (c->trace_sums) (void)hipFree(c->trace_sums);
-    if (c->trace_host) (void)hipHostFree(c->trace_host);
-    if (c->pipe.copy) {
-        (void)hipStreamSynchronize(c->pipe.copy);
-        for (int i = 0; i < st_ctx::Pipe::kSlots; ++i) {
-            dfree(c->pipe.hwc[i]);
-            if (c->pipe.pin_base[i]) (void)hipHostFree(c->pipe.pin_base[i]);
-            if (c->pipe.trace_pin[i]) (void)hipHostFree(c->pipe.trace_pin[i]);
-            if (c->pipe.ready[i]) (void)hipEventDestroy(c->pipe.ready[i]);
-            if (c->pipe.done[i]) (void)hipEventDestroy(c->pipe.done[i]);
-        }
-        for (auto& r : c->pipe.retired) (void)hipHostFree(r.p);
-        (void)hipStreamDestroy(c->pipe.copy);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);      // (null: st_create failed before it had a stream; nothing ran)
+    if (c->pipe.copy) (void)hipStreamSynchronize(c->pipe.copy);
+    for (int i = 0; i < 2; ++i) if (c->gexec[i]) (void)hipGraphExecDestroy(c->gexec[i]);
+    for (int i = 0; i < st_ctx::Pipe::kSlots; ++i) {
+        if (c->pipe.ready[i]) (void)hipEventDestroy(c->pipe.ready[i]);
+        if (c->pipe.done[i]) (void)hipEventDestroy(c->pipe.done[i]);
     }
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
-    (void)hipStreamDestroy(c->stream);
+    comm_free(c);
+    // the buffers go with the context, BEFORE the streams they were used on
+    const hipStream_t stream = c->stream, copy = c->pipe.copy;
     delete c;
+    if (copy) (void)hipStreamDestroy(copy);
+    if (stream) (void)hipStreamDestroy(stream);
     return ST_OK;
 }
 
@@ -637,12 +575,12 @@ static int make_split_packs(Layer& L, const float* w)
 {
     for (int dir = 0; dir < 2; ++dir) {
         const int K = dir ? L.cout : L.cin, M = dir ? L.cin : L.cout;
-        unsigned short** dst = dir ? &L.us_bwd : &L.us_fwd;
-        if (*dst || !wino_split_resolve(K, M, 4, 4).ok) continue;
+        DevBuf<unsigned short>& dst = dir ? L.us_bwd : L.us_fwd;
+        if (dst || !wino_split_resolve(K, M, 4, 4).ok) continue;
         std::vector<unsigned short> hu(wino_split_pack_elems(K, M), 0);
         if (dir) pack_wino_split_weights_dgrad(w, L.cout, L.cin, hu.data()); else pack_wino_split_weights_fwd(w, L.cout, L.cin, hu.data());
-        ST_TRY(dmalloc16(dst, hu.size()));
-        HIP_TRY(hipMemcpy(*dst, hu.data(), hu.size() * 2, hipMemcpyHostToDevice));
+        ST_TRY(dst.alloc(hu.size()));
+        HIP_TRY(hipMemcpy(dst, hu.data(), hu.size() * 2, hipMemcpyHostToDevice));
     }
     return ST_OK;
 }
@@ -659,33 +597,36 @@ int st_load_conv_weights(st_ctx* c, const char* layer, const float* w, const flo
         pack_conv_weights_fwd(w, L.cout, L.cin, pf.data());
         pack_conv_weights_dgrad(w, L.cout, L.cin, pb.data());
         if (bias) memcpy(bp.data(), bias, L.cout * sizeof(float));
-        dfree(L.w_fwd); dfree(L.w_bwd); dfree(L.w_raw); dfree(L.w_raw_r); dfree(L.bias); dfree16(L.w16_fwd); dfree16(L.w16_bwd); dfree16(L.w_split); dfree(L.u_fwd); dfree(L.u_bwd); dfree16(L.us_fwd); dfree16(L.us_bwd);
+        // the old packs go first (a reload peaks at one set); until the new ones are complete the layer counts as never loaded, so
+        // that a reload that fails half-way leaves a layer forward_range refuses, not one with null packs
+        L.loaded = false;
+        static_cast<LayerPacks&>(L) = LayerPacks{};       // move-assigns twelve empty buffers: frees every pack, leaves name / cin / cout
         for (int dir = 0; dir < 2; ++dir) {   // Winograd packs for the directions the Winograd kernel can take (any image size)
             const int K = dir ? L.cout : L.cin, M = dir ? L.cin : L.cout;
             if (!wino_resolve(K, M, 4, 4).ok) continue;
             std::vector<float> hu(wino_pack_floats(K, M));
             if (dir) pack_wino_weights_dgrad(w, L.cout, L.cin, hu.data()); else pack_wino_weights_fwd(w, L.cout, L.cin, hu.data());
-            float** dst = dir ? &L.u_bwd : &L.u_fwd;
-            ST_TRY(dmalloc(dst, hu.size()));
-            HIP_TRY(hipMemcpy(*dst, hu.data(), hu.size() * sizeof(float), hipMemcpyHostToDevice));
+            DevBuf<float>& dst = dir ? L.u_bwd : L.u_fwd;
+            ST_TRY(dst.alloc(hu.size()));
+            HIP_TRY(hipMemcpy(dst, hu.data(), hu.size() * sizeof(float), hipMemcpyHostToDevice));
         }
         {   // bf16 packs for the bf16 feature path
             const size_t n16f = conv16_pack_elems(L.cin, L.cout), n16b = conv16_pack_elems(L.cout, L.cin);
             std::vector<unsigned short> hf(n16f), hb(n16b);
             pack_conv_weights16_fwd(w, L.cout, L.cin, hf.data());
             pack_conv_weights16_dgrad(w, L.cout, L.cin, hb.data());
-            ST_TRY(dmalloc16(&L.w16_fwd, n16f)); ST_TRY(dmalloc16(&L.w16_bwd, n16b));
+            ST_TRY(L.w16_fwd.alloc(n16f)); ST_TRY(L.w16_bwd.alloc(n16b));
             HIP_TRY(hipMemcpy(L.w16_fwd, hf.data(), n16f * 2, hipMemcpyHostToDevice));
             HIP_TRY(hipMemcpy(L.w16_bwd, hb.data(), n16b * 2, hipMemcpyHostToDevice));
         }
         if (L.cin == 3 && L.cout % 32 == 0) {   // first layer on the bf16 path: split weights for conv3x3_first_split.hip
             std::vector<unsigned short> hs(conv_first_split_pack_elems(L.cout));
             pack_conv_first_split(w, bias, L.cout, L.cin, hs.data());
-            ST_TRY(dmalloc16(&L.w_split, hs.size()));
+            ST_TRY(L.w_split.alloc(hs.size()));
             HIP_TRY(hipMemcpy(L.w_split, hs.data(), hs.size() * 2, hipMemcpyHostToDevice));
         }
-        ST_TRY(dmalloc(&L.w_fwd, nf)); ST_TRY(dmalloc(&L.w_bwd, nb));
-        ST_TRY(dmalloc(&L.w_raw, (size_t)L.cout * L.cin * 9)); ST_TRY(dmalloc(&L.bias, bp.size()));
+        ST_TRY(L.w_fwd.alloc(nf)); ST_TRY(L.w_bwd.alloc(nb));
+        ST_TRY(L.w_raw.alloc((size_t)L.cout * L.cin * 9)); ST_TRY(L.bias.alloc(bp.size()));
         HIP_TRY(hipMemcpy(L.w_fwd, pf.data(), nf * sizeof(float), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(L.w_bwd, pb.data(), nb * sizeof(float), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(L.w_raw, w, (size_t)L.cout * L.cin * 9 * sizeof(float), hipMemcpyHostToDevice));
@@ -696,7 +637,7 @@ int st_load_conv_weights(st_ctx* c, const char* layer, const float* w, const flo
                 u = (u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u;          // round to nearest even (weights are finite)
                 memcpy(&wr[k], &u, 4);
             }
-            ST_TRY(dmalloc(&L.w_raw_r, wr.size()));
+            ST_TRY(L.w_raw_r.alloc(wr.size()));
             HIP_TRY(hipMemcpy(L.w_raw_r, wr.data(), wr.size() * sizeof(float), hipMemcpyHostToDevice));
         }
         HIP_TRY(hipMemcpy(L.bias, bp.data(), bp.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -735,13 +676,12 @@ int st_set_gram_algo(st_ctx* c, int algo)
         shapes_for(c, 16, 16, C, h, w);
         size_t need = 0;
         for (int i = 0; i < c->nb; ++i) if (style_grad_split_ok(C[i], 4)) need = std::max(need, style_grad_split_pack_elems(C[i]));
-        if (need > c->dsplit_cap) {
+        if (need > c->dsplit.cap()) {      // the new buffer exists before the old one is given up
             HIP_TRY(hipSetDevice(c->device));
-            unsigned short* p = nullptr;
-            ST_TRY(dmalloc16(&p, need));
+            DevBuf<unsigned short> p;
+            ST_TRY(p.alloc(need));
             HIP_TRY(hipStreamSynchronize(c->stream));
-            dfree16(c->dsplit);
-            c->dsplit = p; c->dsplit_cap = need;
+            c->dsplit = std::move(p);
         }
     }
     c->epoch++;                // anything but st_step may change what a step launches: captured step graphs are stale
@@ -811,7 +751,7 @@ int st_forward(st_ctx* c, const float* x_nchw, int H, int W, int last_blob)
     ST_TRY(set_input_common(c, H, W));
     ST_TRY(act_ensure(c, c->act, H, W));
     const size_t n3 = (size_t)3 * H * W;
-    if (n3 > c->fwd_x_cap) { dfree(c->fwd_x); c->fwd_x_cap = 0; ST_TRY(dmalloc(&c->fwd_x, n3)); c->fwd_x_cap = n3; }
+    ST_TRY(c->fwd_x.reserve(n3));
     HIP_TRY(hipMemcpyAsync(c->fwd_x, x_nchw, n3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if (last_blob < 0 || last_blob >= c->nb) last_blob = c->nb - 1;
     ST_TRY(forward_range(c, c->act, c->fwd_x, last_blob));
@@ -842,14 +782,14 @@ int st_backward(st_ctx* c, int n, const int* blob_index, const float* const* dif
         const int b = blob_index[i];
         if (b < 0 || b > c->act.valid_to) return fail(ST_ERR_ARG, "diff for blob %d which the last forward did not reach", b);
         const size_t nb = (size_t)c->act.C[b] * c->act.h[b] * c->act.w[b];
-        if (!c->inject[b]) ST_TRY(dmalloc(&c->inject[b], nb));
+        if (!c->inject[b]) ST_TRY(c->inject[b].alloc(nb));
         HIP_TRY(hipMemcpyAsync(c->inject[b], diffs[i], nb * sizeof(float), hipMemcpyHostToDevice, c->stream));
         c->inject_roi_zero[b] = 0;
         inj[b] = c->inject[b];
         top = std::max(top, b);
     }
     if (top < 0) { memset(out_grad, 0, n3 * sizeof(float)); return ST_OK; }
-    if (!c->diffA) { ST_TRY(dmalloc(&c->diffA, c->max_blob)); ST_TRY(dmalloc(&c->diffB, c->max_blob)); }
+    if (!c->diffA) { ST_TRY(c->diffA.alloc(c->max_blob)); ST_TRY(c->diffB.alloc(c->max_blob)); }
     const float* g = inj[0];
     if (top > 0) ST_TRY(backward_chain(c, top, inj[top], inj, &g));
     HIP_TRY(hipMemcpyAsync(out_grad, g, n3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -866,15 +806,14 @@ int st_gram(st_ctx* c, int index, float* out)
     if (!c->act.plan.fwd[index].out32) return fail(ST_ERR_STATE, "blob %d (%s) is not materialised in fp32 by the lean evaluation of an iteration: no Gram of it (st_opfunc / st_forward write every fp32 blob; bf16: st_set_precision(ctx, 2))", index, c->blob_names[index].c_str());
     HIP_TRY(hipSetDevice(c->device));
     const int C = c->act.C[index], hw = c->act.h[index] * c->act.w[index];
-    float* g = nullptr;
-    ST_TRY(dmalloc(&g, (size_t)C * C));
+    DevBuf<float> g;
+    ST_TRY(g.alloc((size_t)C * C));
     int r = gram_into(c, c->act.data[index], C, hw, nullptr, g, C, nullptr, nullptr);
     if (r == ST_OK) {
         hipError_t e = hipMemcpyAsync(out, g, (size_t)C * C * sizeof(float), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) r = fail(ST_ERR_HIP, "gram copy: %s", hipGetErrorString(e));
     }
-    dfree(g);
     return r;
 }
 
@@ -923,12 +862,11 @@ int st_set_content(st_ctx* c, const void* hwc, int H, int W, int is_u8)
     if (c) c->epoch++;       // anything but st_step may change what a step launches: captured step graphs are stale
     if (!c) return fail(ST_ERR_ARG, "ctx is NULL");
     HIP_TRY(hipSetDevice(c->device));
-    float* tmp = nullptr;
-    ST_TRY(dmalloc(&tmp, (size_t)3 * H * W));
+    DevBuf<float> tmp;
+    ST_TRY(tmp.alloc((size_t)3 * H * W));
     int r = preprocess_into(c, hwc, H, W, is_u8, tmp);
     if (r == ST_OK) r = content_from_device(c, tmp, H, W);
-    (void)hipStreamSynchronize(c->stream);
-    dfree(tmp);
+    (void)hipStreamSynchronize(c->stream);       // (before tmp goes)
     return r;
 }
 
@@ -937,13 +875,12 @@ int st_set_content_nchw(st_ctx* c, const float* x, int H, int W)
     if (c) c->epoch++;       // anything but st_step may change what a step launches: captured step graphs are stale
     if (!c || !x || H <= 0 || W <= 0) return fail(ST_ERR_ARG, "bad argument");
     HIP_TRY(hipSetDevice(c->device));
-    float* tmp = nullptr;
-    ST_TRY(dmalloc(&tmp, (size_t)3 * H * W));
+    DevBuf<float> tmp;
+    ST_TRY(tmp.alloc((size_t)3 * H * W));
     int r = ST_OK;
     if (hipMemcpy(tmp, x, (size_t)3 * H * W * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) r = fail(ST_ERR_HIP, "content upload failed");
     if (r == ST_OK) r = content_from_device(c, tmp, H, W);
-    (void)hipStreamSynchronize(c->stream);
-    dfree(tmp);
+    (void)hipStreamSynchronize(c->stream);       // (before tmp goes)
     return r;
 }
 
@@ -952,9 +889,9 @@ int st_set_style(st_ctx* c, const void* hwc, int H, int W, int is_u8)
     if (c) c->epoch++;       // anything but st_step may change what a step launches: captured step graphs are stale
     if (!c) return fail(ST_ERR_ARG, "ctx is NULL");
     HIP_TRY(hipSetDevice(c->device));
-    float* tmp = nullptr;
-    ST_TRY(dmalloc(&tmp, (size_t)3 * H * W));
-    ActSet aux;
+    DevBuf<float> tmp;
+    ST_TRY(tmp.alloc((size_t)3 * H * W));
+    ActSet aux;                // (freed on return, after the synchronisation below)
     ActSet* a = &aux;
     const bool same = c->act.H == H && c->act.W == W && !c->act.data.empty();
     if (same) a = &c->act;
@@ -963,13 +900,11 @@ int st_set_style(st_ctx* c, const void* hwc, int H, int W, int is_u8)
     if (r == ST_OK) r = forward_range(c, *a, tmp, c->nb - 1);
     for (int i = 0; i < c->nb && r == ST_OK; ++i) {
         const int C = a->C[i], hw = a->h[i] * a->w[i];
-        if (!c->style_gram[i]) r = dmalloc(&c->style_gram[i], (size_t)C * C);
+        if (!c->style_gram[i]) r = c->style_gram[i].alloc((size_t)C * C);
         if (r == ST_OK) r = gram_into(c, a->data[i], C, hw, nullptr, c->style_gram[i], C, nullptr, nullptr);
     }
     (void)hipStreamSynchronize(c->stream);
-    if (!same) act_free(aux);
-    else c->act.valid_to = -1;
-    dfree(tmp);
+    if (same) c->act.valid_to = -1;
     if (r == ST_OK) { c->have_style = true; std::fill(c->style_valid.begin(), c->style_valid.end(), 1); }
     return r;
 }
@@ -1009,6 +944,14 @@ int st_profile_read(st_ctx* c, long long* launches, double* ms, double* flops, d
     }
     c->prof.clear();
     c->ev_used = 0;
+    return ST_OK;
+}
+
+// ---- test hook: what the funnel holds, over every context of the process
+int st_live_bytes(long long* device, long long* pinned)
+{
+    if (device) *device = g_live_dev.load();
+    if (pinned) *pinned = g_live_pin.load();
     return ST_OK;
 }
 

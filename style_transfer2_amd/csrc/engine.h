@@ -4,6 +4,7 @@
 #include "../../include/st2.h"
 #include "st2_kernels.h"
 #include "env.h"
+#include "devbuf.h"
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -42,16 +43,18 @@ extern const char* const kProfNames[P_COUNT];
 struct ProfRec { int cls; hipEvent_t a, b; double flops, bytes; };
 
 // ------------------------------------------------------------------------------------------- types
-struct Layer {
+struct LayerPacks {                // the device copies of one conv layer's weights
+    DevBuf<float> w_fwd, w_bwd, w_raw, w_raw_r, bias;            // w_raw_r: w_raw rounded to bf16 values
+    DevBuf<unsigned short> w16_fwd, w16_bwd;                     // bf16 packs (bf16 feature path)
+    DevBuf<unsigned short> w_split;                              // first layer, bf16 path: three-way bf16 split of the weights (conv3x3_first_split.hip)
+    DevBuf<float> u_fwd, u_bwd;                                  // Winograd F(2x2,3x3) packs (null: not eligible)
+    DevBuf<unsigned short> us_fwd, us_bwd;                       // split-operand Winograd packs (conv3x3_wino_split.hip; made when st_set_conv_algo(ctx, 2) asks for them)
+};
+struct Layer : LayerPacks {
     bool is_conv = false;
     bool ave = false;                                            // pool layer: average (ST_LAYER_AVEPOOL) instead of max pooling
     std::string name;
     int cin = 0, cout = 0;
-    float *w_fwd = nullptr, *w_bwd = nullptr, *w_raw = nullptr, *w_raw_r = nullptr, *bias = nullptr;   // w_raw_r: w_raw rounded to bf16 values
-    unsigned short *w16_fwd = nullptr, *w16_bwd = nullptr;       // bf16 packs (bf16 feature path)
-    unsigned short* w_split = nullptr;                           // first layer, bf16 path: three-way bf16 split of the weights (conv3x3_first_split.hip)
-    float *u_fwd = nullptr, *u_bwd = nullptr;                    // Winograd F(2x2,3x3) packs (null: not eligible)
-    unsigned short *us_fwd = nullptr, *us_bwd = nullptr;         // split-operand Winograd packs (conv3x3_wino_split.hip; made when st_set_conv_algo(ctx, 2) asks for them)
     bool loaded = false;
 };
 
@@ -93,10 +96,11 @@ struct RoutePlan { std::vector<FwdRoute> fwd; std::vector<BwdRoute> bwd; };
 struct ActSet {                    // activations of one forward geometry
     int H = 0, W = 0;
     std::vector<int> C, h, w;
-    std::vector<float*> data;      // data[0] is borrowed (the image itself)
-    std::vector<unsigned short*> data16;   // bf16 channel-blocked copies of the blobs that feed a bf16 conv
-    std::vector<unsigned char*> amap;      // arg-max maps of the pools fused into the producing conv
-    std::vector<unsigned short*> bits;     // bf16 lean flow: sign map of a conv blob that feeds a bf16 conv (Conv16Problem::bits_out)
+    std::vector<DevBuf<float>> own;        // the fp32 blobs 1 .. nb - 1; sized and filled by act_ensure ONLY (data[] points into it)
+    std::vector<float*> data;              // views: data[i] == own[i] for i >= 1, data[0] is borrowed (the image itself)
+    std::vector<DevBuf<unsigned short>> data16;   // bf16 channel-blocked copies of the blobs that feed a bf16 conv
+    std::vector<DevBuf<unsigned char>> amap;      // arg-max maps of the pools fused into the producing conv
+    std::vector<DevBuf<unsigned short>> bits;     // bf16 lean flow: sign map of a conv blob that feeds a bf16 conv (Conv16Problem::bits_out)
     RoutePlan plan;                        // of the last forward_range / backward_chain on these activations: which of the buffers above it wrote
     int valid_to = -1;
 };
@@ -121,8 +125,8 @@ struct st_ctx {
     bool wino_split = false;                       // ... on the bf16 matrix cores with three-way split operands where the shape allows (st_set_conv_algo(ctx, 2))
     int pool_algo = 0;                             // 1: an average pool rides on the bf16 conv launches around it in the lean flow (st_set_pool_algo)
     bool gram_split = false;                       // fp32 features: Gram partials and style gradients on the bf16 matrix cores with three-way split operands where the shape allows (st_set_gram_algo(ctx, 1))
-    unsigned short* dsplit = nullptr; size_t dsplit_cap = 0;      // ... and the three-term operand image of D (gram_split.hip), sized for the widest blob when the option is set
-    unsigned short *diff16A = nullptr, *diff16B = nullptr;
+    DevBuf<unsigned short> dsplit;                 // ... and the three-term operand image of D (gram_split.hip), sized for the widest blob when the option is set
+    DevBuf<unsigned short> diff16A, diff16B;
     std::vector<Layer> topo;
     std::vector<std::string> blob_names;
     int nb = 0;                                    // number of blobs (= layers + 1)
@@ -130,57 +134,55 @@ struct st_ctx {
     ActSet act;                                    // geometry of input/content
     // image state
     int H = 0, W = 0;                              // input geometry (0 = no input)
-    float* x[2] = {nullptr, nullptr};
+    DevBuf<float> x[2];
     int cur = 0;
-    float* fwd_x = nullptr; size_t fwd_x_cap = 0;   // image of the st_forward test hook (never the job's iterate)
-    float* grad = nullptr;                         // combined gradient (opfunc / L-BFGS)
+    DevBuf<float> fwd_x;                           // image of the st_forward test hook (never the job's iterate)
+    DevBuf<float> grad;                            // combined gradient (opfunc / L-BFGS)
     // content / style
     int cH = 0, cW = 0;
-    std::vector<float*> content_feat;              // per blob
-    float* content_x = nullptr;                    // preprocessed content image (for resample_content)
-    std::vector<float*> style_gram;                // per blob, C*C
+    std::vector<DevBuf<float>> content_feat;        // per blob
+    DevBuf<float> content_x;                       // preprocessed content image (for resample_content)
+    std::vector<DevBuf<float>> style_gram;          // per blob, C*C
     std::vector<char> style_valid;                 // per blob: style_gram holds a target (st_set_style: every blob; st_tile_style_commit: 0 .. last_blob)
     bool have_content = false, have_style = false;
     // objective
     std::vector<ActiveLayer> rows;                 // every row of the weights table, in order
     std::vector<ActiveLayer> active;               // rows with any non-zero weight
     float tv_w = 1, tv_pow = 1, p_w = 1, p_pow = 1;   // worker.py:133 defaults
-    float* norms = nullptr;                        // [nb][3] on device
+    DevBuf<float> norms;                           // [nb][3] on device
     std::vector<char> norm_valid;                  // [nb*3]
     // work buffers (input geometry)
-    std::vector<float*> inject;
+    std::vector<DevBuf<float>> inject;
     std::vector<char> inject_roi_zero;             // per blob: the inject buffer is zero outside the tile's region of interest (tile-sharded bf16 style term)
-    float *diffA = nullptr, *diffB = nullptr, *stmp = nullptr;
+    DevBuf<float> diffA, diffB, stmp;
     size_t max_blob = 0;
-    float *gram_slabs = nullptr, *gram_fold = nullptr, *dbuf = nullptr;
-    unsigned short* d16 = nullptr; size_t d16_cap = 0;            // bf16 path: hi/lo operand image of D (style16.hip)
+    DevBuf<float> gram_slabs, gram_fold, dbuf;
+    DevBuf<unsigned short> d16;                    // bf16 path: hi/lo operand image of D (style16.hip)
     // bf16 path, style term fused into the data-gradient conv above the style blob: per blob the scaled hi/lo image of D (kept until
     // that conv has run) and, during one objective evaluation, the operands handed to backward_chain
-    std::vector<unsigned short*> sfuse_w; std::vector<size_t> sfuse_cap;
+    std::vector<DevBuf<unsigned short>> sfuse_w;
     std::vector<const unsigned short*> sf_in, sf_w;
-    float* conv_scratch = nullptr; size_t conv_scratch_cap = 0;       // split-K partial sums of Winograd launches
+    DevBuf<float> conv_scratch;                    // split-K partial sums of Winograd launches
     // hipGraph replay of the steady-state Adam step (launch-bound regime: small images)
     unsigned long long epoch = 0;                  // bumped by every API call that can change what a step launches
     hipGraphExec_t gexec[2] = {nullptr, nullptr};  // one per parity of the x ping-pong
     unsigned long long gepoch[2] = {0, 0};
-    float* adam_dyn = nullptr;                     // device {corr1, corr2, step}: the only per-step arguments
+    DevBuf<float> adam_dyn;                        // device {corr1, corr2, step}: the only per-step arguments
     bool capturing = false, graphs = false;        // opt-in (ST2_GRAPH=1): measured, no gain -- see step_graph_ok()
     int plain_steps = 0;                           // normal steps since the last epoch change (buffers are allocated lazily)
     unsigned long long plain_epoch = ~0ull;
     size_t graph_max_px = 768 * 768;
     long long graph_replays = 0;
-    size_t gram_slab_cap = 0, gram_fold_cap = 0;
-    std::vector<float*> layer_part;                // per blob: 5 * kMaxPartials
-    std::vector<float*> s2_part;                   // per blob: style-grad partial sums
-    std::vector<int> s2_cap;
+    std::vector<DevBuf<float>> layer_part;          // per blob: 5 * kMaxPartials
+    std::vector<DevBuf<float>> s2_part;             // per blob: style-grad partial sums
     std::vector<int> cnt;                          // per blob * 6 partial counts
-    float* image_part = nullptr;                   // 6 * kMaxPartials
+    DevBuf<float> image_part;                      // 6 * kMaxPartials
     int image_cnt = 0;
-    float* trace_dev = nullptr;
-    double* trace_sums = nullptr;                  // device scratch of the trace finalisation
-    float* trace_host = nullptr;                   // pinned
+    DevBuf<float> trace_dev;
+    DevBuf<double> trace_sums;                     // device scratch of the trace finalisation
+    PinBuf<float> trace_host;
     int trace_len_last = 8;
-    float* hwc_dev = nullptr;
+    DevBuf<float> hwc_dev;
     // pipelined iterations (st_step_begin / st_step_end): up to two in flight; the iterate of step k travels to pinned host memory
     // on its own stream while step k + 1 computes
     struct Pipe {
@@ -188,8 +190,8 @@ struct st_ctx {
         // kSlots - 1 further begins, which is what lets the worker's sender thread pickle it without a host-side copy
         static constexpr int kSlots = 6;
         hipStream_t copy = nullptr;
-        float* hwc[kSlots] = {}; float* img_pin[kSlots] = {}; float* trace_pin[kSlots] = {};
-        char* pin_base[kSlots] = {};               // the pinned allocation of a slot: [head room | image | tail room]; img_pin points at the image
+        DevBuf<float> hwc[kSlots]; float* img_pin[kSlots] = {}; PinBuf<float> trace_pin[kSlots];
+        PinBuf<char> pin_base[kSlots];             // the pinned allocation of a slot: [head room | image | tail room]; img_pin points at the image
         hipEvent_t ready[kSlots] = {}, done[kSlots] = {};
         size_t cap = 0; long long head = 0; int count = 0, tlen[kSlots] = {}, H[kSlots] = {}, W[kSlots] = {};
         // bytes the caller may write in front of / behind an iterate handed out by st_step_end (a message frame around the image,
@@ -197,45 +199,44 @@ struct st_ctx {
         size_t want_head = 0, want_tail = 0, have_head = 0, have_tail = 0;
         // Buffers replaced by a re-allocation (the input grew, the frame room changed) stay alive until kSlots further begins have
         // passed: views handed out before it keep the documented lifetime.
-        struct Retired { void* p; long long at; };
+        struct Retired { PinBuf<char> buf; long long at; };
         std::vector<Retired> retired;
         long long begins = 0;
     } pipe;
-    void* stage_dev = nullptr; size_t stage_cap = 0;
+    DevBuf<unsigned char> stage_dev;               // host images on their way to preprocess_into
     // optimizer
     int opt_kind = ST_OPT_NONE;
     double step_size = 1.0;
-    float *m = nullptr, *v = nullptr;
+    DevBuf<float> m, v;
     int items1 = 0, items2 = 0;
     bool m_zero = true, v_zero = true;
     // L-BFGS
     static const int kCorr = kLbfgsCorr;
-    float* hs[kLbfgsSlots] = {nullptr};            // ring of s vectors (10 pairs + the one being formed)
-    float* hy[kLbfgsSlots] = {nullptr};
-    LbfgsDev* lb_dev = nullptr;                    // history bookkeeping (pair count, ring order, s.y, y.y): device-resident
+    DevBuf<float> hs[kLbfgsSlots];                 // ring of s vectors (10 pairs + the one being formed)
+    DevBuf<float> hy[kLbfgsSlots];
+    DevBuf<LbfgsDev> lb_dev;                       // history bookkeeping (pair count, ring order, s.y, y.y): device-resident
     bool lb_clear = true;                          // history to be emptied before the next step (reset / objective_changed)
-    float* lb_part = nullptr;                      // [4][kMaxPartials] partial sums of the chained dot products
-    LbfgsGram* lb_gram = nullptr;                  // Gram form (lbfgs.hip, second half): inner-product matrix + coefficients
-    float* lb_gpart = nullptr;                     // [kLbGramRows][kMaxPartials] partial sums of the inner-product pass
-    float* lb_dots = nullptr;                      // test hook: [kLbNB][kLbNB] pairwise inner products
+    DevBuf<float> lb_part;                         // [4][kMaxPartials] partial sums of the chained dot products
+    DevBuf<LbfgsGram> lb_gram;                     // Gram form (lbfgs.hip, second half): inner-product matrix + coefficients
+    DevBuf<float> lb_gpart;                        // [kLbGramRows][kMaxPartials] partial sums of the inner-product pass
+    DevBuf<float> lb_dots;                         // test hook: [kLbNB][kLbNB] pairwise inner products
     bool lb_gram_form = false;                     // form of the current history (decided while it is empty)
-    float* g_cur = nullptr; float* pvec = nullptr;
+    DevBuf<float> g_cur, pvec;
     bool have_cur = false;
     float last_loss = 0.f;
     // tile-sharded mode (BASELINE config 5): this context holds ONE window of a larger image
     struct Tile : TileGeom {
         bool on = false;
-        float *p1 = nullptr, *p2 = nullptr, *p3 = nullptr, *pd = nullptr;    // reduce buffers (device)
-        size_t p1_n = 0, p2_n = 0, p3_n = 0, pd_n = 0;
+        DevBuf<float> p1, p2, p3, pd;              // reduce buffers (device)
         bool s2_in_p2 = false;
-        float* wgrad = nullptr;                    // window gradient (3, wh, ww)
+        DevBuf<float> wgrad;                       // window gradient (3, wh, ww)
         bool fused = false;                        // inside st_tile_step: the phases do not synchronise the stream on their own
         // fused L-BFGS over the sharded image (engine_comm.cpp): this rank's tile of x as a compact (3, th, tw) vector, the sums of
         // one inner-product pass (all-reduced), and the global image size the unit-RMS first direction divides by
-        float* lb_x = nullptr; float* lb_sums = nullptr; size_t lb_n = 0;
+        DevBuf<float> lb_x, lb_sums;
         // the sharded style pass (st_tile_style_partials -> all-reduce -> st_tile_style_commit): raw Gram sums of blobs 0 .. sp_last over
         // this rank's tile of the sp_gH x sp_gW style image, back to back; sp_last < 0: no partials wait for a commit
-        float* sp = nullptr; size_t sp_cap = 0; int sp_n = 0, sp_last = -1, sp_gH = 0, sp_gW = 0;
+        DevBuf<float> sp; int sp_n = 0, sp_last = -1, sp_gH = 0, sp_gW = 0;
     } tile;
     // communicator of the tile-sharded mode (engine_comm.cpp): RCCL over xGMI, or caller-supplied transport functions (tests)
     struct Comm {
@@ -244,14 +245,14 @@ struct st_ctx {
         int rank = 0, world = 1;
         bool set = false;                          // st_comm_init / st_comm_callbacks has run (a fresh context looks like world 1 otherwise)
         st_allreduce_fn ar = nullptr; st_exchange_fn ex = nullptr; void* user = nullptr;
-        struct Peer { int peer = 0; std::vector<int> send, recv; float *sbuf = nullptr, *rbuf = nullptr; size_t sn = 0, rn = 0; };
+        struct Peer { int peer = 0; std::vector<int> send, recv; DevBuf<float> sbuf, rbuf; size_t sn = 0, rn = 0; };
         std::vector<Peer> plan[3];                 // per phase (ST_TILE_PLAN_*): the peers this rank exchanges strips with
         bool planned[3] = {false, false, false};
         bool self_via_rccl = false;                // test hook (ST2_COMM_SELF_VIA_RCCL=1): copies to the own rank travel through RCCL too
-        float* ring = nullptr; size_t ring_cap = 0;
+        DevBuf<float> ring;
         long long steps = 0;
         std::vector<float> h1, h2, h3, hd, hn;     // host side of a traced step (sized once: no allocation per step)
-        float *tile_chw = nullptr, *tile_hwc = nullptr; size_t tile_cap = 0;      // st_tile_get_tile's staging (kept across calls)
+        DevBuf<float> tile_chw, tile_hwc;          // st_tile_get_tile's staging (kept across calls)
     } comm;
     // profiling
     bool prof_on = false;
@@ -269,10 +270,6 @@ struct st_ctx {
 
 namespace st2e {
 // ---------------------------------------------------------------------------------------- helpers (engine.cpp)
-int dmalloc(float** p, size_t nfloats);
-void dfree(float*& p);
-int dmalloc16(unsigned short** p, size_t n);
-void dfree16(unsigned short*& p);
 inline size_t act16_elems(int C, size_t hw) { return (size_t)((C + 7) / 8) * hw * 8; }
 inline bool conv16_ok(const st_ctx* c, int K) { (void)c; return K >= 8 && K % 8 == 0; }
 int wino_scratch(st_ctx* c, ConvProblem& p, int splits);      // room for the split-K partial sums (WinoLaunch::splits) of a Winograd launch that would otherwise leave most CUs idle
@@ -313,7 +310,6 @@ inline void prof_note(st_ctx* c, int cls, double flops)
 }
 
 void shapes_for(const st_ctx* c, int H, int W, std::vector<int>& C, std::vector<int>& h, std::vector<int>& w);
-void act_free(ActSet& a);
 int act_ensure(st_ctx* c, ActSet& a, int H, int W);
 int forward_range(st_ctx* c, ActSet& a, const float* x, int last, bool lean = false);
 int ensure_gram_bufs(st_ctx* c, int C, int hw, GramPlan& pl, bool plan16 = false);

@@ -59,12 +59,8 @@ static int rccl_load()
 void comm_free(st_ctx* c)
 {
     st_ctx::Comm& m = c->comm;
-    for (auto& plan : m.plan) {
-        for (auto& p : plan) { dfree(p.sbuf); dfree(p.rbuf); }
-        plan.clear();
-    }
-    dfree(m.ring); m.ring_cap = 0;
-    dfree(m.tile_chw); dfree(m.tile_hwc); m.tile_cap = 0;
+    for (auto& plan : m.plan) plan.clear();
+    m.ring.reset(); m.tile_chw.reset(); m.tile_hwc.reset();
     if (m.comm && g_rccl.destroy) (void)g_rccl.destroy(m.comm);
     m.comm = nullptr;
     m.ar = nullptr; m.ex = nullptr; m.user = nullptr;
@@ -287,7 +283,7 @@ int st_comm_barrier(st_ctx* c)
     if (!comm_ready(c)) return fail(ST_ERR_STATE, "st_comm_init first");
     HIP_TRY(hipSetDevice(c->device));
     if (c->comm.world > 1) {
-        if (c->comm.ring_cap < 4) { dfree(c->comm.ring); ST_TRY(dmalloc(&c->comm.ring, 4)); c->comm.ring_cap = 4; }
+        ST_TRY(c->comm.ring.reserve(4));
         HIP_TRY(hipMemsetAsync(c->comm.ring, 0, sizeof(float), c->stream));
         ST_TRY(comm_allreduce(c, c->comm.ring, 1));
     }
@@ -302,7 +298,6 @@ int st_tile_plan(st_ctx* c, int phase, int n_peers, const st_tile_peer* peers)
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     auto& plan = c->comm.plan[phase];
-    for (auto& p : plan) { dfree(p.sbuf); dfree(p.rbuf); }
     plan.clear();
     for (int i = 0; i < n_peers; ++i) {
         const st_tile_peer& q = peers[i];
@@ -318,9 +313,9 @@ int st_tile_plan(st_ctx* c, int phase, int n_peers, const st_tile_peer* peers)
         for (int r = 0; r < q.n_recv; ++r) p.rn += (size_t)3 * p.recv[4 * r + 2] * p.recv[4 * r + 3];
         if (q.peer == c->comm.rank && p.sn != p.rn) return fail(ST_ERR_ARG, "a local copy must send and receive the same number of pixels");
         if (p.sn > 0x7fffffffu || p.rn > 0x7fffffffu) return fail(ST_ERR_ARG, "a strip message is limited to 2^31 floats");
-        if (p.sn) ST_TRY(dmalloc(&p.sbuf, p.sn));
+        if (p.sn) ST_TRY(p.sbuf.alloc(p.sn));
         if (p.rn && (q.peer != c->comm.rank || c->comm.self_via_rccl)) {
-            ST_TRY(dmalloc(&p.rbuf, p.rn));
+            ST_TRY(p.rbuf.alloc(p.rn));
             // a transport that delivers nothing (the solo-rank timing hook) must leave zeros, not whatever the allocation held
             HIP_TRY(hipMemset(p.rbuf, 0, p.rn * sizeof(float)));
         }
@@ -351,7 +346,7 @@ static int tile_evaluate(st_ctx* c, bool adam, TileEval& e, bool want_trace)
     ST_TRY(st_tile_backward(c, &wgrad));                                        // phase 3: ranged backward on the window
     ST_TRY(comm_exchange(c, ST_TILE_PLAN_OVERLAP, wgrad, wh, ww, wgrad, wh, ww, true));
     const size_t ring_n = (size_t)3 * (th + 2) * (tw + 2);
-    if (ring_n > c->comm.ring_cap) { HIP_TRY(hipStreamSynchronize(c->stream)); dfree(c->comm.ring); c->comm.ring_cap = 0; ST_TRY(dmalloc(&c->comm.ring, ring_n)); c->comm.ring_cap = ring_n; }
+    if (ring_n > c->comm.ring.cap()) { HIP_TRY(hipStreamSynchronize(c->stream)); ST_TRY(c->comm.ring.reserve(ring_n)); }
     HIP_TRY(hipMemsetAsync(c->comm.ring, 0, ring_n * sizeof(float), c->stream));
     ST_TRY(comm_exchange(c, ST_TILE_PLAN_RING, c->x[c->cur], wh, ww, c->comm.ring, th + 2, tw + 2, false));
     if (adam) ST_TRY(st_tile_update(c, c->comm.ring, &e.p3, &e.n3));            // phase 4: TV / p-norm / Adam on the tile
@@ -397,12 +392,11 @@ static int tile_lbfgs_step(st_ctx* c, TileEval& e, bool want_trace)
     const int wh = c->H, ww = c->W, th = t.ty1 - t.ty0, tw = t.tx1 - t.tx0;
     const size_t n_t = (size_t)3 * th * tw;
     ST_TRY(lbfgs_alloc(c));                                                     // (window-sized vectors: the tile's fit)
-    if (t.lb_n != n_t) {
+    if (t.lb_x.cap() != n_t) {
         HIP_TRY(hipStreamSynchronize(c->stream));
-        dfree(t.lb_x); dfree(t.lb_sums);
-        ST_TRY(dmalloc(&t.lb_x, n_t)); ST_TRY(dmalloc(&t.lb_sums, (size_t)lbfgs_gram_rows()));
+        t.lb_x.reset(); t.lb_sums.reset();
+        ST_TRY(t.lb_x.alloc(n_t)); ST_TRY(t.lb_sums.alloc((size_t)lbfgs_gram_rows()));
         HIP_TRY(hipMemset(c->lb_gpart, 0, (size_t)lbfgs_gram_rows() * kMaxPartials * sizeof(float)));      // rows of dead ids are summed too (never used)
-        t.lb_n = n_t;
     }
     hipStream_t s = c->stream;
     const std::vector<int> tile_rect = {t.ty0 - t.wy0, t.tx0 - t.wx0, th, tw};
@@ -491,11 +485,10 @@ int st_tile_get_tile(st_ctx* c, float* out_hwc)
     const st_ctx::Tile& t = c->tile;
     const int th = t.ty1 - t.ty0, tw = t.tx1 - t.tx0;
     const size_t n = (size_t)3 * th * tw;
-    if (n > c->comm.tile_cap) {          // staging kept in the context (two device allocations per call until round 4)
+    if (n > c->comm.tile_hwc.cap()) {    // staging kept in the context (two device allocations per call until round 4)
         HIP_TRY(hipStreamSynchronize(c->stream));
-        dfree(c->comm.tile_chw); dfree(c->comm.tile_hwc); c->comm.tile_cap = 0;
-        ST_TRY(dmalloc(&c->comm.tile_chw, n)); ST_TRY(dmalloc(&c->comm.tile_hwc, n));
-        c->comm.tile_cap = n;
+        c->comm.tile_chw.reset(); c->comm.tile_hwc.reset();
+        ST_TRY(c->comm.tile_chw.alloc(n)); ST_TRY(c->comm.tile_hwc.alloc(n));
     }
     float *chw = c->comm.tile_chw, *hwc = c->comm.tile_hwc;
     int rc = ST_OK;

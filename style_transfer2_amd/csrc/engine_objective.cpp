@@ -33,9 +33,9 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
         const int b = al.blob;
         const int C = a.C[b], hw = a.h[b] * a.w[b];
         const size_t n = (size_t)C * hw;
-        if (!c->inject[b]) ST_TRY(dmalloc(&c->inject[b], n));
+        if (!c->inject[b]) ST_TRY(c->inject[b].alloc(n));
         c->inject_roi_zero[b] = 0;
-        if (!c->layer_part[b]) ST_TRY(dmalloc(&c->layer_part[b], 5 * kMaxPartials));
+        if (!c->layer_part[b]) ST_TRY(c->layer_part[b].alloc(5 * kMaxPartials));
         float* part = c->layer_part[b];
         float* nrm = c->norms + b * 3;
         int* cnt = &c->cnt[b * 6];
@@ -65,7 +65,7 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
             if (!c->dbuf) {          // [C][MPad] scratch for D = G - G_style, sized for the widest blob
                 size_t cc = 1;
                 for (int i = 0; i < c->nb; ++i) cc = std::max(cc, (size_t)a.C[i] * conv_mpad(a.C[i]));
-                ST_TRY(dmalloc(&c->dbuf, cc));
+                ST_TRY(c->dbuf.alloc(cc));
                 HIP_TRY(hipMemsetAsync(c->dbuf, 0, cc * sizeof(float), c->stream));
             }
             // bf16 path: the Gram of the CURRENT features and F of the style gradient are taken from the blob's bf16 copy where this
@@ -78,14 +78,10 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
             // bf16 path, norm known: the gradient rides on the data-gradient conv above this blob; only its trace value is taken here
             const bool fuse = want_grad && s16 && c->norm_valid[b * 3 + 1] && style_fuse_ok(c, a, b, last);
             // st_set_gram_algo(ctx, 1), fp32 features: the same S from split operands on the bf16 matrix cores (gram_split.hip)
-            const bool ssplit = !s16 && use_gram_split(c, C, hw) && style_grad_split_pack_elems(C) <= c->dsplit_cap;
+            const bool ssplit = !s16 && use_gram_split(c, C, hw) && style_grad_split_pack_elems(C) <= c->dsplit.cap();
             const int need = fuse ? style_s2_trace_blocks(C) : s16 ? style_grad16_blocks(C, (size_t)hw) : ssplit ? style_grad_split_blocks(C, hw) : style_grad_blocks(C, a.h[b], a.w[b]);
-            if (c->s2_cap[b] < need) { dfree(c->s2_part[b]); ST_TRY(dmalloc(&c->s2_part[b], need)); c->s2_cap[b] = need; }
-            if (s16 && style_grad16_pack_elems(C) > c->d16_cap) {
-                dfree16(c->d16); c->d16_cap = 0;
-                ST_TRY(dmalloc16(&c->d16, style_grad16_pack_elems(C)));
-                c->d16_cap = style_grad16_pack_elems(C);
-            }
+            ST_TRY(c->s2_part[b].reserve(need));
+            if (s16) ST_TRY(c->d16.reserve(style_grad16_pack_elems(C)));
             const double fl = 2.0 * C * C * (double)hw;
             auto style_launch = [&](float* dst, int fused, int accumulate) -> int {
                 ProfScope ps(c, s16 ? P_STYLE_GRAD_BF16 : ssplit ? P_STYLE_GRAD_SPLIT : P_STYLE_GRAD, fl, n * (s16 ? 6.0 : 8.0));
@@ -96,7 +92,7 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
             };
             if (fuse) {
                 const size_t pe = style_fuse_pack_elems(C, conv_mpad(C));
-                if (c->sfuse_cap[b] < pe) { dfree16(c->sfuse_w[b]); c->sfuse_cap[b] = 0; ST_TRY(dmalloc16(&c->sfuse_w[b], pe)); c->sfuse_cap[b] = pe; }
+                ST_TRY(c->sfuse_w[b].reserve(pe));
                 { ProfScope ps(c, P_MISC, 0, 4.0 * C * C + 2.0 * pe);
                   HIP_TRY(launch_style_fuse_pack(c->dbuf, conv_mpad(C), C, conv_mpad(C), c2, al.sw, nrm + 1, c->sfuse_w[b], c->stream)); }
                 { ProfScope ps(c, P_STYLE_GRAD, 2.0 * C * C * (double)C, 12.0 * C * C);
@@ -105,7 +101,7 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
             } else if (c->norm_valid[b * 3 + 1]) {
                 ST_TRY(style_launch(c->inject[b], 1, wrote));
             } else {              // first evaluation: S unscaled -> norm -> saxpy (worker.py:265-269)
-                if (!c->stmp) ST_TRY(dmalloc(&c->stmp, c->max_blob));
+                if (!c->stmp) ST_TRY(c->stmp.alloc(c->max_blob));
                 ST_TRY(style_launch(c->stmp, 0, 0));
                 { ProfScope ps(c, P_FINALIZE, 0, 0);
                   HIP_TRY(launch_finalize_norm(c->s2_part[b], cnt[5], (double)n, nrm + 1, c->stream)); }
@@ -119,7 +115,7 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
 
     const float* scd = nullptr;
     if (want_grad && !c->active.empty()) {
-        if (!c->diffA) { ST_TRY(dmalloc(&c->diffA, c->max_blob)); ST_TRY(dmalloc(&c->diffB, c->max_blob)); }
+        if (!c->diffA) { ST_TRY(c->diffA.alloc(c->max_blob)); ST_TRY(c->diffB.alloc(c->max_blob)); }
         if (last == 0) scd = inj[0];
         else {
             std::vector<const float*> below = inj;
@@ -212,7 +208,7 @@ int st_set_weights(st_ctx* c, int n_rows, const int* blob_index, const float* co
         for (const ActiveLayer& al : c->active) if (al.c) used[al.blob] = 1;
         HIP_TRY(hipSetDevice(c->device));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        for (int b = 0; b < c->nb; ++b) if (!used[b]) dfree(c->content_feat[b]);
+        for (int b = 0; b < c->nb; ++b) if (!used[b]) c->content_feat[b].reset();
     }
     return ST_OK;
 }

@@ -2,28 +2,19 @@
 #include "engine.h"
 
 namespace st2e {
-struct DevTable { int* lo = nullptr; int* n = nullptr; double* k = nullptr; ResampleTable t{}; int out = 0; };
+struct DevTable { DevBuf<int> lo, n; DevBuf<double> k; ResampleTable t{}; int out = 0; };
 
 int table_upload(const st_resample_table* h, DevTable* d)
 {
     if (!h || !h->lo || !h->n || !h->k || h->kmax <= 0 || h->out_size <= 0) return fail(ST_ERR_ARG, "bad resample table");
     const size_t no = (size_t)h->out_size;
-    HIP_TRY(hipMalloc((void**)&d->lo, no * sizeof(int)));
-    HIP_TRY(hipMalloc((void**)&d->n, no * sizeof(int)));
-    HIP_TRY(hipMalloc((void**)&d->k, no * h->kmax * sizeof(double)));
+    ST_TRY(d->lo.alloc(no)); ST_TRY(d->n.alloc(no)); ST_TRY(d->k.alloc(no * h->kmax));
     HIP_TRY(hipMemcpy(d->lo, h->lo, no * sizeof(int), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d->n, h->n, no * sizeof(int), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d->k, h->k, no * h->kmax * sizeof(double), hipMemcpyHostToDevice));
     d->t = ResampleTable{d->lo, d->n, d->k, h->kmax};
     d->out = h->out_size;
     return ST_OK;
-}
-void table_free(DevTable* d)
-{
-    if (d->lo) (void)hipFree(d->lo);
-    if (d->n) (void)hipFree(d->n);
-    if (d->k) (void)hipFree(d->k);
-    *d = DevTable{};
 }
 int tables_valid_for(const st_resample_table* x, const st_resample_table* y, int H, int W)
 {
@@ -48,40 +39,32 @@ int st_resample_state(st_ctx* c, const st_resample_table* lan_x, const st_resamp
     if (!tables_valid_for(lan_x, lan_y, H, W) || (adam && !tables_valid_for(bil_x, bil_y, H, W))) return fail(ST_ERR_ARG, "resample table does not fit the %dx%d state", H, W);
     HIP_TRY(hipStreamSynchronize(c->stream));
     DevTable lx, ly, bx, by;
-    int rc = table_upload(lan_x, &lx);
-    if (rc == ST_OK) rc = table_upload(lan_y, &ly);
-    if (rc == ST_OK && adam) rc = table_upload(bil_x, &bx);
-    if (rc == ST_OK && adam) rc = table_upload(bil_y, &by);
+    ST_TRY(table_upload(lan_x, &lx)); ST_TRY(table_upload(lan_y, &ly));
+    if (adam) { ST_TRY(table_upload(bil_x, &bx)); ST_TRY(table_upload(bil_y, &by)); }
     const size_t n2 = (size_t)3 * H2 * W2, ntmp = (size_t)3 * H * W2;
-    float *tx = nullptr, *tm = nullptr, *tv = nullptr, *tmp = nullptr;
-    if (rc == ST_OK) rc = dmalloc(&tx, n2);
-    if (rc == ST_OK) rc = dmalloc(&tmp, ntmp);
     const bool keep_m = adam && !c->m_zero, keep_v = adam && !c->v_zero;
-    if (rc == ST_OK && keep_m) rc = dmalloc(&tm, n2);
-    if (rc == ST_OK && keep_v) rc = dmalloc(&tv, n2);
-    auto hip_ok = [&](hipError_t e, const char* what) { if (e != hipSuccess && rc == ST_OK) rc = fail(ST_ERR_HIP, "%s: %s", what, hipGetErrorString(e)); };
-    if (rc == ST_OK) {
-        if (new_x_nchw) hip_ok(hipMemcpyAsync(tx, new_x_nchw, n2 * sizeof(float), hipMemcpyHostToDevice, c->stream), "new x upload");
-        else hip_ok(launch_resample(c->x[c->cur], tmp, tx, 3, H, W, H2, W2, lx.t, ly.t, 0, c->stream), "resample x");
-        if (keep_m) hip_ok(launch_resample(c->m, tmp, tm, 3, H, W, H2, W2, lx.t, ly.t, 0, c->stream), "resample m");
-        if (keep_v) hip_ok(launch_resample(c->v, tmp, tv, 3, H, W, H2, W2, bx.t, by.t, 1, c->stream), "resample v");   // np.maximum(0, .)
-        hip_ok(hipStreamSynchronize(c->stream), "resample sync");
-    }
+    // (an early return below frees the temporaries and tables while a launch that reads them may still be queued: hipFree waits
+    // for the device first, so that is safe)
+    DevBuf<float> tx, tm, tv, tmp;
+    ST_TRY(tx.alloc(n2)); ST_TRY(tmp.alloc(ntmp));
+    if (keep_m) ST_TRY(tm.alloc(n2));
+    if (keep_v) ST_TRY(tv.alloc(n2));
+    if (new_x_nchw) HIP_TRY(hipMemcpyAsync(tx, new_x_nchw, n2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    else HIP_TRY(launch_resample(c->x[c->cur], tmp, tx, 3, H, W, H2, W2, lx.t, ly.t, 0, c->stream));
+    if (keep_m) HIP_TRY(launch_resample(c->m, tmp, tm, 3, H, W, H2, W2, lx.t, ly.t, 0, c->stream));
+    if (keep_v) HIP_TRY(launch_resample(c->v, tmp, tv, 3, H, W, H2, W2, bx.t, by.t, 1, c->stream));   // np.maximum(0, .)
+    HIP_TRY(hipStreamSynchronize(c->stream));
     const bool mz = c->m_zero, vz = c->v_zero;
     const int i1 = c->items1, i2 = c->items2;
-    if (rc == ST_OK) rc = ensure_input_buffers(c, H2, W2);            // frees and re-creates x, m, v, L-BFGS vectors
-    if (rc == ST_OK) {
-        c->lb_clear = true; c->have_cur = false;
-        iterate_overwritten(c);                        // (a resample to the SAME size keeps the buffers)
-        hip_ok(hipMemcpyAsync(c->x[c->cur], tx, n2 * sizeof(float), hipMemcpyDeviceToDevice, c->stream), "x copy");
-        if (keep_m) hip_ok(hipMemcpyAsync(c->m, tm, n2 * sizeof(float), hipMemcpyDeviceToDevice, c->stream), "m copy");
-        if (keep_v) hip_ok(hipMemcpyAsync(c->v, tv, n2 * sizeof(float), hipMemcpyDeviceToDevice, c->stream), "v copy");
-        hip_ok(hipStreamSynchronize(c->stream), "copy sync");
-        c->m_zero = mz; c->v_zero = vz; c->items1 = i1; c->items2 = i2;
-    }
-    dfree(tx); dfree(tm); dfree(tv); dfree(tmp);
-    table_free(&lx); table_free(&ly); table_free(&bx); table_free(&by);
-    return rc;
+    ST_TRY(ensure_input_buffers(c, H2, W2));           // frees and re-creates x, m, v, L-BFGS vectors
+    c->lb_clear = true; c->have_cur = false;
+    iterate_overwritten(c);                            // (a resample to the SAME size keeps the buffers)
+    HIP_TRY(hipMemcpyAsync(c->x[c->cur], tx, n2 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    if (keep_m) HIP_TRY(hipMemcpyAsync(c->m, tm, n2 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    if (keep_v) HIP_TRY(hipMemcpyAsync(c->v, tv, n2 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->m_zero = mz; c->v_zero = vz; c->items1 = i1; c->items2 = i2;
+    return ST_OK;
 }
 
 int st_resample_content(st_ctx* c, const st_resample_table* lan_x, const st_resample_table* lan_y)
@@ -93,17 +76,13 @@ int st_resample_content(st_ctx* c, const st_resample_table* lan_x, const st_resa
     const int H = c->cH, W = c->cW, H2 = lan_y->out_size, W2 = lan_x->out_size;
     if (!tables_valid_for(lan_x, lan_y, H, W)) return fail(ST_ERR_ARG, "resample table does not fit the %dx%d content", H, W);
     DevTable lx, ly;
-    int rc = table_upload(lan_x, &lx);
-    if (rc == ST_OK) rc = table_upload(lan_y, &ly);
-    float *tx = nullptr, *tmp = nullptr;
-    if (rc == ST_OK) rc = dmalloc(&tx, (size_t)3 * H2 * W2);
-    if (rc == ST_OK) rc = dmalloc(&tmp, (size_t)3 * H * W2);
-    if (rc == ST_OK && launch_resample(c->content_x, tmp, tx, 3, H, W, H2, W2, lx.t, ly.t, 0, c->stream) != hipSuccess) rc = fail(ST_ERR_HIP, "content resample failed");
-    if (rc == ST_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(ST_ERR_HIP, "content resample sync failed");
-    if (rc == ST_OK) rc = content_from_device(c, tx, H2, W2);
-    (void)hipStreamSynchronize(c->stream);
-    dfree(tx); dfree(tmp);
-    table_free(&lx); table_free(&ly);
+    ST_TRY(table_upload(lan_x, &lx)); ST_TRY(table_upload(lan_y, &ly));
+    DevBuf<float> tx, tmp;         // (freed on an early return too; hipFree waits for the device, as above)
+    ST_TRY(tx.alloc((size_t)3 * H2 * W2)); ST_TRY(tmp.alloc((size_t)3 * H * W2));
+    HIP_TRY(launch_resample(c->content_x, tmp, tx, 3, H, W, H2, W2, lx.t, ly.t, 0, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const int rc = content_from_device(c, tx, H2, W2);
+    (void)hipStreamSynchronize(c->stream);             // (before tx goes)
     return rc;
 }
 

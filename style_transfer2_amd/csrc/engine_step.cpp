@@ -6,17 +6,17 @@ namespace st2e {
 int lbfgs_alloc(st_ctx* c)
 {
     const size_t n3 = (size_t)3 * c->H * c->W;
-    if (!c->g_cur) ST_TRY(dmalloc(&c->g_cur, n3));
-    if (!c->pvec) ST_TRY(dmalloc(&c->pvec, n3));
+    if (!c->g_cur) ST_TRY(c->g_cur.alloc(n3));
+    if (!c->pvec) ST_TRY(c->pvec.alloc(n3));
     for (int i = 0; i <= st_ctx::kCorr; ++i) {
-        if (!c->hs[i]) ST_TRY(dmalloc(&c->hs[i], n3));
-        if (!c->hy[i]) ST_TRY(dmalloc(&c->hy[i], n3));
+        if (!c->hs[i]) ST_TRY(c->hs[i].alloc(n3));
+        if (!c->hy[i]) ST_TRY(c->hy[i].alloc(n3));
     }
     if (!c->lb_gram) {
-        HIP_TRY(hipMalloc((void**)&c->lb_gram, sizeof(LbfgsGram)));
+        ST_TRY(c->lb_gram.alloc(1));
         HIP_TRY(hipMemset(c->lb_gram, 0, sizeof(LbfgsGram)));
     }
-    if (!c->lb_gpart) ST_TRY(dmalloc(&c->lb_gpart, (size_t)kLbGramRows * kMaxPartials));
+    if (!c->lb_gpart) ST_TRY(c->lb_gpart.alloc((size_t)kLbGramRows * kMaxPartials));
     return ST_OK;
 }
 
@@ -104,7 +104,7 @@ bool step_graph_ok(const st_ctx* c)
 int step_graph_capture(st_ctx* c, int par)
 {
     if (c->gexec[par]) { (void)hipGraphExecDestroy(c->gexec[par]); c->gexec[par] = nullptr; }
-    if (!c->adam_dyn) ST_TRY(dmalloc(&c->adam_dyn, 4));
+    if (!c->adam_dyn) ST_TRY(c->adam_dyn.alloc(4));
     hipGraph_t g = nullptr;
     HIP_TRY(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
     c->capturing = true;
@@ -251,13 +251,13 @@ int st_step_begin(st_ctx* c)
         for (int i = 0; i < st_ctx::Pipe::kSlots; ++i) {
             HIP_TRY(hipEventCreateWithFlags(&p.ready[i], hipEventDisableTiming));
             HIP_TRY(hipEventCreateWithFlags(&p.done[i], hipEventDisableTiming));
-            HIP_TRY(hipHostMalloc((void**)&p.trace_pin[i], (kMaxTraceLayers * 6 + 8) * sizeof(float), 0));
+            ST_TRY(p.trace_pin[i].alloc(kMaxTraceLayers * 6 + 8));
         }
     }
     p.begins += 1;
     // buffers a re-allocation replaced: free them once no view handed out before it can still be in use (st2.h: five further begins)
     for (size_t i = 0; i < p.retired.size();) {
-        if (p.begins - p.retired[i].at >= st_ctx::Pipe::kSlots) { (void)hipHostFree(p.retired[i].p); p.retired.erase(p.retired.begin() + i); }
+        if (p.begins - p.retired[i].at >= st_ctx::Pipe::kSlots) p.retired.erase(p.retired.begin() + i);
         else ++i;
     }
     if (n3 > p.cap || p.want_head != p.have_head || p.want_tail != p.have_tail) {
@@ -265,9 +265,9 @@ int st_step_begin(st_ctx* c)
         const size_t cap = std::max(n3, p.cap);
         for (int i = 0; i < st_ctx::Pipe::kSlots; ++i) {
             // the iterates already handed out are views of these buffers: retire them instead of freeing them
-            if (p.pin_base[i]) { p.retired.push_back({p.pin_base[i], p.begins}); p.pin_base[i] = nullptr; p.img_pin[i] = nullptr; }
-            if (cap > p.cap) { dfree(p.hwc[i]); ST_TRY(dmalloc(&p.hwc[i], cap)); }
-            HIP_TRY(hipHostMalloc((void**)&p.pin_base[i], p.want_head + cap * sizeof(float) + p.want_tail, 0));
+            if (p.pin_base[i]) { p.retired.push_back({std::move(p.pin_base[i]), p.begins}); p.img_pin[i] = nullptr; }
+            ST_TRY(p.hwc[i].reserve(cap));         // (after a begin that failed half-way the slots it did re-make are kept)
+            ST_TRY(p.pin_base[i].alloc(p.want_head + cap * sizeof(float) + p.want_tail));
             p.img_pin[i] = (float*)(p.pin_base[i] + p.want_head);
         }
         p.cap = cap; p.have_head = p.want_head; p.have_tail = p.want_tail;
@@ -345,7 +345,7 @@ int st_lbfgs_inv_hv(st_ctx* c, int n_pairs, const float* const* s_vecs, const fl
     if (host.count != n_pairs) return fail(ST_ERR_ARG, "%d of %d pairs failed the s.y > 1e-10 gate", n_pairs - host.count, n_pairs);
     if (lbfgs_wants_gram(c)) {      // the Gram form of the same recursion: its matrix from pairwise inner products taken one by one
         const size_t n3 = (size_t)3 * c->H * c->W;
-        if (!c->lb_dots) ST_TRY(dmalloc(&c->lb_dots, (size_t)kLbNB * kLbNB));
+        if (!c->lb_dots) ST_TRY(c->lb_dots.alloc((size_t)kLbNB * kLbNB));
         HIP_TRY(hipMemsetAsync(c->lb_dots, 0, sizeof(float) * kLbNB * kLbNB, st));
         std::vector<std::pair<int, const float*>> basis;
         for (int k = 0; k < n_pairs; ++k) { basis.push_back({k, c->hs[k]}); basis.push_back({kLbfgsSlots + k, c->hy[k]}); }

@@ -22,11 +22,6 @@ BlobRoi tile_roi(const st_ctx* c, const ActSet& a, const TileGeom& t, int b)
     return r;
 }
 BlobRoi tile_roi(const st_ctx* c, int b) { return tile_roi(c, c->act, c->tile, b); }
-int tile_ensure(float** p, size_t* cap, size_t n)
-{
-    if (n > *cap) { dfree(*p); ST_TRY(dmalloc(p, n)); *cap = n; }
-    return ST_OK;
-}
 // bf16 operands: does the style term of blob b run on its bf16 copy here (region-of-interest forms of gram16.hip / style16.hip)?
 bool tile_style16(const st_ctx* c, int b)
 {
@@ -43,7 +38,7 @@ int tile_style_grad(st_ctx* c, int b, const BlobRoi& r, float* dst, bool is_inje
     if (!tile_style16(c, b)) {
         if (!a.plan.fwd[b].out32) return fail(ST_ERR_STATE, "internal: style blob %d has no fp32 copy", b);
         const int need = style_grad_blocks(C, a.h[b], a.w[b]);
-        if (c->s2_cap[b] < need) { dfree(c->s2_part[b]); ST_TRY(dmalloc(&c->s2_part[b], need)); c->s2_cap[b] = need; }
+        ST_TRY(c->s2_part[b].reserve(need));
         PixRoi pr{r.y0, r.x0, r.y1, r.x1};
         HIP_TRY(launch_style_grad(c->dbuf, a.data[b], dst, c2, fused, sw, c->norms + b * 3 + 1, accumulate, c->s2_part[b], np, C, a.h[b], a.w[b], c->stream, &pr));
         return ST_OK;
@@ -51,12 +46,8 @@ int tile_style_grad(st_ctx* c, int b, const BlobRoi& r, float* dst, bool is_inje
     const int rw = r.x1 - r.x0, rh = r.y1 - r.y0;
     const size_t hw = (size_t)rw * rh, plane = (size_t)a.h[b] * a.w[b];
     const int need = style_grad16_blocks(C, hw);
-    if (c->s2_cap[b] < need) { dfree(c->s2_part[b]); ST_TRY(dmalloc(&c->s2_part[b], need)); c->s2_cap[b] = need; }
-    if (style_grad16_pack_elems(C) > c->d16_cap) {
-        dfree16(c->d16); c->d16_cap = 0;
-        ST_TRY(dmalloc16(&c->d16, style_grad16_pack_elems(C)));
-        c->d16_cap = style_grad16_pack_elems(C);
-    }
+    ST_TRY(c->s2_part[b].reserve(need));
+    ST_TRY(c->d16.reserve(style_grad16_pack_elems(C)));
     if (is_inject && !accumulate && !c->inject_roi_zero[b]) {
         HIP_TRY(hipMemsetAsync(dst, 0, (size_t)C * plane * sizeof(float), c->stream));
         c->inject_roi_zero[b] = 1;
@@ -72,7 +63,7 @@ int tile_style_D(st_ctx* c, int b, const float* graw, double n_global, float* pd
 {
     const ActSet& a = c->act;
     const int C = a.C[b];
-    if (!c->layer_part[b]) ST_TRY(dmalloc(&c->layer_part[b], 5 * kMaxPartials));
+    if (!c->layer_part[b]) ST_TRY(c->layer_part[b].alloc(5 * kMaxPartials));
     float* part = c->layer_part[b] + 4 * kMaxPartials;
     int np = 0;
     GramPlan one{}; one.splits = 1;
@@ -118,7 +109,7 @@ int st_tile_forward(st_ctx* c, float** dev_ptr, int* n_floats)
             return fail(ST_ERR_STATE, "blob %d (%s) carries a style weight but has no style target: the sharded style pass (st_tile_set_style) stopped below it", al.blob, c->blob_names[al.blob].c_str());
     }
     ST_TRY(ensure_content_features(c));
-    ST_TRY(tile_ensure(&c->tile.p1, &c->tile.p1_n, std::max<size_t>(n1, 1)));
+    ST_TRY(c->tile.p1.reserve(std::max<size_t>(n1, 1)));
     HIP_TRY(hipMemsetAsync(c->tile.p1, 0, std::max<size_t>(n1, 1) * sizeof(float), c->stream));
     // bf16 operands: the lean data flow here too -- an fp32 blob / diff is written only where something reads fp32 (the weighted
     // blobs: the region-of-interest loss kernels are fp32), pools ride on their producing conv, the backward masks from the bf16 copies
@@ -131,7 +122,7 @@ int st_tile_forward(st_ctx* c, float** dev_ptr, int* n_floats)
         const int b = al.blob, C = a.C[b];
         const BlobRoi r = tile_roi(c, b);
         const size_t n = (size_t)C * a.h[b] * a.w[b];
-        if (!c->layer_part[b]) ST_TRY(dmalloc(&c->layer_part[b], 5 * kMaxPartials));
+        if (!c->layer_part[b]) ST_TRY(c->layer_part[b].alloc(5 * kMaxPartials));
         float* part = c->layer_part[b];
         if (al.c || al.d) {
             LayerElemArgs e{};
@@ -179,13 +170,13 @@ int st_tile_losses(st_ctx* c, float** dev_ptr, int* n_floats)
     int n_style = 0;
     bool missing = false;
     for (const ActiveLayer& al : c->active) if (al.s) { ++n_style; missing = missing || !c->norm_valid[al.blob * 3 + 1]; }
-    ST_TRY(tile_ensure(&c->tile.p2, &c->tile.p2_n, std::max(n_style, 1)));
-    ST_TRY(tile_ensure(&c->tile.pd, &c->tile.pd_n, std::max(n_style, 1)));
+    ST_TRY(c->tile.p2.reserve(std::max(n_style, 1)));
+    ST_TRY(c->tile.pd.reserve(std::max(n_style, 1)));
     c->tile.s2_in_p2 = missing;
     if (!c->dbuf) {
         size_t cc = 1;
         for (int i = 0; i < c->nb; ++i) cc = std::max(cc, (size_t)a.C[i] * conv_mpad(a.C[i]));
-        ST_TRY(dmalloc(&c->dbuf, cc));
+        ST_TRY(c->dbuf.alloc(cc));
         HIP_TRY(hipMemsetAsync(c->dbuf, 0, cc * sizeof(float), c->stream));
     }
     size_t pos = 0;
@@ -217,7 +208,7 @@ int st_tile_losses_finish(st_ctx* c)
         const int b = al.blob, C = a.C[b];
         const BlobRoi r = tile_roi(c, b);
         const size_t n = (size_t)C * a.h[b] * a.w[b];
-        if (!c->inject[b]) ST_TRY(dmalloc(&c->inject[b], n));
+        if (!c->inject[b]) ST_TRY(c->inject[b].alloc(n));
         float* nrm = c->norms + b * 3;
         bool wrote = false;
         if (al.c || al.d) {
@@ -246,7 +237,7 @@ int st_tile_losses_finish(st_ctx* c)
             } else {
                 ST_TRY(tile_style_grad(c, b, r, c->inject[b], true, c2, 1, al.sw, wrote, &np));
                 // sum S^2 of this rank's region -> p3 tail (all-reduced with the image sums)
-                ST_TRY(tile_ensure(&c->tile.p3, &c->tile.p3_n, 6 + kMaxTraceLayers));
+                ST_TRY(c->tile.p3.reserve(6 + kMaxTraceLayers));
                 HIP_TRY(launch_sum_partials(c->s2_part[b], np, c->tile.p3 + 6 + k, c->stream));
             }
             pos += (size_t)C * C;
@@ -272,7 +263,7 @@ int st_tile_style_raw(st_ctx* c)
         const BlobRoi r = tile_roi(c, b);
         ST_TRY(tile_style_D(c, b, c->tile.p1 + pos, r.n_global, c->tile.pd + k));
         const float c2 = (float)(2.0 / ((double)C * C * r.n_global));
-        if (!c->stmp) ST_TRY(dmalloc(&c->stmp, c->max_blob));
+        if (!c->stmp) ST_TRY(c->stmp.alloc(c->max_blob));
         int np = 0;
         ST_TRY(tile_style_grad(c, b, r, c->stmp, false, c2, 0, al.sw, 0, &np));
         HIP_TRY(launch_sum_partials(c->s2_part[b], np, c->tile.p2 + k, c->stream));
@@ -289,13 +280,13 @@ int st_tile_backward(st_ctx* c, float** dev_grad)
     if (!c || !c->tile.on) return fail(ST_ERR_STATE, "st_tile_configure first");
     HIP_TRY(hipSetDevice(c->device));
     const size_t n3 = (size_t)3 * c->H * c->W;
-    if (!c->tile.wgrad) ST_TRY(dmalloc(&c->tile.wgrad, n3));
+    if (!c->tile.wgrad) ST_TRY(c->tile.wgrad.alloc(n3));
     std::vector<const float*> inj(c->nb, nullptr);
     int last = -1;
     for (const ActiveLayer& al : c->active) { inj[al.blob] = c->inject[al.blob]; last = std::max(last, al.blob); }
     if (last < 0) HIP_TRY(hipMemsetAsync(c->tile.wgrad, 0, n3 * sizeof(float), c->stream));
     else {
-        if (!c->diffA) { ST_TRY(dmalloc(&c->diffA, c->max_blob)); ST_TRY(dmalloc(&c->diffB, c->max_blob)); }
+        if (!c->diffA) { ST_TRY(c->diffA.alloc(c->max_blob)); ST_TRY(c->diffB.alloc(c->max_blob)); }
         const float* g = inj[0];
         if (last > 0) ST_TRY(backward_chain(c, last, inj[last], inj, &g, c->bf16 && c->lean));
         HIP_TRY(hipMemcpyAsync(c->tile.wgrad, g, n3 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
@@ -314,7 +305,7 @@ int st_tile_update(st_ctx* c, const float* ring_dev, float** dev_ptr, int* n_flo
     if (c->opt_kind != ST_OPT_ADAM) return fail(ST_ERR_STATE, "the tile-sharded mode implements Adam");
     HIP_TRY(hipSetDevice(c->device));
     const st_ctx::Tile& t = c->tile;
-    ST_TRY(tile_ensure(&c->tile.p3, &c->tile.p3_n, 6 + kMaxTraceLayers));
+    ST_TRY(c->tile.p3.reserve(6 + kMaxTraceLayers));
     c->items1 += 1; c->items2 += 1;
     ImageTileArgs ta{};
     ImagePassArgs& ip = ta.base;
@@ -348,7 +339,7 @@ int st_tile_gradient(st_ctx* c, const float* ring_dev, float** dev_ptr, int* n_f
     if (!c || !c->tile.on || !ring_dev) return fail(ST_ERR_STATE, "st_tile_configure first");
     HIP_TRY(hipSetDevice(c->device));
     const st_ctx::Tile& t = c->tile;
-    ST_TRY(tile_ensure(&c->tile.p3, &c->tile.p3_n, 6 + kMaxTraceLayers));
+    ST_TRY(c->tile.p3.reserve(6 + kMaxTraceLayers));
     ImageTileArgs ta{};
     ImagePassArgs& ip = ta.base;
     ip.x = c->x[c->cur]; ip.scd = c->tile.wgrad; ip.grad = c->grad; ip.C = 3; ip.H = c->H; ip.W = c->W;
@@ -462,12 +453,12 @@ int st_tile_style_partials(st_ctx* c, const void* hwc, int H, int W, int is_u8, 
     for (int b = 0; b <= last_blob; ++b) { const size_t C = c->blob_c_topo(b); total += C * C; }
     if (total > 0x7fffffffu) return fail(ST_ERR_ARG, "the style partials exceed 2^31 floats");
     c->tile.sp_last = -1;
-    ST_TRY(tile_ensure(&c->tile.sp, &c->tile.sp_cap, total));
+    ST_TRY(c->tile.sp.reserve(total));
     HIP_TRY(hipMemsetAsync(c->tile.sp, 0, total * sizeof(float), c->stream));
     int r = ST_OK;
     if (hwc) {
-        float* tmp = nullptr;
-        ST_TRY(dmalloc(&tmp, (size_t)3 * H * W));
+        DevBuf<float> tmp;         // (tmp and aux are freed at the end of the block, after the synchronisation)
+        ST_TRY(tmp.alloc((size_t)3 * H * W));
         ActSet aux;
         ActSet* a = &aux;
         const bool same = c->act.H == H && c->act.W == W && !c->act.data.empty();
@@ -504,9 +495,7 @@ int st_tile_style_partials(st_ctx* c, const void* hwc, int H, int W, int is_u8, 
             pos += (size_t)C * C;
         }
         (void)hipStreamSynchronize(c->stream);
-        if (!same) act_free(aux);
-        else c->act.valid_to = -1;
-        dfree(tmp);
+        if (same) c->act.valid_to = -1;
     } else {
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
@@ -531,7 +520,7 @@ int st_tile_style_commit(st_ctx* c)
     for (int b = 0; b <= c->tile.sp_last; ++b) {
         if (b > 0 && !c->topo[b - 1].is_conv) { gh = pooled_size(gh); gw = pooled_size(gw); }
         const int C = c->blob_c_topo(b);
-        if (!c->style_gram[b]) ST_TRY(dmalloc(&c->style_gram[b], (size_t)C * C));
+        if (!c->style_gram[b]) ST_TRY(c->style_gram[b].alloc((size_t)C * C));
         ProfScope ps(c, P_GRAM_REDUCE, 0, 8.0 * C * C);
         HIP_TRY(launch_gram_reduce(c->tile.sp + pos, nullptr, nullptr, c->style_gram[b], C, nullptr, nullptr, C, (double)C * gh * gw, one, c->stream));
         pos += (size_t)C * C;
