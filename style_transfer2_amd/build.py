@@ -32,6 +32,7 @@ SOURCES = (
     ('conv3x3_first_split.hip', ()),
     ('engine.cpp', ('-x', 'hip')),
     ('engine_route.cpp', ('-x', 'hip')),
+    ('engine_style.cpp', ('-x', 'hip')),
     ('engine_objective.cpp', ('-x', 'hip')),
     ('engine_step.cpp', ('-x', 'hip')),
     ('engine_resample.cpp', ('-x', 'hip')),

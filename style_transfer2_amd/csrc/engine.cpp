@@ -207,42 +207,6 @@ int forward_range(st_ctx* c, ActSet& a, const float* x, int last, bool lean)
     return ST_OK;
 }
 
-int ensure_gram_bufs(st_ctx* c, int C, int hw, GramPlan& pl, bool plan16)
-{
-    pl = plan16 ? gram_plan16(C, hw) : gram_plan(C, hw);
-    ST_TRY(c->gram_slabs.reserve(pl.slab_floats));
-    return c->gram_fold.reserve((size_t)gram_fold_groups(pl) * C * C);
-}
-
-// fp32 features, not tile-sharded (the ROI Grams of that mode and their all-reduced raw sums keep the fp32 kernels), a shape the
-// split kernels take
-bool use_gram_split(const st_ctx* c, int C, int hw)
-{
-    return c->gram_split && !c->bf16 && !c->tile.on && gram_split_ok(C, hw) && style_grad_split_ok(C, hw);
-}
-
-// G (or G - target) of blob data F -> out (C*C); optional sum-of-squares partials
-// F16 (optional): the bf16 channel-blocked copy of the blob -- the bf16 feature path then takes the partials on the bf16 matrix cores
-int gram_into(st_ctx* c, const float* F, int C, int hw, const float* target, float* out, int out_ld, float* partial, int* n_partial,
-                     const unsigned short* F16)
-{
-    GramPlan pl;
-    const bool use16 = F16 && C % 8 == 0 && hw % 64 == 0 && gram16_ok(C, hw, gram_plan16(C, hw));
-    const bool split = !use16 && use_gram_split(c, C, hw);       // st_set_gram_algo(ctx, 1): same plan, same slabs, same reduction
-    ST_TRY(ensure_gram_bufs(c, C, hw, pl, use16));
-    {
-        ProfScope ps(c, use16 ? P_GRAM_BF16 : split ? P_GRAM_SPLIT : P_GRAM, 2.0 * C * C * (double)hw, (use16 ? 2.0 : 4.0) * C * (double)hw);      // (the class names the matrix core that ran)
-        if (use16) HIP_TRY(launch_gram16_partial(F16, c->gram_slabs, C, hw, pl, c->stream));
-        else if (split) HIP_TRY(launch_gram_split_partial(F, c->gram_slabs, C, hw, pl, c->stream));
-        else HIP_TRY(launch_gram_partial(F, c->gram_slabs, C, hw, pl, c->stream));
-    }
-    {
-        ProfScope ps(c, P_GRAM_REDUCE, 0, 4.0 * (double)pl.slab_floats);
-        HIP_TRY(launch_gram_reduce(c->gram_slabs, c->gram_fold, target, out, out_ld, partial, n_partial, C, (double)C * hw, pl, c->stream));
-    }
-    return ST_OK;
-}
-
 // backward chain from blob `top` whose diff is `top_diff` down to data; returns pointer in *out.  Executes plan_backward's routes;
 // `lean` must be what the forward that filled c->act ran with.
 int backward_chain(st_ctx* c, int top, const float* top_diff, const std::vector<const float*>& inj, const float** out, bool lean)
@@ -675,7 +639,7 @@ int st_set_gram_algo(st_ctx* c, int algo)
         std::vector<int> C, h, w;
         shapes_for(c, 16, 16, C, h, w);
         size_t need = 0;
-        for (int i = 0; i < c->nb; ++i) if (style_grad_split_ok(C[i], 4)) need = std::max(need, style_grad_split_pack_elems(C[i]));
+        for (int i = 0; i < c->nb; ++i) need = std::max(need, style_split_scratch(C[i], 4));
         if (need > c->dsplit.cap()) {      // the new buffer exists before the old one is given up
             HIP_TRY(hipSetDevice(c->device));
             DevBuf<unsigned short> p;
@@ -808,7 +772,7 @@ int st_gram(st_ctx* c, int index, float* out)
     const int C = c->act.C[index], hw = c->act.h[index] * c->act.w[index];
     DevBuf<float> g;
     ST_TRY(g.alloc((size_t)C * C));
-    int r = gram_into(c, c->act.data[index], C, hw, nullptr, g, C, nullptr, nullptr);
+    int r = style_gram(c, c->act, style_term(c, c->act, index, nullptr, true), nullptr, g, C, (double)C * hw, nullptr, nullptr);
     if (r == ST_OK) {
         hipError_t e = hipMemcpyAsync(out, g, (size_t)C * C * sizeof(float), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -901,7 +865,7 @@ int st_set_style(st_ctx* c, const void* hwc, int H, int W, int is_u8)
     for (int i = 0; i < c->nb && r == ST_OK; ++i) {
         const int C = a->C[i], hw = a->h[i] * a->w[i];
         if (!c->style_gram[i]) r = c->style_gram[i].alloc((size_t)C * C);
-        if (r == ST_OK) r = gram_into(c, a->data[i], C, hw, nullptr, c->style_gram[i], C, nullptr, nullptr);
+        if (r == ST_OK) r = style_gram(c, *a, style_term(c, *a, i, nullptr, true), nullptr, c->style_gram[i], C, (double)C * hw, nullptr, nullptr);
     }
     (void)hipStreamSynchronize(c->stream);
     if (same) c->act.valid_to = -1;

@@ -79,8 +79,8 @@ struct FwdRoute {
     AmapLayout amap = AMAP_NONE;                           // arg-max map (average pool: sign map) of a pool blob: what THIS forward wrote, whatever the switches say later
     bool pack16 = false;                                   // the bf16 copy comes from a pack_act16 pass after the launch
     bool pools_next = false;                               // conv: the pool above rides on this launch (entry i + 1 says what it writes)
-    bool style16 = false;                                  // the Gram / style gradient of this blob take their F operand from the bf16 copy
-    bool style_all16 = false;                              // ... and nothing of the style term reads the fp32 blob (style_runs16)
+    bool style16 = false;                                  // a style blob: the bf16 copy is written and the style gradient can read it (style_shape's grad16)
+    bool style_all16 = false;                              // ... and the Gram too: nothing of the style term reads the fp32 blob (style_shape's gram16)
 };
 struct BwdRoute {
     BwdKind kind = B_NONE;
@@ -111,6 +111,24 @@ inline bool nonzero(float w) { return fabsf(w) > 1e-15f; }   // NaN compares fal
 
 // one rank's share of a tile-sharded image, in global pixels: the gH x gW image, the origin of the window this context holds, the tile
 struct TileGeom { int gH = 0, gW = 0, wy0 = 0, wx0 = 0, ty0 = 0, tx0 = 0, ty1 = 0, tx1 = 0; };
+struct BlobRoi { int y0, x0, y1, x1; double n_global; };    // the tile's region of one blob; n_global: elements of the blob of the WHOLE image
+
+// ------------------------------------------------------------------------------------- style term
+// The style term of one blob, resolved once (engine_style.cpp): the kernel family of each of its two GEMMs, what the launches need and book
+struct StyleShape { bool grad16, gram16; };        // from shapes and switches alone: the style gradient / also the Gram can run on the blob's bf16 copy
+enum StyleOps : unsigned char { OPS_F32, OPS_SPLIT, OPS_BF16,    // the fp32 blob on the fp32 matrix cores; its three-way split on the bf16 ones (gram_split.hip); the bf16 copy (gram16.hip, style16.hip)
+                                OPS_FUSED };                    // gradient only: rides on the bf16 data-gradient conv above the blob; here its operand pack and trace value
+struct StyleLaunch { StyleOps ops; int cls; double flops, bytes; };      // family, profiler class and figures of one launch
+struct StyleTerm {
+    int b, C, hw;                                  // hw: the pixels both GEMMs contract -- the blob's, or the region's
+    bool roi; GramRoi groi; PixRoi proi;           // region of interest (tile-sharded phases, sharded style pass), in both kernels' forms
+    StyleLaunch gram, grad, pack;                  // Gram partials (plan below), style gradient, OPS_FUSED: the operand pack before it
+    GramPlan plan;                                 // gram_plan, or gram_plan16 for OPS_BF16
+    int slots;                                     // sum S^2 partials the gradient launch writes (s2_part)
+    size_t d16, sfuse;                             // scratch elements the gradient needs in c->d16 / c->sfuse_w[b] (OPS_SPLIT: c->dsplit, sized by st_set_gram_algo)
+    bool reads32, reads16, missing32;              // copies of the blob the term reads; missing32: it reads the fp32 blob and the forward skipped it
+    bool book;                                     // the launches are booked with the profiler (the phases of a tile-sharded iteration are not)
+};
 }  // namespace st2e
 
 using namespace st2e;
@@ -276,9 +294,9 @@ int wino_scratch(st_ctx* c, ConvProblem& p, int splits);      // room for the sp
 
 struct ProfScope {
     st_ctx* c; int idx = -1;
-    ProfScope(st_ctx* ctx, int cls, double flops, double bytes) : c(ctx)
+    ProfScope(st_ctx* ctx, int cls, double flops, double bytes, bool book = true) : c(ctx)
     {
-        if (!c->prof_on) return;
+        if (!c->prof_on || !book) return;
         auto get = [&]() {
             if (c->ev_used == c->ev_pool.size()) {
                 hipEvent_t e;
@@ -312,10 +330,6 @@ inline void prof_note(st_ctx* c, int cls, double flops)
 void shapes_for(const st_ctx* c, int H, int W, std::vector<int>& C, std::vector<int>& h, std::vector<int>& w);
 int act_ensure(st_ctx* c, ActSet& a, int H, int W);
 int forward_range(st_ctx* c, ActSet& a, const float* x, int last, bool lean = false);
-int ensure_gram_bufs(st_ctx* c, int C, int hw, GramPlan& pl, bool plan16 = false);
-int gram_into(st_ctx* c, const float* F, int C, int hw, const float* target, float* out, int out_ld, float* partial, int* n_partial,
-              const unsigned short* F16 = nullptr);
-bool use_gram_split(const st_ctx* c, int C, int hw);      // this whole-blob fp32 Gram / style gradient runs on gram_split.hip
 int backward_chain(st_ctx* c, int top, const float* top_diff, const std::vector<const float*>& inj, const float** out, bool lean = false);
 int ensure_input_buffers(st_ctx* c, int H, int W);
 int stage_upload(st_ctx* c, const void* host, size_t bytes);
@@ -333,8 +347,22 @@ void plan_forward(const st_ctx* c, const ActSet& a, int last, bool lean, std::ve
 // where a fused style operand waits for the data gradient above the blob
 void plan_backward(const st_ctx* c, const ActSet& a, int top, const std::vector<const float*>& inj,
                    const std::vector<const unsigned short*>& fused_w, bool lean, std::vector<BwdRoute>& bwd);
-bool style_fuse_ok(const st_ctx* c, const ActSet& a, int b, int last);
 bool lean32_enabled();                            // ST2_LEAN32 (read per evaluation: A/B runs)
+// ---------------------------------------------------------------------------------------- engine_style.cpp
+// The resolver: no HIP call, no allocation, nothing in the context changes; every predicate and per-call switch of the style term is
+// read here.  style_shape: what plan_forward asks before the forward; style_term: from what that forward left (a.plan.fwd) -- roi: the
+// tile's region, target: a style target (always the fp32 blob), fuse_last >= 0: the backward starts at that blob and the term may ride on it
+StyleShape style_shape(const st_ctx* c, const ActSet& a, int b);
+StyleTerm style_term(const st_ctx* c, const ActSet& a, int b, const BlobRoi* roi = nullptr, bool target = false, int fuse_last = -1);
+size_t style_split_scratch(int C, int hw);        // elements of c->dsplit the split-operand style gradient of such a blob needs; 0: the split kernels refuse it
+// launch_gram_reduce's contract over the term's Gram partials
+int style_gram(st_ctx* c, const ActSet& a, const StyleTerm& t, const float* target, float* out, int out_ld, double divisor, float* partial, int* n_partial);
+// launch_style_grad's contract with D in c->dbuf; the partials go to c->s2_part[b], their count to *np.  OPS_FUSED ignores dst / fused / accumulate
+int style_grad(st_ctx* c, const ActSet& a, const StyleTerm& t, float* dst, float c2, int fused, float sw, int accumulate, int* np);
+int ensure_dbuf(st_ctx* c);                       // [C][MPad] scratch for D = G - G_style, sized for the widest blob, zeroed once
+int ensure_layer_part(st_ctx* c, int b);
+// the content / deep-dream term of an active blob of c->act: n_norm divides its coefficients, part (nullable) takes the four sums
+LayerElemArgs layer_elem_args(const st_ctx* c, const ActiveLayer& al, double n_norm, int write, float* part, const BlobRoi* roi = nullptr);
 // ---------------------------------------------------------------------------------------- engine_objective.cpp
 int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, bool adam, float* x_next);
 int read_trace(st_ctx* c, double* trace, float* loss);

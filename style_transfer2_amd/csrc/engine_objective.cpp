@@ -35,18 +35,13 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
         const size_t n = (size_t)C * hw;
         if (!c->inject[b]) ST_TRY(c->inject[b].alloc(n));
         c->inject_roi_zero[b] = 0;
-        if (!c->layer_part[b]) ST_TRY(c->layer_part[b].alloc(5 * kMaxPartials));
+        ST_TRY(ensure_layer_part(c, b));
         float* part = c->layer_part[b];
         float* nrm = c->norms + b * 3;
         int* cnt = &c->cnt[b * 6];
         bool wrote = false;
         if (al.c || al.d) {
-            LayerElemArgs e{};
-            e.feat = a.data[b]; e.target = al.c ? c->content_feat[b] : nullptr; e.inject = c->inject[b];
-            e.n = n; e.cn_coef = (float)(2.0 / (double)n); e.dn_coef = (float)(-2.0 / (double)n);
-            e.cw = al.cw; e.dw = al.dw; e.content = al.c; e.deepdream = al.d;
-            e.norm_c = nrm + 0; e.norm_d = nrm + 2;
-            e.part_d2 = part; e.part_gc2 = part + kMaxPartials; e.part_f2 = part + 2 * kMaxPartials; e.part_gd2 = part + 3 * kMaxPartials;
+            LayerElemArgs e = layer_elem_args(c, al, (double)n, 1, part);
             const bool need_norm = (al.c && !c->norm_valid[b * 3 + 0]) || (al.d && !c->norm_valid[b * 3 + 2]);
             int np = 0;
             if (need_norm) {      // first evaluation after reset(): norms are captured (worker.py:253-254,274-275)
@@ -62,47 +57,17 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
             wrote = true;
         }
         if (al.s) {
-            if (!c->dbuf) {          // [C][MPad] scratch for D = G - G_style, sized for the widest blob
-                size_t cc = 1;
-                for (int i = 0; i < c->nb; ++i) cc = std::max(cc, (size_t)a.C[i] * conv_mpad(a.C[i]));
-                ST_TRY(c->dbuf.alloc(cc));
-                HIP_TRY(hipMemsetAsync(c->dbuf, 0, cc * sizeof(float), c->stream));
-            }
-            // bf16 path: the Gram of the CURRENT features and F of the style gradient are taken from the blob's bf16 copy where this
-            // forward wrote one the kernels can take (the style targets stay fp32 Grams)
-            const FwdRoute& fr = a.plan.fwd[b];
-            const bool s16 = !c->tile.on && fr.style16;
-            if (!fr.out32 && !(fr.out16 && fr.style_all16)) return fail(ST_ERR_STATE, "internal: style blob %d has neither an fp32 nor a usable bf16 copy", b);
-            ST_TRY(gram_into(c, a.data[b], C, hw, c->style_gram[b], c->dbuf, conv_mpad(C), part + 4 * kMaxPartials, &cnt[4], s16 ? a.data16[b] : nullptr));
+            ST_TRY(ensure_dbuf(c));
+            // which kernels, on which copy of the blob (bf16 operands: the copy where this forward wrote one the kernels take; norm
+            // known: the gradient may ride on the data-gradient conv above this blob, and only its trace value is taken here)
+            const StyleTerm t = style_term(c, a, b, nullptr, false, want_grad ? last : -1);
+            ST_TRY(style_gram(c, a, t, c->style_gram[b], c->dbuf, conv_mpad(C), (double)C * hw, part + 4 * kMaxPartials, &cnt[4]));
             const float c2 = (float)(2.0 / ((double)C * C * (double)n));
-            // bf16 path, norm known: the gradient rides on the data-gradient conv above this blob; only its trace value is taken here
-            const bool fuse = want_grad && s16 && c->norm_valid[b * 3 + 1] && style_fuse_ok(c, a, b, last);
-            // st_set_gram_algo(ctx, 1), fp32 features: the same S from split operands on the bf16 matrix cores (gram_split.hip)
-            const bool ssplit = !s16 && use_gram_split(c, C, hw) && style_grad_split_pack_elems(C) <= c->dsplit.cap();
-            const int need = fuse ? style_s2_trace_blocks(C) : s16 ? style_grad16_blocks(C, (size_t)hw) : ssplit ? style_grad_split_blocks(C, hw) : style_grad_blocks(C, a.h[b], a.w[b]);
-            ST_TRY(c->s2_part[b].reserve(need));
-            if (s16) ST_TRY(c->d16.reserve(style_grad16_pack_elems(C)));
-            const double fl = 2.0 * C * C * (double)hw;
-            auto style_launch = [&](float* dst, int fused, int accumulate) -> int {
-                ProfScope ps(c, s16 ? P_STYLE_GRAD_BF16 : ssplit ? P_STYLE_GRAD_SPLIT : P_STYLE_GRAD, fl, n * (s16 ? 6.0 : 8.0));
-                if (ssplit) HIP_TRY(launch_style_grad_split(c->dbuf, conv_mpad(C), c->dsplit, a.data[b], dst, c2, fused, al.sw, nrm + 1, accumulate, c->s2_part[b], &cnt[5], C, hw, c->stream));
-                else if (s16) HIP_TRY(launch_style_grad16(c->dbuf, conv_mpad(C), c->d16, a.data16[b], dst, c2, fused, al.sw, nrm + 1, accumulate, c->s2_part[b], &cnt[5], C, (size_t)hw, c->stream));
-                else HIP_TRY(launch_style_grad(c->dbuf, a.data[b], dst, c2, fused, al.sw, nrm + 1, accumulate, c->s2_part[b], &cnt[5], C, a.h[b], a.w[b], c->stream));
-                return ST_OK;
-            };
-            if (fuse) {
-                const size_t pe = style_fuse_pack_elems(C, conv_mpad(C));
-                ST_TRY(c->sfuse_w[b].reserve(pe));
-                { ProfScope ps(c, P_MISC, 0, 4.0 * C * C + 2.0 * pe);
-                  HIP_TRY(launch_style_fuse_pack(c->dbuf, conv_mpad(C), C, conv_mpad(C), c2, al.sw, nrm + 1, c->sfuse_w[b], c->stream)); }
-                { ProfScope ps(c, P_STYLE_GRAD, 2.0 * C * C * (double)C, 12.0 * C * C);
-                  HIP_TRY(launch_style_s2_trace(c->dbuf, conv_mpad(C), c->style_gram[b], C, (double)C * hw, c2, c->s2_part[b], &cnt[5], c->stream)); }
-                c->sf_in[b] = a.data16[b]; c->sf_w[b] = c->sfuse_w[b];
-            } else if (c->norm_valid[b * 3 + 1]) {
-                ST_TRY(style_launch(c->inject[b], 1, wrote));
+            if (c->norm_valid[b * 3 + 1]) {
+                ST_TRY(style_grad(c, a, t, c->inject[b], c2, 1, al.sw, wrote, &cnt[5]));
             } else {              // first evaluation: S unscaled -> norm -> saxpy (worker.py:265-269)
                 if (!c->stmp) ST_TRY(c->stmp.alloc(c->max_blob));
-                ST_TRY(style_launch(c->stmp, 0, 0));
+                ST_TRY(style_grad(c, a, t, c->stmp, c2, 0, al.sw, 0, &cnt[5]));
                 { ProfScope ps(c, P_FINALIZE, 0, 0);
                   HIP_TRY(launch_finalize_norm(c->s2_part[b], cnt[5], (double)n, nrm + 1, c->stream)); }
                 c->norm_valid[b * 3 + 1] = 1;

@@ -11,35 +11,13 @@ static bool blob_active(const st_ctx* c, int b)
     return false;
 }
 
-// Will the style term of blob b (a style layer) run entirely on the blob's bf16 copy (gram16.hip + style16.hip)?  Decided from
-// shapes only, so that the forward (which may then skip the fp32 blob) and the objective agree.
-static bool style_runs16(const st_ctx* c, const ActSet& a, int b)
-{
-    if (!c->bf16 || b < 1 || !c->topo[b - 1].is_conv) return false;
-    const int C = a.C[b], hw = a.h[b] * a.w[b];
-    if (!(conv16_ok(c, C) && style_grad16_ok(C, (size_t)hw) && C % 8 == 0)) return false;
-    // tile-sharded mode: the region-of-interest forms of both kernels take any region (ragged last step, 4-byte stores when the
-    // region's rows are not 16-byte aligned); ST2_TILE_STYLE16=0 keeps the fp32 region-of-interest kernels
-    if (c->tile.on) return !env_off("ST2_TILE_STYLE16");
-    return hw % 64 == 0 && gram16_ok(C, hw, gram_plan16(C, hw));
-}
-
 // lean evaluation: does anything read blob b in fp32?  Content / deep-dream terms do (layer_elem_k); a style term only when
-// its Gram / gradient cannot run on the bf16 copy.
-static bool blob_needs32(const st_ctx* c, const ActSet& a, int b)
+// its Gram / gradient cannot both run on the bf16 copy (sty: style_shape of the style blobs).
+static bool blob_needs32(const st_ctx* c, const std::vector<StyleShape>& sty, int b)
 {
     for (const ActiveLayer& al : c->active)
-        if (al.blob == b && (al.c || al.d || (al.s && !style_runs16(c, a, b)))) return true;
+        if (al.blob == b && (al.c || al.d || (al.s && !sty[b].gram16))) return true;
     return false;
-}
-
-// May the style gradient of blob b ride on the data-gradient conv of the layer above it (conv3x3_mfma_bf16.hip, fused style term)?
-bool style_fuse_ok(const st_ctx* c, const ActSet& a, int b, int last)
-{
-    // (ST2_STYLE_FUSE is read per evaluation: the tests compare both flows in one process)
-    if (env_off("ST2_STYLE_FUSE") || !style_runs16(c, a, b) || b + 1 > last || a.C[b] % 32 != 0) return false;
-    const Layer& up = c->topo[b];                       // layer b + 1: consumes blob b
-    return up.is_conv && up.loaded && conv16_ok(c, up.cout) && up.cin == a.C[b];
 }
 
 // does the layer that consumes blob i run on the bf16 matrix cores?
@@ -87,6 +65,9 @@ void plan_forward(const st_ctx* c, const ActSet& a, int last, bool lean, std::ve
     // (both read per forward: the tests compare both)
     const bool want_bits = lean && c->bf16 && !env_off("ST2_MASK_BITS");
     const bool want_amap = !env_off("ST2_POOL_AMAP");
+    // the style terms of this evaluation, from shapes alone: the forward (which may then skip an fp32 blob) and the objective agree
+    std::vector<StyleShape> sty(c->nb, StyleShape{});
+    for (const ActiveLayer& al : c->active) if (al.s) sty[al.blob] = style_shape(c, a, al.blob);
     for (int i = 1; i <= last; ++i) {
         const Layer& L = c->topo[i - 1];
         FwdRoute& r = fwd[i];
@@ -109,9 +90,7 @@ void plan_forward(const st_ctx* c, const ActSet& a, int last, bool lean, std::ve
         }
         const bool conv_next16 = feeds_conv16(c, a, i, last);
         // ... or does the style gradient of this blob read the bf16 copy (style16.hip)?
-        bool next16 = conv_next16;
-        if (c->bf16 && conv16_ok(c, L.cout) && style_grad16_ok(L.cout, (size_t)H * W))
-            for (const ActiveLayer& al : c->active) if (al.blob == i && al.s) next16 = true;
+        const bool next16 = conv_next16 || sty[i].grad16;
         // lean: the data gradient of the bf16 conv above masks with blob i -- through a sign map (1 bit per element, written by
         // this launch's epilogue) instead of the bf16 copy (16 bits)
         const bool bits_i = want_bits && conv_next16 && L.cout % 32 == 0;
@@ -121,7 +100,7 @@ void plan_forward(const st_ctx* c, const ActSet& a, int last, bool lean, std::ve
         if (c->bf16 && conv16_ok(c, L.cin) && fwd[i - 1].out16) {
             r.kind = F_CONV16;
             r.out16 = next16;
-            if (lean && !blob_needs32(c, a, i) && i < last) {
+            if (lean && !blob_needs32(c, sty, i) && i < last) {
                 // (a weighted blob gets an injected diff: classic pool backward; an average pool runs stand-alone on the fp32 blob
                 // unless st_set_pool_algo(ctx, 1) and its backward can go through the sign map: ave_pool_fuse_ok)
                 if ((next_max_pool || (next_ave_pool && ave_pool_fuse_ok(c, a, i))) && !blob_active(c, i) && conv16_resolve(shape16(L.cin, L.cout, H, W)).can_pool) {
@@ -164,16 +143,11 @@ void plan_forward(const st_ctx* c, const ActSet& a, int last, bool lean, std::ve
             r.out16 = next16;
             r.pack16 = next16 && L.cout % 8 != 0;          // (otherwise the epilogue writes the bf16 copy too)
             // lean: conv1_1's fp32 blob is written only if something reads it (conv1_2, the ReLU mask and a style term take the copy)
-            if (lean && next16 && !r.pack16 && conv_next16 && i < last && !blob_needs32(c, a, i)) r.out32 = false;
+            if (lean && next16 && !r.pack16 && conv_next16 && i < last && !blob_needs32(c, sty, i)) r.out32 = false;
             r.bits = r.kind == F_FIRST_SPLIT && bits_i && next16 && !r.pack16;
         }
     }
-    for (const ActiveLayer& al : c->active) {
-        const int b = al.blob;
-        if (!al.s || b < 1 || b > last || !c->topo[b - 1].is_conv) continue;
-        fwd[b].style16 = fwd[b].out16 && style_grad16_ok(a.C[b], (size_t)a.h[b] * a.w[b]);
-        fwd[b].style_all16 = fwd[b].out16 && style_runs16(c, a, b);
-    }
+    for (int b = 1; b <= last; ++b) { fwd[b].style16 = fwd[b].out16 && sty[b].grad16; fwd[b].style_all16 = fwd[b].out16 && sty[b].gram16; }
 }
 
 // ----------------------------------------------------------------------------------------- backward

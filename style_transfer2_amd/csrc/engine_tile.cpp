@@ -5,8 +5,6 @@
 // This context runs the window (tile + apron) of one rank.  Every reduction is restricted to the tile's region
 // of each blob and left UN-normalised in a flat device buffer that the caller all-reduces (RCCL) between phases.
 namespace st2e {
-struct BlobRoi { int y0, x0, y1, x1; double n_global; };
-
 // the tile's region in blob b of the activation set `a` that holds the window (geometry `t`: the iterate's c->tile, or the style
 // image's of st_tile_style_partials)
 BlobRoi tile_roi(const st_ctx* c, const ActSet& a, const TileGeom& t, int b)
@@ -22,48 +20,13 @@ BlobRoi tile_roi(const st_ctx* c, const ActSet& a, const TileGeom& t, int b)
     return r;
 }
 BlobRoi tile_roi(const st_ctx* c, int b) { return tile_roi(c, c->act, c->tile, b); }
-// bf16 operands: does the style term of blob b run on its bf16 copy here (region-of-interest forms of gram16.hip / style16.hip)?
-bool tile_style16(const st_ctx* c, int b)
-{
-    const FwdRoute& fr = c->act.plan.fwd[b];
-    return fr.out16 && fr.style_all16;
-}
-
-// the style gradient of blob b over the tile's region (worker.py:262-269): fp32 kernel on the fp32 blob, or -- bf16 operands -- the
-// bf16 kernel on the blob's bf16 copy, which touches the region's pixels only (the inject buffer is zeroed outside it once)
-int tile_style_grad(st_ctx* c, int b, const BlobRoi& r, float* dst, bool is_inject, float c2, int fused, float sw, int accumulate, int* np)
-{
-    const ActSet& a = c->act;
-    const int C = a.C[b];
-    if (!tile_style16(c, b)) {
-        if (!a.plan.fwd[b].out32) return fail(ST_ERR_STATE, "internal: style blob %d has no fp32 copy", b);
-        const int need = style_grad_blocks(C, a.h[b], a.w[b]);
-        ST_TRY(c->s2_part[b].reserve(need));
-        PixRoi pr{r.y0, r.x0, r.y1, r.x1};
-        HIP_TRY(launch_style_grad(c->dbuf, a.data[b], dst, c2, fused, sw, c->norms + b * 3 + 1, accumulate, c->s2_part[b], np, C, a.h[b], a.w[b], c->stream, &pr));
-        return ST_OK;
-    }
-    const int rw = r.x1 - r.x0, rh = r.y1 - r.y0;
-    const size_t hw = (size_t)rw * rh, plane = (size_t)a.h[b] * a.w[b];
-    const int need = style_grad16_blocks(C, hw);
-    ST_TRY(c->s2_part[b].reserve(need));
-    ST_TRY(c->d16.reserve(style_grad16_pack_elems(C)));
-    if (is_inject && !accumulate && !c->inject_roi_zero[b]) {
-        HIP_TRY(hipMemsetAsync(dst, 0, (size_t)C * plane * sizeof(float), c->stream));
-        c->inject_roi_zero[b] = 1;
-    }
-    GramRoi roi{r.y0, r.x0, rw, a.w[b], plane};
-    HIP_TRY(launch_style_grad16(c->dbuf, conv_mpad(C), c->d16, a.data16[b], dst, c2, fused, sw, c->norms + b * 3 + 1, accumulate, c->s2_part[b], np,
-                                C, hw, c->stream, &roi));
-    return ST_OK;
-}
 
 // D = Graw / n_global - G_style into dbuf ([C][MPad]); sum D^2 -> pd[k]
 int tile_style_D(st_ctx* c, int b, const float* graw, double n_global, float* pd_slot)
 {
     const ActSet& a = c->act;
     const int C = a.C[b];
-    if (!c->layer_part[b]) ST_TRY(c->layer_part[b].alloc(5 * kMaxPartials));
+    ST_TRY(ensure_layer_part(c, b));
     float* part = c->layer_part[b] + 4 * kMaxPartials;
     int np = 0;
     GramPlan one{}; one.splits = 1;
@@ -121,35 +84,17 @@ int st_tile_forward(st_ctx* c, float** dev_ptr, int* n_floats)
     for (const ActiveLayer& al : c->active) {
         const int b = al.blob, C = a.C[b];
         const BlobRoi r = tile_roi(c, b);
-        const size_t n = (size_t)C * a.h[b] * a.w[b];
-        if (!c->layer_part[b]) ST_TRY(c->layer_part[b].alloc(5 * kMaxPartials));
+        ST_TRY(ensure_layer_part(c, b));
         float* part = c->layer_part[b];
         if (al.c || al.d) {
-            LayerElemArgs e{};
-            e.feat = a.data[b]; e.target = al.c ? c->content_feat[b] : nullptr; e.n = n;
-            e.cn_coef = (float)(2.0 / r.n_global); e.dn_coef = (float)(-2.0 / r.n_global);
-            e.content = al.c; e.deepdream = al.d; e.write = 0;
-            e.part_d2 = part; e.part_gc2 = part + kMaxPartials; e.part_f2 = part + 2 * kMaxPartials; e.part_gd2 = part + 3 * kMaxPartials;
-            e.h = a.h[b]; e.w = a.w[b]; e.ry0 = r.y0; e.rx0 = r.x0; e.ry1 = r.y1; e.rx1 = r.x1;
             int np = 0;
-            HIP_TRY(launch_layer_elem(e, &np, c->stream));
+            HIP_TRY(launch_layer_elem(layer_elem_args(c, al, r.n_global, 0, part, &r), &np, c->stream));
             for (int k = 0; k < 4; ++k) HIP_TRY(launch_sum_partials(part + k * kMaxPartials, np, c->tile.p1 + pos + k, c->stream));
         }
         pos += 4;
         if (al.s) {
-            const int rw = r.x1 - r.x0, rh = r.y1 - r.y0, hw = rw * rh;
-            GramPlan pl;
-            GramRoi roi{r.y0, r.x0, rw, a.w[b], (size_t)a.h[b] * a.w[b]};
-            if (tile_style16(c, b)) {       // bf16 operands: the partials on the bf16 matrix cores, from the blob's bf16 copy (gram16.hip)
-                ST_TRY(ensure_gram_bufs(c, C, hw, pl, true));
-                HIP_TRY(launch_gram16_partial(a.data16[b], c->gram_slabs, C, hw, pl, c->stream, &roi));
-            } else {
-                if (!a.plan.fwd[b].out32) return fail(ST_ERR_STATE, "internal: style blob %d has no fp32 copy", b);
-                ST_TRY(ensure_gram_bufs(c, C, hw, pl));
-                HIP_TRY(launch_gram_partial(a.data[b], c->gram_slabs, C, hw, pl, c->stream, &roi));
-            }
-            // raw sum over this rank's region (divisor 1, no target), contiguous C x C
-            HIP_TRY(launch_gram_reduce(c->gram_slabs, c->gram_fold, nullptr, c->tile.p1 + pos, C, nullptr, nullptr, C, 1.0, pl, c->stream));
+            // raw sum over this rank's region (divisor 1, no target), contiguous C x C; bf16 operands: from the blob's bf16 copy
+            ST_TRY(style_gram(c, a, style_term(c, a, b, &r), nullptr, c->tile.p1 + pos, C, 1.0, nullptr, nullptr));
             pos += (size_t)C * C;
         }
     }
@@ -173,12 +118,7 @@ int st_tile_losses(st_ctx* c, float** dev_ptr, int* n_floats)
     ST_TRY(c->tile.p2.reserve(std::max(n_style, 1)));
     ST_TRY(c->tile.pd.reserve(std::max(n_style, 1)));
     c->tile.s2_in_p2 = missing;
-    if (!c->dbuf) {
-        size_t cc = 1;
-        for (int i = 0; i < c->nb; ++i) cc = std::max(cc, (size_t)a.C[i] * conv_mpad(a.C[i]));
-        ST_TRY(c->dbuf.alloc(cc));
-        HIP_TRY(hipMemsetAsync(c->dbuf, 0, cc * sizeof(float), c->stream));
-    }
+    ST_TRY(ensure_dbuf(c));
     size_t pos = 0;
     for (const ActiveLayer& al : c->active) {
         const int b = al.blob, C = a.C[b];
@@ -212,14 +152,8 @@ int st_tile_losses_finish(st_ctx* c)
         float* nrm = c->norms + b * 3;
         bool wrote = false;
         if (al.c || al.d) {
-            LayerElemArgs e{};
-            e.feat = a.data[b]; e.target = al.c ? c->content_feat[b] : nullptr; e.inject = c->inject[b]; e.n = n;
-            e.cn_coef = (float)(2.0 / r.n_global); e.dn_coef = (float)(-2.0 / r.n_global);
-            e.cw = al.cw; e.dw = al.dw; e.content = al.c; e.deepdream = al.d; e.write = 1;
-            e.norm_c = nrm + 0; e.norm_d = nrm + 2;
-            e.h = a.h[b]; e.w = a.w[b]; e.ry0 = r.y0; e.rx0 = r.x0; e.ry1 = r.y1; e.rx1 = r.x1;
             int np = 0;
-            HIP_TRY(launch_layer_elem(e, &np, c->stream));
+            HIP_TRY(launch_layer_elem(layer_elem_args(c, al, r.n_global, 1, nullptr, &r), &np, c->stream));
             wrote = true;
         }
         pos += 4;
@@ -227,15 +161,14 @@ int st_tile_losses_finish(st_ctx* c)
             ST_TRY(tile_style_D(c, b, c->tile.p1 + pos, r.n_global, c->tile.pd + k));
             const float c2 = (float)(2.0 / ((double)C * C * r.n_global));
             int np = 0;
-            if (two_step) {
-                // norm from the all-reduced sum S^2 of the first pass (st_tile_style_raw), then saxpy
-                if (!c->norm_valid[b * 3 + 1]) {
-                    HIP_TRY(launch_finalize_norm(c->tile.p2 + k, 1, r.n_global, nrm + 1, c->stream));
-                    c->norm_valid[b * 3 + 1] = 1;
-                }
-                ST_TRY(tile_style_grad(c, b, r, c->inject[b], true, c2, 1, al.sw, wrote, &np));
-            } else {
-                ST_TRY(tile_style_grad(c, b, r, c->inject[b], true, c2, 1, al.sw, wrote, &np));
+            // norm from the all-reduced sum S^2 of the first pass (st_tile_style_raw), then saxpy
+            if (two_step && !c->norm_valid[b * 3 + 1]) {
+                HIP_TRY(launch_finalize_norm(c->tile.p2 + k, 1, r.n_global, nrm + 1, c->stream));
+                c->norm_valid[b * 3 + 1] = 1;
+            }
+            // (region only: the fp32 kernel on the fp32 blob, or -- bf16 operands -- the bf16 kernel on the blob's bf16 copy)
+            ST_TRY(style_grad(c, a, style_term(c, a, b, &r), c->inject[b], c2, 1, al.sw, wrote, &np));
+            if (!two_step) {
                 // sum S^2 of this rank's region -> p3 tail (all-reduced with the image sums)
                 ST_TRY(c->tile.p3.reserve(6 + kMaxTraceLayers));
                 HIP_TRY(launch_sum_partials(c->s2_part[b], np, c->tile.p3 + 6 + k, c->stream));
@@ -265,7 +198,7 @@ int st_tile_style_raw(st_ctx* c)
         const float c2 = (float)(2.0 / ((double)C * C * r.n_global));
         if (!c->stmp) ST_TRY(c->stmp.alloc(c->max_blob));
         int np = 0;
-        ST_TRY(tile_style_grad(c, b, r, c->stmp, false, c2, 0, al.sw, 0, &np));
+        ST_TRY(style_grad(c, a, style_term(c, a, b, &r), c->stmp, c2, 0, al.sw, 0, &np));
         HIP_TRY(launch_sum_partials(c->s2_part[b], np, c->tile.p2 + k, c->stream));
         pos += (size_t)C * C;
         ++k;
@@ -477,21 +410,8 @@ int st_tile_style_partials(st_ctx* c, const void* hwc, int H, int W, int is_u8, 
                 r = fail(ST_ERR_ARG, "the style tile has no region in blob %d of its window", b);
                 break;
             }
-            if (!a->plan.fwd[b].out32) { r = fail(ST_ERR_STATE, "internal: style blob %d has no fp32 copy", b); break; }
-            const int hw = rw * rh;
-            // the fp32 region-of-interest kernel on the fp32 blob under every precision and gram_algo, as st_set_style's targets under bf16
-            GramPlan pl;
-            r = ensure_gram_bufs(c, C, hw, pl);
-            if (r != ST_OK) break;
-            GramRoi gr{roi.y0, roi.x0, rw, a->w[b], (size_t)a->h[b] * a->w[b]};
-            hipError_t e;
-            { ProfScope ps(c, P_GRAM, 2.0 * C * C * (double)hw, 4.0 * C * (double)hw);
-              e = launch_gram_partial(a->data[b], c->gram_slabs, C, hw, pl, c->stream, &gr); }
-            if (e == hipSuccess) {
-                ProfScope ps(c, P_GRAM_REDUCE, 0, 4.0 * (double)pl.slab_floats);
-                e = launch_gram_reduce(c->gram_slabs, c->gram_fold, nullptr, c->tile.sp + pos, C, nullptr, nullptr, C, 1.0, pl, c->stream);
-            }
-            if (e != hipSuccess) { r = fail(ST_ERR_HIP, "style Gram partials of blob %d: %s", b, hipGetErrorString(e)); break; }
+            // a target: the fp32 region-of-interest kernel on the fp32 blob under every precision and gram_algo, as st_set_style's under bf16
+            r = style_gram(c, *a, style_term(c, *a, b, &roi, true), nullptr, c->tile.sp + pos, C, 1.0, nullptr, nullptr);
             pos += (size_t)C * C;
         }
         (void)hipStreamSynchronize(c->stream);

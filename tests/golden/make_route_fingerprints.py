@@ -18,11 +18,12 @@ and never on the tree a test run is about to judge.  Public Python API only.  Th
   calls     first opfunc (norms captured), second opfunc, an Adam step (lean fp32 inside the iteration); once per net / path / size
             the ranged hooks: forward to a middle blob, two backwards with diffs injected at two blobs, one of them a pool blob
   switches  each per-call environment switch at its non-default value, one at a time, bench table, on the paths it affects; the bf16
-            ones also with the conv tile forced that pools and unpools (see SWITCHES)
+            ones also with the conv tile forced that pools and unpools (see SWITCHES); on the fp32 paths the split-operand Gram /
+            style gradient (`gram_algo=1`: conv1_1's 64 channels and the mixed net's 20 are refused, odd sizes mix both GEMMs)
 A call the engine refuses is recorded as its error and must be refused the same way.
 
 The fixture keeps one digest per case (`digest`: of launches, FLOPs and bytes of every class; any difference in any figure changes
-it), not the figures themselves: 972 cases of a dozen classes are half a megabyte.  To see WHICH figure of a failing case moved, write
+it), not the figures themselves: 1053 cases of a dozen classes are half a megabyte.  To see WHICH figure of a failing case moved, write
 the figures of both commits with --figures FILE and compare the case in the two files.
 """
 import argparse
@@ -186,6 +187,12 @@ def run_group(net, precision, algo):
             finally:
                 for var in env:
                     del os.environ[var]
+        if precision == 'fp32':
+            eng.set_gram_algo(1)
+            try:
+                _objective_calls(out, '%s/bench/gram_algo=1' % base, model, (h, w), tables[0][1])
+            finally:
+                eng.set_gram_algo(0)
         # the ranged hooks
         x = (np.random.RandomState(h + w).randn(1, 3, h, w) * 40).astype(F32)
         out[base + '/hooks/forward_' + mid] = _record(eng, lambda: eng.forward(x, mid))

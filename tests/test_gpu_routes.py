@@ -6,7 +6,7 @@ tests/golden/make_route_fingerprints.py, which also defines the cases run here. 
 mask sources, fused style chunks and skipped outputs, so equal figures mean equal routes.
 
 The figures are sums of integers and of multiples of 1/8 far below 2^53: exact equality, no tolerance.  The fixture keeps one digest
-per case over all its figures (the figures of 972 cases are half a megabyte); a failing case prints what the tree gave, and the
+per case over all its figures (the figures of 1053 cases are half a megabyte); a failing case prints what the tree gave, and the
 generator's --figures option writes the recorded commit's figures to compare with.
 The whole file takes about 6 s on an MI355X."""
 
