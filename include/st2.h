@@ -277,6 +277,13 @@ int st_tile_plan(st_ctx* ctx, int phase, int n_peers, const st_tile_peer* peers)
  * collective sequence is the same either way (round 5: the few KB of image-space sums that only the trace reads are reduced on every
  * call), so ranks may choose NULL independently of each other. */
 int st_tile_step(st_ctx* ctx, double* trace);
+/* The trace of the last complete evaluation of the tile-sharded image, finished from the reduced sums in the reference's fp32 order
+ * (worker.py:249-301: the per-layer losses and gradient RMS values, the scd / tv / p losses, the total): st_trace_len(ctx) values, the
+ * layout of st_step's.  st_tile_step finishes its trace through it; a caller that drives the phases itself calls it once p1, p2 (first
+ * evaluation) and p3 are all-reduced in place -- the device buffers stay valid until the next st_tile_forward, and every rank then
+ * finishes the same numbers.  Waits for the engine's stream.  ST_ERR_STATE before st_tile_configure, and until an evaluation has reached
+ * st_tile_update / st_tile_gradient under the current weights. */
+int st_tile_trace(st_ctx* ctx, double* trace);
 int st_tile_get_tile(st_ctx* ctx, float* out_hwc);                           /* this rank's tile of the current iterate, (th, tw, 3) deprocessed */
 
 /* ---- the style targets of a tile-sharded job, sharded as well -------------------------------------------------------------------

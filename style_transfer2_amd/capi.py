@@ -113,6 +113,7 @@ PROTOTYPES = {
     'st_comm_barrier': (c_int, [c_void_p]),
     'st_tile_plan': (c_int, [c_void_p, c_int, c_int, POINTER(TilePeer)]),
     'st_tile_step': (c_int, [c_void_p, c_void_p]),
+    'st_tile_trace': (c_int, [c_void_p, c_void_p]),
     'st_tile_get_tile': (c_int, [c_void_p, c_void_p]),
     'st_tile_style_partials': (c_int, [c_void_p, c_void_p] + [c_int] * 12 + [POINTER(c_void_p), POINTER(c_int)]),
     'st_tile_style_commit': (c_int, [c_void_p]),

@@ -112,6 +112,23 @@ inline bool nonzero(float w) { return fabsf(w) > 1e-15f; }   // NaN compares fal
 // one rank's share of a tile-sharded image, in global pixels: the gH x gW image, the origin of the window this context holds, the tile
 struct TileGeom { int gH = 0, gW = 0, wy0 = 0, wx0 = 0, ty0 = 0, tx0 = 0, ty1 = 0, tx1 = 0; };
 struct BlobRoi { int y0, x0, y1, x1; double n_global; };    // the tile's region of one blob; n_global: elements of the blob of the WHOLE image
+struct BlobSize { int h, w, stride; double n; };            // blob b of a gH x gW image: height, width, total stride of its pools, elements
+
+// ------------------------------------------------------------------------------------- objective terms
+// The layout of one evaluation's objective, resolved once (objective_terms, engine_objective.cpp): per active row what it is normalised
+// by, its region, and the slots it owns in the phase buffers of the tile-sharded mode
+struct ObjTerm {                       // one row of c->active, laid out
+    ActiveLayer al; int b, C;
+    size_t n;                          // elements of the blob this context holds
+    double n_norm;                     // elements of the blob of the WHOLE image (== n without a tile)
+    BlobRoi roi; bool has_roi;         // the tile's region (tile mode), else the whole blob
+    size_t sums;                       // offset of its four sums [d2, gc2, F2, gd2] in the phase-1 buffer
+    size_t gram;                       // offset of its raw C x C Gram sums there (style rows), else kNoSlot
+    int k;                             // ordinal among the style rows (slot in p2 / pd / p3 + 6), else -1
+    const BlobRoi* region() const { return has_roi ? &roi : nullptr; }
+};
+constexpr size_t kNoSlot = ~(size_t)0;
+struct ObjTerms { std::vector<ObjTerm> t; int last = -1; size_t n1 = 0; int n_style = 0; };     // last: deepest weighted blob (-1: none); n1: floats of the phase-1 buffer
 
 // ------------------------------------------------------------------------------------- style term
 // The style term of one blob, resolved once (engine_style.cpp): the kernel family of each of its two GEMMs, what the launches need and book
@@ -247,6 +264,7 @@ struct st_ctx {
         bool on = false;
         DevBuf<float> p1, p2, p3, pd;              // reduce buffers (device)
         bool s2_in_p2 = false;
+        bool evaluated = false;                    // the phase buffers hold a complete evaluation (forward .. image pass) of the current weights: st_tile_trace may finish it
         DevBuf<float> wgrad;                       // window gradient (3, wh, ww)
         bool fused = false;                        // inside st_tile_step: the phases do not synchronise the stream on their own
         // fused L-BFGS over the sharded image (engine_comm.cpp): this rank's tile of x as a compact (3, th, tw) vector, the sums of
@@ -364,6 +382,14 @@ int ensure_layer_part(st_ctx* c, int b);
 // the content / deep-dream term of an active blob of c->act: n_norm divides its coefficients, part (nullable) takes the four sums
 LayerElemArgs layer_elem_args(const st_ctx* c, const ActiveLayer& al, double n_norm, int write, float* part, const BlobRoi* roi = nullptr);
 // ---------------------------------------------------------------------------------------- engine_objective.cpp
+// The table: no HIP call, no allocation, nothing in the context changes; rebuilt per call (the tests change weights and switches between
+// evaluations).  `a` holds the geometry of the evaluation (act_ensure has run); tile: the geometry of a tile-sharded context, else NULL.
+// It is also the preflight: ST_ERR_STATE where a weighted row lacks its content features or its style target
+int objective_terms(const st_ctx* c, const ActSet& a, const TileGeom* tile, ObjTerms& terms);
+BlobSize blob_size(const st_ctx* c, int b, int gH, int gW);
+BlobRoi tile_roi(const st_ctx* c, const ActSet& a, const TileGeom& t, int b);      // the tile's region in blob b of the activation set that holds the window
+// launch_image_pass's arguments for the image x: adam: the fused update into x_next (the only place that names Adam's constants)
+ImagePassArgs image_pass_args(const st_ctx* c, const float* x, const float* scd, float* grad, bool adam, float* x_next);
 int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, bool adam, float* x_next);
 int read_trace(st_ctx* c, double* trace, float* loss);
 // ---------------------------------------------------------------------------------------- engine_step.cpp

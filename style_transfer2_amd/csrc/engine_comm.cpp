@@ -159,19 +159,15 @@ static int comm_exchange(st_ctx* c, int phase, float* src, int sh, int sw, float
 
 // Trace scalars from the reduced sums, in the reference's fp32 order (worker.py:249-301); the layout of the single-GPU engine's
 // trace: 6 per active layer + 8.  p1 / p2 / p3 are the all-reduced phase buffers, pd the sum D^2 per style layer.
-static void tile_trace(const st_ctx* c, const float* p1, const float* s2, const float* p3, const float* pd, const float* norms, double* out)
+static void tile_trace(const st_ctx* c, const ObjTerms& terms, const float* p1, const float* s2, const float* p3, const float* pd, const float* norms, double* out)
 {
-    const ActSet& a = c->act;
     float loss = 0.f;
-    size_t pos = 0;
-    int k = 0, o = 0;
-    for (const ActiveLayer& al : c->active) {
-        const int b = al.blob, C = a.C[b];
-        int gh = c->tile.gH, gw = c->tile.gW;
-        for (int i = 1; i <= b; ++i) if (!c->topo[i - 1].is_conv) { gh = pooled_size(gh); gw = pooled_size(gw); }
-        const float n = (float)((double)C * gh * gw);
-        const float* sums = p1 + pos;
-        pos += 4;
+    int o = 0;
+    for (const ObjTerm& t : terms.t) {
+        const ActiveLayer& al = t.al;
+        const int b = t.b, C = t.C, k = t.k;
+        const float n = (float)t.n_norm;
+        const float* sums = p1 + t.sums;
         float v[6] = {0, 0, 0, 0, 0, 0};
         if (al.c) {
             const float cn = norms[b * 3 + 0];
@@ -184,8 +180,6 @@ static void tile_trace(const st_ctx* c, const float* p1, const float* s2, const 
             v[2] = al.sw * (pd[k] / (float)(C * C)) / sn;
             v[3] = fabsf(al.sw / sn) * sqrtf(s2[k] / n);
             loss += v[2];
-            pos += (size_t)C * C;
-            ++k;
         }
         if (al.d) {
             const float dn = norms[b * 3 + 2];
@@ -329,18 +323,18 @@ int st_tile_plan(st_ctx* c, int phase, int n_peers, const st_tile_peer* peers)
 // -> losses (first evaluation: raw style gradients -> all-reduce) -> ranged backward -> overlap-add of the window gradients -> the
 // torus ring of the TV stencil -> image-space pass.  adam: that pass is the fused TV / p-norm / Adam update into x[cur ^ 1]; else it
 // leaves the combined gradient of the tile's pixels in c->grad (window layout).  The phase-3 sums are all-reduced either way.
-struct TileEval { float *p1 = nullptr, *p2 = nullptr, *p3 = nullptr; int n1 = 0, n2 = 0, n3 = 0; };
-static int tile_evaluate(st_ctx* c, bool adam, TileEval& e, bool want_trace)
+static int tile_evaluate(st_ctx* c, bool adam)
 {
     st_ctx::Tile& t = c->tile;
     const int wh = c->H, ww = c->W, th = t.ty1 - t.ty0, tw = t.tx1 - t.tx0;
-    float* wgrad = nullptr;
-    ST_TRY(st_tile_forward(c, &e.p1, &e.n1));                                   // phase 1: forward, region sums + raw Gram sums
-    ST_TRY(comm_allreduce(c, e.p1, e.n1));
-    ST_TRY(st_tile_losses(c, &e.p2, &e.n2));                                    // phase 2: norms (first evaluation: raw style gradients)
-    if (e.n2) {
+    float *p = nullptr, *wgrad = nullptr;
+    int n = 0;
+    ST_TRY(st_tile_forward(c, &p, &n));                                         // phase 1: forward, region sums + raw Gram sums
+    ST_TRY(comm_allreduce(c, p, n));
+    ST_TRY(st_tile_losses(c, &p, &n));                                          // phase 2: norms (first evaluation: raw style gradients)
+    if (n) {
         ST_TRY(st_tile_style_raw(c));
-        ST_TRY(comm_allreduce(c, e.p2, e.n2));
+        ST_TRY(comm_allreduce(c, p, n));
     }
     ST_TRY(st_tile_losses_finish(c));
     ST_TRY(st_tile_backward(c, &wgrad));                                        // phase 3: ranged backward on the window
@@ -349,34 +343,13 @@ static int tile_evaluate(st_ctx* c, bool adam, TileEval& e, bool want_trace)
     if (ring_n > c->comm.ring.cap()) { HIP_TRY(hipStreamSynchronize(c->stream)); ST_TRY(c->comm.ring.reserve(ring_n)); }
     HIP_TRY(hipMemsetAsync(c->comm.ring, 0, ring_n * sizeof(float), c->stream));
     ST_TRY(comm_exchange(c, ST_TILE_PLAN_RING, c->x[c->cur], wh, ww, c->comm.ring, th + 2, tw + 2, false));
-    if (adam) ST_TRY(st_tile_update(c, c->comm.ring, &e.p3, &e.n3));            // phase 4: TV / p-norm / Adam on the tile
-    else ST_TRY(st_tile_gradient(c, c->comm.ring, &e.p3, &e.n3));               //          or the combined gradient only
+    if (adam) ST_TRY(st_tile_update(c, c->comm.ring, &p, &n));                  // phase 4: TV / p-norm / Adam on the tile
+    else ST_TRY(st_tile_gradient(c, c->comm.ring, &p, &n));                     //          or the combined gradient only
     // the image-space sums (and, in steady state, the style-gradient sums) feed the TRACE only.  They are reduced on EVERY call all the
     // same (a few KB; until round 4 a caller that passed trace == NULL skipped this collective: ranks that disagreed on NULL for one
-    // iteration then desynchronised the collective sequence and RCCL hung instead of failing) -- trace == NULL now only means that
+    // iteration then desynchronised the collective sequence and RCCL hung instead of failing) -- trace == NULL only means that
     // nothing is read back and nothing waits for the GPU
-    (void)want_trace;
-    ST_TRY(comm_allreduce(c, e.p3, e.n3));
-    return ST_OK;
-}
-
-// the trace of the evaluation just enqueued: the reduced sums cross PCIe (a few KB + the Gram sums), the scalars are finished on the host
-static int tile_read_trace(st_ctx* c, const TileEval& e, double* trace)
-{
-    int n_style = 0;
-    for (const ActiveLayer& al : c->active) n_style += al.s;
-    std::vector<float> &h1 = c->comm.h1, &h2 = c->comm.h2, &h3 = c->comm.h3, &hd = c->comm.hd, &hn = c->comm.hn;      // (kept in the context: grown, never shrunk)
-    auto room = [](std::vector<float>& v, size_t n) { if (v.size() < n) v.resize(n); };
-    room(h1, (size_t)std::max(e.n1, 1)); room(h2, (size_t)std::max(std::max(n_style, e.n2), 1)); room(h3, (size_t)std::max(6 + kMaxTraceLayers, e.n3));
-    room(hd, (size_t)std::max(n_style, 1)); room(hn, (size_t)c->nb * 3);
-    if (e.n1) HIP_TRY(hipMemcpyAsync(h1.data(), e.p1, (size_t)e.n1 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (e.n2) HIP_TRY(hipMemcpyAsync(h2.data(), e.p2, (size_t)e.n2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(h3.data(), e.p3, (size_t)e.n3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (n_style) HIP_TRY(hipMemcpyAsync(hd.data(), c->tile.pd, (size_t)n_style * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(hn.data(), c->norms, hn.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    tile_trace(c, h1.data(), e.n2 ? h2.data() : h3.data() + 6, h3.data(), hd.data(), hn.data(), trace);
-    return ST_OK;
+    return comm_allreduce(c, p, n);
 }
 
 // LBFGSOptimizer.step (optimizers.py:62-108) over the sharded image, fused: every rank keeps its TILE of x, of the gradient and of
@@ -386,7 +359,7 @@ static int tile_read_trace(st_ctx* c, const TileEval& e, double* trace)
 // 2 kLbNB-vector replaces the <= 2k + 3 scalar all-reduces of the chain form (tiled.TiledTransfer), after which every rank runs the same
 // bookkeeping (the s.y > 1e-10 gate, eviction) and coefficient recursion on the same numbers.  Per step: 2 all-reduces + 3 exchanges
 // for the evaluation, 1 all-reduce for the pair, 1 apron refresh.
-static int tile_lbfgs_step(st_ctx* c, TileEval& e, bool want_trace)
+static int tile_lbfgs_step(st_ctx* c)
 {
     st_ctx::Tile& t = c->tile;
     const int wh = c->H, ww = c->W, th = t.ty1 - t.ty0, tw = t.tx1 - t.tx0;
@@ -414,7 +387,7 @@ static int tile_lbfgs_step(st_ctx* c, TileEval& e, bool want_trace)
     }
     if (!c->lb_gram_form) return fail(ST_ERR_STATE, "the history was built by the chain form: reset the optimizer before the fused tile-sharded L-BFGS");
     if (!c->have_cur) {             // optimizers.py:64-65: loss, grad at the starting point
-        ST_TRY(tile_evaluate(c, false, e, false));
+        ST_TRY(tile_evaluate(c, false));
         ST_TRY(strips(c, c->grad, 3, wh, ww, tile_rect, c->g_cur, 0));
         { ProfScope ps(c, P_VECTOR, 0, 4.0 * n_t);
           HIP_TRY(launch_lbfgs_gram_pass_local(args(1), nullptr, 0, s)); }
@@ -429,7 +402,7 @@ static int tile_lbfgs_step(st_ctx* c, TileEval& e, bool want_trace)
         ST_TRY(strips(c, c->x[c->cur], 3, wh, ww, tile_rect, t.lb_x, 1));
         ST_TRY(comm_exchange(c, ST_TILE_PLAN_REFRESH, c->x[c->cur], wh, ww, c->x[c->cur], wh, ww, false));
     }
-    ST_TRY(tile_evaluate(c, false, e, want_trace));                             // loss, grad = opfunc(x)           (optimizers.py:72)
+    ST_TRY(tile_evaluate(c, false));                                            // loss, grad = opfunc(x)           (optimizers.py:72)
     ST_TRY(strips(c, c->grad, 3, wh, ww, tile_rect, c->pvec, 0));               // this rank's tile of the new gradient
     {   // y = grad - self.grad; store_curvature_pair(s, y)                                                         (optimizers.py:73-87)
         { ProfScope ps(c, P_VECTOR, 0, 4.0 * n_t * (2.0 * kLbfgsCorr + 4.0));
@@ -438,6 +411,32 @@ static int tile_lbfgs_step(st_ctx* c, TileEval& e, bool want_trace)
         HIP_TRY(launch_lbfgs_gram_commit_global(args(1), 1, s));
     }
     std::swap(c->g_cur, c->pvec);
+    return ST_OK;
+}
+
+// The trace of the last complete evaluation (st_tile_forward .. st_tile_update / st_tile_gradient with the phase buffers all-reduced in
+// place, by the caller or by st_tile_step): the reduced sums cross PCIe (a few KB + the Gram sums), the scalars are finished on the host
+int st_tile_trace(st_ctx* c, double* trace)
+{
+    if (!c || !trace) return fail(ST_ERR_ARG, "bad argument");
+    if (!c->tile.on) return fail(ST_ERR_STATE, "st_tile_configure first");
+    if (!c->tile.evaluated) return fail(ST_ERR_STATE, "no complete evaluation to finish: the phases up to st_tile_update / st_tile_gradient (or st_tile_step) first");
+    HIP_TRY(hipSetDevice(c->device));
+    ObjTerms terms;
+    ST_TRY(objective_terms(c, c->act, &c->tile, terms));
+    const st_ctx::Tile& t = c->tile;
+    const size_t n1 = terms.n1, ns = (size_t)terms.n_style, n2 = t.s2_in_p2 ? ns : 0, n3 = 6 + (t.s2_in_p2 ? 0 : ns);
+    std::vector<float> &h1 = c->comm.h1, &h2 = c->comm.h2, &h3 = c->comm.h3, &hd = c->comm.hd, &hn = c->comm.hn;      // (kept in the context: grown, never shrunk)
+    auto room = [](std::vector<float>& v, size_t n) { if (v.size() < n) v.resize(n); };
+    room(h1, std::max<size_t>(n1, 1)); room(h2, std::max<size_t>(ns, 1)); room(h3, (size_t)6 + kMaxTraceLayers);
+    room(hd, std::max<size_t>(ns, 1)); room(hn, (size_t)c->nb * 3);
+    if (n1) HIP_TRY(hipMemcpyAsync(h1.data(), t.p1, n1 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (n2) HIP_TRY(hipMemcpyAsync(h2.data(), t.p2, n2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(h3.data(), t.p3, n3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (ns) HIP_TRY(hipMemcpyAsync(hd.data(), t.pd, ns * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(hn.data(), c->norms, hn.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    tile_trace(c, terms, h1.data(), n2 ? h2.data() : h3.data() + 6, h3.data(), hd.data(), hn.data(), trace);
     return ST_OK;
 }
 
@@ -451,14 +450,13 @@ int st_tile_step(st_ctx* c, double* trace)
     const int wh = c->H, ww = c->W;
     struct Unfuse { st_ctx* c; ~Unfuse() { c->tile.fused = false; } } unfuse{c};
     c->tile.fused = true;
-    TileEval e;
     if (c->opt_kind == ST_OPT_LBFGS) {
-        ST_TRY(tile_lbfgs_step(c, e, trace != nullptr));
-        if (trace) ST_TRY(tile_read_trace(c, e, trace));                        // (x was updated in place: no swap)
+        ST_TRY(tile_lbfgs_step(c));
+        if (trace) ST_TRY(st_tile_trace(c, trace));                             // (x was updated in place: no swap)
     } else {
-        ST_TRY(tile_evaluate(c, true, e, trace != nullptr));
+        ST_TRY(tile_evaluate(c, true));
         ST_TRY(comm_exchange(c, ST_TILE_PLAN_REFRESH, c->x[c->cur ^ 1], wh, ww, c->x[c->cur ^ 1], wh, ww, false));
-        if (trace) ST_TRY(tile_read_trace(c, e, trace));
+        if (trace) ST_TRY(st_tile_trace(c, trace));
         c->cur ^= 1;                                                            // st_tile_swap
     }
     c->comm.steps += 1;

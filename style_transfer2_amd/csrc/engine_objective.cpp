@@ -2,21 +2,64 @@
 #include "engine.h"
 
 namespace st2e {
-// ------------------------------------------------------------------------------------ the objective
-int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, bool adam, float* x_next)
+// ------------------------------------------------------------------------------------ the objective's layout
+int objective_terms(const st_ctx* c, const ActSet& a, const TileGeom* tile, ObjTerms& terms)
 {
-    if (!c->x[0]) return fail(ST_ERR_STATE, "no input image");
-    ST_TRY(act_ensure(c, c->act, c->H, c->W));
-    ActSet& a = c->act;
-    int last = 0;
-    for (const ActiveLayer& al : c->active) last = std::max(last, al.blob);
+    terms = ObjTerms{};
+    if (!c->active.empty() && ((int)a.C.size() != c->nb || a.H != c->H || a.W != c->W))
+        return fail(ST_ERR_STATE, "no forward of the current input has sized the activations");
+    size_t pos = 0;
     for (const ActiveLayer& al : c->active) {
         if (al.c && (!c->have_content || c->cH != c->H || c->cW != c->W))
             return fail(ST_ERR_STATE, "content features missing or of a different size than the input");
         if (al.s && !c->have_style) return fail(ST_ERR_STATE, "style Gram matrices missing");
         if (al.s && !c->style_valid[al.blob])
             return fail(ST_ERR_STATE, "blob %d (%s) carries a style weight but has no style target: the sharded style pass (st_tile_set_style) stopped below it", al.blob, c->blob_names[al.blob].c_str());
+        ObjTerm t{};
+        t.al = al; t.b = al.blob; t.C = a.C[t.b];
+        t.n = (size_t)t.C * a.h[t.b] * a.w[t.b];
+        t.has_roi = tile != nullptr;
+        t.roi = tile ? tile_roi(c, a, *tile, t.b) : BlobRoi{0, 0, a.h[t.b], a.w[t.b], (double)t.n};
+        t.n_norm = t.roi.n_global;
+        t.sums = pos;
+        pos += 4;
+        t.gram = kNoSlot; t.k = -1;
+        if (al.s) { t.gram = pos; pos += (size_t)t.C * t.C; t.k = terms.n_style++; }
+        terms.last = std::max(terms.last, t.b);
+        terms.t.push_back(t);
     }
+    terms.n1 = pos;
+    return ST_OK;
+}
+
+ImagePassArgs image_pass_args(const st_ctx* c, const float* x, const float* scd, float* grad, bool adam, float* x_next)
+{
+    ImagePassArgs ip{};
+    ip.x = x; ip.scd = scd; ip.grad = grad;
+    ip.C = 3; ip.H = c->H; ip.W = c->W;
+    ip.tv_w = c->tv_w; ip.tv_beta = c->tv_pow; ip.p_w = c->p_w; ip.p_pow = c->p_pow;
+    ip.partial = c->image_part;
+    if (adam) {
+        // utils.py:58-64: python doubles are rounded to fp32 when they meet the fp32 arrays
+        ip.x_out = x_next; ip.m = c->m; ip.v = c->v;
+        ip.d1 = (float)0.9; ip.c1 = (float)(1 - 0.9); ip.d2 = (float)0.999; ip.c2 = (float)(1 - 0.999);
+        ip.corr1 = (float)(1 - pow(0.9, c->items1)); ip.corr2 = (float)(1 - pow(0.999, c->items2));
+        ip.step = (float)c->step_size;
+        ip.m_is_zero = c->m_zero; ip.v_is_zero = c->v_zero;
+        if (c->capturing) ip.dyn = c->adam_dyn;
+    }
+    return ip;
+}
+
+// ------------------------------------------------------------------------------------ the objective
+int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, bool adam, float* x_next)
+{
+    if (!c->x[0]) return fail(ST_ERR_STATE, "no input image");
+    ST_TRY(act_ensure(c, c->act, c->H, c->W));
+    ActSet& a = c->act;
+    ObjTerms terms;
+    ST_TRY(objective_terms(c, a, nullptr, terms));
+    const int last = std::max(terms.last, 0);
     // lean data flow: tensors nothing reads are not written.  bf16: the whole evaluation (st_set_precision(ctx, 1)); fp32: inside an
     // iteration (st_step / st_step_begin), where no caller can ask for a blob afterwards -- st_opfunc keeps every blob for the test hooks.
     // Identical values either way.  ST2_LEAN32=0 switches the fp32 part off (read per evaluation: A/B runs).
@@ -29,10 +72,10 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
     std::vector<const float*> inj(c->nb, nullptr);
     std::fill(c->cnt.begin(), c->cnt.end(), 0);
     c->sf_in.assign(c->nb, nullptr); c->sf_w.assign(c->nb, nullptr);
-    for (const ActiveLayer& al : c->active) {
-        const int b = al.blob;
-        const int C = a.C[b], hw = a.h[b] * a.w[b];
-        const size_t n = (size_t)C * hw;
+    for (const ObjTerm& ot : terms.t) {
+        const ActiveLayer& al = ot.al;
+        const int b = ot.b, C = ot.C;
+        const size_t n = ot.n;
         if (!c->inject[b]) ST_TRY(c->inject[b].alloc(n));
         c->inject_roi_zero[b] = 0;
         ST_TRY(ensure_layer_part(c, b));
@@ -61,7 +104,7 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
             // which kernels, on which copy of the blob (bf16 operands: the copy where this forward wrote one the kernels take; norm
             // known: the gradient may ride on the data-gradient conv above this blob, and only its trace value is taken here)
             const StyleTerm t = style_term(c, a, b, nullptr, false, want_grad ? last : -1);
-            ST_TRY(style_gram(c, a, t, c->style_gram[b], c->dbuf, conv_mpad(C), (double)C * hw, part + 4 * kMaxPartials, &cnt[4]));
+            ST_TRY(style_gram(c, a, t, c->style_gram[b], c->dbuf, conv_mpad(C), (double)n, part + 4 * kMaxPartials, &cnt[4]));
             const float c2 = (float)(2.0 / ((double)C * C * (double)n));
             if (c->norm_valid[b * 3 + 1]) {
                 ST_TRY(style_grad(c, a, t, c->inject[b], c2, 1, al.sw, wrote, &cnt[5]));
@@ -91,20 +134,7 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
     }
 
     {
-        ImagePassArgs ip{};
-        ip.x = x; ip.scd = scd; ip.grad = want_grad ? grad_out : nullptr;
-        ip.C = 3; ip.H = c->H; ip.W = c->W;
-        ip.tv_w = c->tv_w; ip.tv_beta = c->tv_pow; ip.p_w = c->p_w; ip.p_pow = c->p_pow;
-        ip.partial = c->image_part;
-        if (adam) {
-            // utils.py:58-64: python doubles are rounded to fp32 when they meet the fp32 arrays
-            ip.x_out = x_next; ip.m = c->m; ip.v = c->v;
-            ip.d1 = (float)0.9; ip.c1 = (float)(1 - 0.9); ip.d2 = (float)0.999; ip.c2 = (float)(1 - 0.999);
-            ip.corr1 = (float)(1 - pow(0.9, c->items1)); ip.corr2 = (float)(1 - pow(0.999, c->items2));
-            ip.step = (float)c->step_size;
-            ip.m_is_zero = c->m_zero; ip.v_is_zero = c->v_zero;
-            if (c->capturing) ip.dyn = c->adam_dyn;
-        }
+        const ImagePassArgs ip = image_pass_args(c, x, scd, want_grad ? grad_out : nullptr, adam, x_next);
         const double n3 = 3.0 * c->H * c->W;
         ProfScope ps(c, P_IMAGE_PASS, 0, 4.0 * n3 * (adam ? 7 : 3));
         HIP_TRY(launch_image_pass(ip, &c->image_cnt, c->stream));
@@ -112,14 +142,14 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
 
     {
         TraceArgs t{};
-        t.n_layers = (int)c->active.size();
+        t.n_layers = (int)terms.t.size();
         for (int l = 0; l < t.n_layers; ++l) {
-            const ActiveLayer& al = c->active[l];
+            const ActiveLayer& al = terms.t[l].al;
             const int b = al.blob;
             TraceLayer& L = t.layer[l];
             L.content = al.c; L.style = al.s; L.deepdream = al.d;
             L.cw = al.cw; L.sw = al.sw; L.dw = al.dw;
-            L.n = (double)a.C[b] * a.h[b] * a.w[b];
+            L.n = (double)terms.t[l].n;
             L.gram_n = (double)a.C[b] * a.C[b];
             for (int k = 0; k < 5; ++k) { L.part[k] = c->layer_part[b] + k * kMaxPartials; L.count[k] = c->cnt[b * 6 + k]; }
             L.part[5] = c->s2_part[b]; L.count[5] = c->cnt[b * 6 + 5];
@@ -166,6 +196,7 @@ int st_set_weights(st_ctx* c, int n_rows, const int* blob_index, const float* co
     c->rows = rows;
     c->active.clear();
     for (const ActiveLayer& r : rows) if (r.c || r.s || r.d) c->active.push_back(r);
+    c->tile.evaluated = false;
     c->tv_w = (float)params[0]; c->tv_pow = (float)params[1]; c->p_w = (float)params[2]; c->p_pow = (float)params[3];
     // content features are kept only where a content weight reads them (ensure_content_features brings back what a later table needs)
     if (c->have_content) {

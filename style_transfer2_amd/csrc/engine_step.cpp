@@ -134,9 +134,9 @@ int step_enqueue(st_ctx* c)
             const int par = c->cur;
             if (!c->gexec[par] || c->gepoch[par] != c->epoch) ST_TRY(step_graph_capture(c, par));
             if (c->gexec[par]) {
-                // the only per-step arguments (utils.py:58-64: python doubles rounded to fp32 where they meet the arrays)
-                HIP_TRY(launch_set_scalars3(c->adam_dyn, (float)(1 - pow(0.9, c->items1)), (float)(1 - pow(0.999, c->items2)),
-                                            (float)c->step_size, c->stream));
+                // the only per-step arguments: the corrections and the step as image_pass_args forms them for this item count
+                const ImagePassArgs ip = image_pass_args(c, nullptr, nullptr, nullptr, true, nullptr);
+                HIP_TRY(launch_set_scalars3(c->adam_dyn, ip.corr1, ip.corr2, ip.step, c->stream));
                 HIP_TRY(hipGraphLaunch(c->gexec[par], c->stream));
                 replayed = true;
                 c->graph_replays += 1;

@@ -5,21 +5,28 @@
 // This context runs the window (tile + apron) of one rank.  Every reduction is restricted to the tile's region
 // of each blob and left UN-normalised in a flat device buffer that the caller all-reduces (RCCL) between phases.
 namespace st2e {
+// blob b of a gH x gW image: every pool below it halves the size (Caffe ceil mode) and doubles the stride
+BlobSize blob_size(const st_ctx* c, int b, int gH, int gW)
+{
+    int s = 1, gh = gH, gw = gW;
+    for (int i = 1; i <= b; ++i)
+        if (!c->topo[i - 1].is_conv) { gh = pooled_size(gh); gw = pooled_size(gw); s *= 2; }
+    return BlobSize{gh, gw, s, (double)c->blob_c_topo(b) * gh * gw};
+}
+
 // the tile's region in blob b of the activation set `a` that holds the window (geometry `t`: the iterate's c->tile, or the style
 // image's of st_tile_style_partials)
 BlobRoi tile_roi(const st_ctx* c, const ActSet& a, const TileGeom& t, int b)
 {
-    int s = 1, gh = t.gH, gw = t.gW;
-    for (int i = 1; i <= b; ++i)
-        if (!c->topo[i - 1].is_conv) { s *= 2; gh = pooled_size(gh); gw = pooled_size(gw); }
+    const BlobSize g = blob_size(c, b, t.gH, t.gW);
+    const int s = g.stride;
     BlobRoi r;
     r.y0 = (t.ty0 - t.wy0) / s; r.x0 = (t.tx0 - t.wx0) / s;
     r.y1 = t.ty1 == t.gH ? a.h[b] : (t.ty1 - t.wy0) / s;
     r.x1 = t.tx1 == t.gW ? a.w[b] : (t.tx1 - t.wx0) / s;
-    r.n_global = (double)a.C[b] * gh * gw;
+    r.n_global = g.n;
     return r;
 }
-BlobRoi tile_roi(const st_ctx* c, int b) { return tile_roi(c, c->act, c->tile, b); }
 
 // D = Graw / n_global - G_style into dbuf ([C][MPad]); sum D^2 -> pd[k]
 int tile_style_D(st_ctx* c, int b, const float* graw, double n_global, float* pd_slot)
@@ -32,6 +39,49 @@ int tile_style_D(st_ctx* c, int b, const float* graw, double n_global, float* pd
     GramPlan one{}; one.splits = 1;
     HIP_TRY(launch_gram_reduce(graw, nullptr, c->style_gram[b], c->dbuf, conv_mpad(C), part, &np, C, n_global, one, c->stream));
     HIP_TRY(launch_sum_partials(part, np, pd_slot, c->stream));
+    return ST_OK;
+}
+
+// the phases called one by one return with their work done; inside st_tile_step they only enqueue
+static int tile_sync(st_ctx* c)
+{
+    if (!c->tile.fused) HIP_TRY(hipStreamSynchronize(c->stream));
+    return ST_OK;
+}
+
+// what every phase starts with: the configured context on its device and the layout of the objective (the preflight with it)
+static int tile_begin(st_ctx* c, ObjTerms& terms)
+{
+    if (c) c->epoch++;       // anything but st_step may change what a step launches: captured step graphs are stale
+    if (!c || !c->tile.on) return fail(ST_ERR_STATE, "st_tile_configure first");
+    HIP_TRY(hipSetDevice(c->device));
+    ST_TRY(act_ensure(c, c->act, c->H, c->W));
+    return objective_terms(c, c->act, &c->tile, terms);
+}
+
+// phase 4, both forms.  adam: TV + p-norm + combine + Adam on the tile into x[cur ^ 1]; else the combined gradient of the tile's pixels
+// into c->grad (window layout).  The 6 image sums go to p3[0..6) (p3[6..) already holds this rank's sum S^2 per style layer in steady state).
+static int tile_image_pass(st_ctx* c, const float* ring_dev, bool adam, float** dev_ptr, int* n_floats)
+{
+    HIP_TRY(hipSetDevice(c->device));
+    ObjTerms terms;
+    ST_TRY(objective_terms(c, c->act, &c->tile, terms));
+    const st_ctx::Tile& t = c->tile;
+    ST_TRY(c->tile.p3.reserve(6 + kMaxTraceLayers));
+    if (adam) { c->items1 += 1; c->items2 += 1; }
+    ImageTileArgs ta{};
+    ta.base = image_pass_args(c, c->x[c->cur], c->tile.wgrad, adam ? nullptr : c->grad.get(), adam, c->x[c->cur ^ 1]);
+    ta.ring = ring_dev; ta.ty = t.ty0 - t.wy0; ta.tx = t.tx0 - t.wx0; ta.th = t.ty1 - t.ty0; ta.tw = t.tx1 - t.tx0;
+    // the untouched apron of x_next is refreshed by the caller; start it from the current values
+    if (adam) HIP_TRY(hipMemcpyAsync(c->x[c->cur ^ 1], c->x[c->cur], (size_t)3 * c->H * c->W * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    int np = 0;
+    HIP_TRY(launch_image_pass_tile(ta, &np, c->stream));
+    for (int k = 0; k < 6; ++k) HIP_TRY(launch_sum_partials(c->image_part + k * kMaxPartials, np, c->tile.p3 + k, c->stream));
+    if (adam) c->m_zero = c->v_zero = false;
+    ST_TRY(tile_sync(c));
+    c->tile.evaluated = true;
+    if (dev_ptr) *dev_ptr = c->tile.p3;
+    if (n_floats) *n_floats = 6 + (c->tile.s2_in_p2 ? 0 : terms.n_style);
     return ST_OK;
 }
 }  // namespace st2e
@@ -50,56 +100,39 @@ int st_tile_configure(st_ctx* c, int gH, int gW, int wy0, int wx0, int ty0, int 
         return fail(ST_ERR_ARG, "tile/window geometry is inconsistent with the %dx%d window", c->H, c->W);
     st_ctx::Tile& t = c->tile;
     t.on = true; t.gH = gH; t.gW = gW; t.wy0 = wy0; t.wx0 = wx0; t.ty0 = ty0; t.tx0 = tx0; t.ty1 = ty1; t.tx1 = tx1;
+    t.evaluated = false;
     return ST_OK;
 }
 
 // phase 1: forward on the window, region sums [d2, gc2, F2, gd2] per active layer and the RAW Gram sums
 int st_tile_forward(st_ctx* c, float** dev_ptr, int* n_floats)
 {
-    if (c) c->epoch++;       // anything but st_step may change what a step launches: captured step graphs are stale
-    if (!c || !c->tile.on) return fail(ST_ERR_STATE, "st_tile_configure first");
-    HIP_TRY(hipSetDevice(c->device));
-    ST_TRY(act_ensure(c, c->act, c->H, c->W));
+    ObjTerms terms;
+    ST_TRY(tile_begin(c, terms));
     ActSet& a = c->act;
-    int last = 0;
-    size_t n1 = 0;
-    for (const ActiveLayer& al : c->active) {
-        last = std::max(last, al.blob);
-        n1 += 4 + (al.s ? (size_t)a.C[al.blob] * a.C[al.blob] : 0);
-        if (al.c && (!c->have_content || c->cH != c->H || c->cW != c->W)) return fail(ST_ERR_STATE, "content features missing");
-        if (al.s && !c->have_style) return fail(ST_ERR_STATE, "style Gram matrices missing");
-        if (al.s && !c->style_valid[al.blob])
-            return fail(ST_ERR_STATE, "blob %d (%s) carries a style weight but has no style target: the sharded style pass (st_tile_set_style) stopped below it", al.blob, c->blob_names[al.blob].c_str());
-    }
+    c->tile.evaluated = false;
     ST_TRY(ensure_content_features(c));
-    ST_TRY(c->tile.p1.reserve(std::max<size_t>(n1, 1)));
-    HIP_TRY(hipMemsetAsync(c->tile.p1, 0, std::max<size_t>(n1, 1) * sizeof(float), c->stream));
+    ST_TRY(c->tile.p1.reserve(std::max<size_t>(terms.n1, 1)));
+    HIP_TRY(hipMemsetAsync(c->tile.p1, 0, std::max<size_t>(terms.n1, 1) * sizeof(float), c->stream));
     // bf16 operands: the lean data flow here too -- an fp32 blob / diff is written only where something reads fp32 (the weighted
     // blobs: the region-of-interest loss kernels are fp32), pools ride on their producing conv, the backward masks from the bf16 copies
     // fp32, inside the fused iteration (st_tile_step): the full-resolution blobs of pooled, un-weighted layers are not written either
     bool lean32 = false;
     if (!c->bf16 && c->tile.fused) lean32 = lean32_enabled();
-    ST_TRY(forward_range(c, a, c->x[c->cur], last, (c->bf16 && c->lean) || lean32));
-    size_t pos = 0;
-    for (const ActiveLayer& al : c->active) {
-        const int b = al.blob, C = a.C[b];
-        const BlobRoi r = tile_roi(c, b);
-        ST_TRY(ensure_layer_part(c, b));
-        float* part = c->layer_part[b];
-        if (al.c || al.d) {
+    ST_TRY(forward_range(c, a, c->x[c->cur], std::max(terms.last, 0), (c->bf16 && c->lean) || lean32));
+    for (const ObjTerm& t : terms.t) {
+        ST_TRY(ensure_layer_part(c, t.b));
+        float* part = c->layer_part[t.b];
+        if (t.al.c || t.al.d) {
             int np = 0;
-            HIP_TRY(launch_layer_elem(layer_elem_args(c, al, r.n_global, 0, part, &r), &np, c->stream));
-            for (int k = 0; k < 4; ++k) HIP_TRY(launch_sum_partials(part + k * kMaxPartials, np, c->tile.p1 + pos + k, c->stream));
+            HIP_TRY(launch_layer_elem(layer_elem_args(c, t.al, t.n_norm, 0, part, t.region()), &np, c->stream));
+            for (int k = 0; k < 4; ++k) HIP_TRY(launch_sum_partials(part + k * kMaxPartials, np, c->tile.p1 + t.sums + k, c->stream));
         }
-        pos += 4;
-        if (al.s) {
-            // raw sum over this rank's region (divisor 1, no target), contiguous C x C; bf16 operands: from the blob's bf16 copy
-            ST_TRY(style_gram(c, a, style_term(c, a, b, &r), nullptr, c->tile.p1 + pos, C, 1.0, nullptr, nullptr));
-            pos += (size_t)C * C;
-        }
+        // raw sum over this rank's region (divisor 1, no target), contiguous C x C; bf16 operands: from the blob's bf16 copy
+        if (t.al.s) ST_TRY(style_gram(c, a, style_term(c, a, t.b, t.region()), nullptr, c->tile.p1 + t.gram, t.C, 1.0, nullptr, nullptr));
     }
     if (dev_ptr) *dev_ptr = c->tile.p1;
-    if (n_floats) *n_floats = (int)n1;
+    if (n_floats) *n_floats = (int)terms.n1;
     return ST_OK;
 }
 
@@ -108,73 +141,60 @@ int st_tile_forward(st_ctx* c, float** dev_ptr, int* n_floats)
 // all-reduces p2 and only then calls st_tile_losses_finish.
 int st_tile_losses(st_ctx* c, float** dev_ptr, int* n_floats)
 {
-    if (c) c->epoch++;       // anything but st_step may change what a step launches: captured step graphs are stale
-    if (!c || !c->tile.on) return fail(ST_ERR_STATE, "st_tile_configure first");
-    HIP_TRY(hipSetDevice(c->device));
-    ActSet& a = c->act;
-    int n_style = 0;
+    ObjTerms terms;
+    ST_TRY(tile_begin(c, terms));
     bool missing = false;
-    for (const ActiveLayer& al : c->active) if (al.s) { ++n_style; missing = missing || !c->norm_valid[al.blob * 3 + 1]; }
-    ST_TRY(c->tile.p2.reserve(std::max(n_style, 1)));
-    ST_TRY(c->tile.pd.reserve(std::max(n_style, 1)));
+    for (const ObjTerm& t : terms.t) if (t.al.s) missing = missing || !c->norm_valid[t.b * 3 + 1];
+    ST_TRY(c->tile.p2.reserve(std::max(terms.n_style, 1)));
+    ST_TRY(c->tile.pd.reserve(std::max(terms.n_style, 1)));
     c->tile.s2_in_p2 = missing;
     ST_TRY(ensure_dbuf(c));
-    size_t pos = 0;
-    for (const ActiveLayer& al : c->active) {
-        const int b = al.blob, C = a.C[b];
-        const BlobRoi r = tile_roi(c, b);
+    for (const ObjTerm& t : terms.t) {
+        const int b = t.b;
+        const float* sums = c->tile.p1 + t.sums;
         float* nrm = c->norms + b * 3;
-        if (al.c && !c->norm_valid[b * 3 + 0]) { HIP_TRY(launch_finalize_norm(c->tile.p1 + pos + 1, 1, r.n_global, nrm + 0, c->stream)); c->norm_valid[b * 3 + 0] = 1; }
-        if (al.d && !c->norm_valid[b * 3 + 2]) { HIP_TRY(launch_finalize_norm(c->tile.p1 + pos + 3, 1, r.n_global, nrm + 2, c->stream)); c->norm_valid[b * 3 + 2] = 1; }
-        pos += 4;
-        if (al.s) pos += (size_t)C * C;
+        if (t.al.c && !c->norm_valid[b * 3 + 0]) { HIP_TRY(launch_finalize_norm(sums + 1, 1, t.n_norm, nrm + 0, c->stream)); c->norm_valid[b * 3 + 0] = 1; }
+        if (t.al.d && !c->norm_valid[b * 3 + 2]) { HIP_TRY(launch_finalize_norm(sums + 3, 1, t.n_norm, nrm + 2, c->stream)); c->norm_valid[b * 3 + 2] = 1; }
     }
     if (dev_ptr) *dev_ptr = missing ? c->tile.p2 : nullptr;
-    if (n_floats) *n_floats = missing ? n_style : 0;
+    if (n_floats) *n_floats = missing ? terms.n_style : 0;
     return ST_OK;
 }
 
 // phase 2b: injected diffs of every active layer (region only, zero elsewhere)
 int st_tile_losses_finish(st_ctx* c)
 {
-    if (c) c->epoch++;       // anything but st_step may change what a step launches: captured step graphs are stale
-    if (!c || !c->tile.on) return fail(ST_ERR_STATE, "st_tile_configure first");
-    HIP_TRY(hipSetDevice(c->device));
+    ObjTerms terms;
+    ST_TRY(tile_begin(c, terms));
     ActSet& a = c->act;
-    size_t pos = 0;
-    int k = 0;
     const bool two_step = c->tile.s2_in_p2;
-    for (const ActiveLayer& al : c->active) {
-        const int b = al.blob, C = a.C[b];
-        const BlobRoi r = tile_roi(c, b);
-        const size_t n = (size_t)C * a.h[b] * a.w[b];
-        if (!c->inject[b]) ST_TRY(c->inject[b].alloc(n));
+    for (const ObjTerm& t : terms.t) {
+        const ActiveLayer& al = t.al;
+        const int b = t.b, C = t.C;
+        if (!c->inject[b]) ST_TRY(c->inject[b].alloc(t.n));
         float* nrm = c->norms + b * 3;
         bool wrote = false;
         if (al.c || al.d) {
             int np = 0;
-            HIP_TRY(launch_layer_elem(layer_elem_args(c, al, r.n_global, 1, nullptr, &r), &np, c->stream));
+            HIP_TRY(launch_layer_elem(layer_elem_args(c, al, t.n_norm, 1, nullptr, t.region()), &np, c->stream));
             wrote = true;
         }
-        pos += 4;
         if (al.s) {
-            ST_TRY(tile_style_D(c, b, c->tile.p1 + pos, r.n_global, c->tile.pd + k));
-            const float c2 = (float)(2.0 / ((double)C * C * r.n_global));
+            ST_TRY(tile_style_D(c, b, c->tile.p1 + t.gram, t.n_norm, c->tile.pd + t.k));
+            const float c2 = (float)(2.0 / ((double)C * C * t.n_norm));
             int np = 0;
             // norm from the all-reduced sum S^2 of the first pass (st_tile_style_raw), then saxpy
             if (two_step && !c->norm_valid[b * 3 + 1]) {
-                HIP_TRY(launch_finalize_norm(c->tile.p2 + k, 1, r.n_global, nrm + 1, c->stream));
+                HIP_TRY(launch_finalize_norm(c->tile.p2 + t.k, 1, t.n_norm, nrm + 1, c->stream));
                 c->norm_valid[b * 3 + 1] = 1;
             }
             // (region only: the fp32 kernel on the fp32 blob, or -- bf16 operands -- the bf16 kernel on the blob's bf16 copy)
-            ST_TRY(style_grad(c, a, style_term(c, a, b, &r), c->inject[b], c2, 1, al.sw, wrote, &np));
+            ST_TRY(style_grad(c, a, style_term(c, a, b, t.region()), c->inject[b], c2, 1, al.sw, wrote, &np));
             if (!two_step) {
                 // sum S^2 of this rank's region -> p3 tail (all-reduced with the image sums)
                 ST_TRY(c->tile.p3.reserve(6 + kMaxTraceLayers));
-                HIP_TRY(launch_sum_partials(c->s2_part[b], np, c->tile.p3 + 6 + k, c->stream));
+                HIP_TRY(launch_sum_partials(c->s2_part[b], np, c->tile.p3 + 6 + t.k, c->stream));
             }
-            pos += (size_t)C * C;
-            ++k;
         }
     }
     return ST_OK;
@@ -183,25 +203,17 @@ int st_tile_losses_finish(st_ctx* c)
 // first evaluation only: unscaled style gradients, sum S^2 per style layer -> p2 (to be all-reduced)
 int st_tile_style_raw(st_ctx* c)
 {
-    if (c) c->epoch++;       // anything but st_step may change what a step launches: captured step graphs are stale
-    if (!c || !c->tile.on) return fail(ST_ERR_STATE, "st_tile_configure first");
-    HIP_TRY(hipSetDevice(c->device));
+    ObjTerms terms;
+    ST_TRY(tile_begin(c, terms));
     ActSet& a = c->act;
-    size_t pos = 0;
-    int k = 0;
-    for (const ActiveLayer& al : c->active) {
-        const int b = al.blob, C = a.C[b];
-        pos += 4;
-        if (!al.s) continue;
-        const BlobRoi r = tile_roi(c, b);
-        ST_TRY(tile_style_D(c, b, c->tile.p1 + pos, r.n_global, c->tile.pd + k));
-        const float c2 = (float)(2.0 / ((double)C * C * r.n_global));
+    for (const ObjTerm& t : terms.t) {
+        if (!t.al.s) continue;
+        ST_TRY(tile_style_D(c, t.b, c->tile.p1 + t.gram, t.n_norm, c->tile.pd + t.k));
+        const float c2 = (float)(2.0 / ((double)t.C * t.C * t.n_norm));
         if (!c->stmp) ST_TRY(c->stmp.alloc(c->max_blob));
         int np = 0;
-        ST_TRY(style_grad(c, a, style_term(c, a, b, &r), c->stmp, c2, 0, al.sw, 0, &np));
-        HIP_TRY(launch_sum_partials(c->s2_part[b], np, c->tile.p2 + k, c->stream));
-        pos += (size_t)C * C;
-        ++k;
+        ST_TRY(style_grad(c, a, style_term(c, a, t.b, t.region()), c->stmp, c2, 0, t.al.sw, 0, &np));
+        HIP_TRY(launch_sum_partials(c->s2_part[t.b], np, c->tile.p2 + t.k, c->stream));
     }
     return ST_OK;
 }
@@ -209,14 +221,13 @@ int st_tile_style_raw(st_ctx* c)
 // phase 3: ranged backward on the window; returns the device pointer of the (3, wh, ww) gradient
 int st_tile_backward(st_ctx* c, float** dev_grad)
 {
-    if (c) c->epoch++;       // anything but st_step may change what a step launches: captured step graphs are stale
-    if (!c || !c->tile.on) return fail(ST_ERR_STATE, "st_tile_configure first");
-    HIP_TRY(hipSetDevice(c->device));
+    ObjTerms terms;
+    ST_TRY(tile_begin(c, terms));
     const size_t n3 = (size_t)3 * c->H * c->W;
     if (!c->tile.wgrad) ST_TRY(c->tile.wgrad.alloc(n3));
     std::vector<const float*> inj(c->nb, nullptr);
-    int last = -1;
-    for (const ActiveLayer& al : c->active) { inj[al.blob] = c->inject[al.blob]; last = std::max(last, al.blob); }
+    const int last = terms.last;
+    for (const ObjTerm& t : terms.t) inj[t.b] = c->inject[t.b];
     if (last < 0) HIP_TRY(hipMemsetAsync(c->tile.wgrad, 0, n3 * sizeof(float), c->stream));
     else {
         if (!c->diffA) { ST_TRY(c->diffA.alloc(c->max_blob)); ST_TRY(c->diffB.alloc(c->max_blob)); }
@@ -224,43 +235,18 @@ int st_tile_backward(st_ctx* c, float** dev_grad)
         if (last > 0) ST_TRY(backward_chain(c, last, inj[last], inj, &g, c->bf16 && c->lean));
         HIP_TRY(hipMemcpyAsync(c->tile.wgrad, g, n3 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     }
-    if (!c->tile.fused) HIP_TRY(hipStreamSynchronize(c->stream));
+    ST_TRY(tile_sync(c));
     if (dev_grad) *dev_grad = c->tile.wgrad;
     return ST_OK;
 }
 
-// phase 4: TV + p-norm + combine + Adam on the tile; ring = (3, th+2, tw+2) device tensor.  The 6 image sums
-// go to p3[0..6) (p3[6..) already holds this rank's sum S^2 per style layer in steady state).
+// phase 4: TV + p-norm + combine + Adam on the tile; ring = (3, th+2, tw+2) device tensor
 int st_tile_update(st_ctx* c, const float* ring_dev, float** dev_ptr, int* n_floats)
 {
     if (c) c->epoch++;       // anything but st_step may change what a step launches: captured step graphs are stale
     if (!c || !c->tile.on || !ring_dev) return fail(ST_ERR_STATE, "st_tile_configure first");
     if (c->opt_kind != ST_OPT_ADAM) return fail(ST_ERR_STATE, "the tile-sharded mode implements Adam");
-    HIP_TRY(hipSetDevice(c->device));
-    const st_ctx::Tile& t = c->tile;
-    ST_TRY(c->tile.p3.reserve(6 + kMaxTraceLayers));
-    c->items1 += 1; c->items2 += 1;
-    ImageTileArgs ta{};
-    ImagePassArgs& ip = ta.base;
-    ip.x = c->x[c->cur]; ip.scd = c->tile.wgrad; ip.grad = nullptr; ip.C = 3; ip.H = c->H; ip.W = c->W;
-    ip.tv_w = c->tv_w; ip.tv_beta = c->tv_pow; ip.p_w = c->p_w; ip.p_pow = c->p_pow; ip.partial = c->image_part;
-    ip.x_out = c->x[c->cur ^ 1]; ip.m = c->m; ip.v = c->v;
-    ip.d1 = (float)0.9; ip.c1 = (float)(1 - 0.9); ip.d2 = (float)0.999; ip.c2 = (float)(1 - 0.999);
-    ip.corr1 = (float)(1 - pow(0.9, c->items1)); ip.corr2 = (float)(1 - pow(0.999, c->items2));
-    ip.step = (float)c->step_size; ip.m_is_zero = c->m_zero; ip.v_is_zero = c->v_zero;
-    ta.ring = ring_dev; ta.ty = t.ty0 - t.wy0; ta.tx = t.tx0 - t.wx0; ta.th = t.ty1 - t.ty0; ta.tw = t.tx1 - t.tx0;
-    // the untouched apron of x_next is refreshed by the caller; start it from the current values
-    HIP_TRY(hipMemcpyAsync(c->x[c->cur ^ 1], c->x[c->cur], (size_t)3 * c->H * c->W * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-    int np = 0;
-    HIP_TRY(launch_image_pass_tile(ta, &np, c->stream));
-    for (int k = 0; k < 6; ++k) HIP_TRY(launch_sum_partials(c->image_part + k * kMaxPartials, np, c->tile.p3 + k, c->stream));
-    c->m_zero = c->v_zero = false;
-    int n_style = 0;
-    for (const ActiveLayer& al : c->active) n_style += al.s;
-    if (!c->tile.fused) HIP_TRY(hipStreamSynchronize(c->stream));
-    if (dev_ptr) *dev_ptr = c->tile.p3;
-    if (n_floats) *n_floats = 6 + (c->tile.s2_in_p2 ? 0 : n_style);
-    return ST_OK;
+    return tile_image_pass(c, ring_dev, true, dev_ptr, n_floats);
 }
 
 // The same image-space pass without an optimizer update: the combined gradient of the tile's pixels goes to the window-sized
@@ -270,24 +256,7 @@ int st_tile_gradient(st_ctx* c, const float* ring_dev, float** dev_ptr, int* n_f
 {
     if (c) c->epoch++;
     if (!c || !c->tile.on || !ring_dev) return fail(ST_ERR_STATE, "st_tile_configure first");
-    HIP_TRY(hipSetDevice(c->device));
-    const st_ctx::Tile& t = c->tile;
-    ST_TRY(c->tile.p3.reserve(6 + kMaxTraceLayers));
-    ImageTileArgs ta{};
-    ImagePassArgs& ip = ta.base;
-    ip.x = c->x[c->cur]; ip.scd = c->tile.wgrad; ip.grad = c->grad; ip.C = 3; ip.H = c->H; ip.W = c->W;
-    ip.tv_w = c->tv_w; ip.tv_beta = c->tv_pow; ip.p_w = c->p_w; ip.p_pow = c->p_pow; ip.partial = c->image_part;
-    ip.x_out = nullptr;
-    ta.ring = ring_dev; ta.ty = t.ty0 - t.wy0; ta.tx = t.tx0 - t.wx0; ta.th = t.ty1 - t.ty0; ta.tw = t.tx1 - t.tx0;
-    int np = 0;
-    HIP_TRY(launch_image_pass_tile(ta, &np, c->stream));
-    for (int k = 0; k < 6; ++k) HIP_TRY(launch_sum_partials(c->image_part + k * kMaxPartials, np, c->tile.p3 + k, c->stream));
-    int n_style = 0;
-    for (const ActiveLayer& al : c->active) n_style += al.s;
-    if (!c->tile.fused) HIP_TRY(hipStreamSynchronize(c->stream));
-    if (dev_ptr) *dev_ptr = c->tile.p3;
-    if (n_floats) *n_floats = 6 + (c->tile.s2_in_p2 ? 0 : n_style);
-    return ST_OK;
+    return tile_image_pass(c, ring_dev, false, dev_ptr, n_floats);
 }
 
 // BLAS-1 pieces for a caller that keeps its own vectors on this device (the tile-sharded L-BFGS): out_dev[0] = sum a b over n
@@ -297,7 +266,7 @@ int st_vec_dot(st_ctx* c, const float* a_dev, const float* b_dev, long long n, f
     if (!c || !a_dev || !b_dev || !out_dev || n < 0) return fail(ST_ERR_ARG, "bad argument");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(launch_vec_dot(a_dev, b_dev, (size_t)n, c->image_part, out_dev, c->stream));
-    if (!c->tile.fused) HIP_TRY(hipStreamSynchronize(c->stream));
+    ST_TRY(tile_sync(c));
     return ST_OK;
 }
 
@@ -306,7 +275,7 @@ int st_vec_axpy(st_ctx* c, float alpha, const float* x_dev, float* y_dev, long l
     if (!c || !x_dev || !y_dev || n < 0) return fail(ST_ERR_ARG, "bad argument");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(launch_vec_axpy(alpha, x_dev, y_dev, (size_t)n, c->stream));
-    if (!c->tile.fused) HIP_TRY(hipStreamSynchronize(c->stream));
+    ST_TRY(tile_sync(c));
     return ST_OK;
 }
 
@@ -315,7 +284,7 @@ int st_vec_div(st_ctx* c, double divisor, float* y_dev, long long n)
     if (!c || !y_dev || n < 0 || !(divisor != 0.0)) return fail(ST_ERR_ARG, "bad argument");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(launch_vec_div(divisor, y_dev, (size_t)n, c->stream));
-    if (!c->tile.fused) HIP_TRY(hipStreamSynchronize(c->stream));
+    ST_TRY(tile_sync(c));
     return ST_OK;
 }
 
@@ -324,7 +293,7 @@ int st_tile_buffer(st_ctx* c, int which, float** dev_ptr)
 {
     if (c) c->epoch++;       // anything but st_step may change what a step launches: captured step graphs are stale
     if (!c || !dev_ptr) return fail(ST_ERR_ARG, "bad argument");
-    if (!c->tile.fused) HIP_TRY(hipStreamSynchronize(c->stream));
+    ST_TRY(tile_sync(c));
     if (which == 0) *dev_ptr = c->x[c->cur];
     else if (which == 1) *dev_ptr = c->x[c->cur ^ 1];
     else if (which == 2) *dev_ptr = c->tile.pd;
@@ -352,7 +321,7 @@ int st_tile_strips(st_ctx* c, void* tensor_dev, int C, int wh, int ww, int n, co
     }
     t.total = total;
     HIP_TRY(launch_strip_copy((float*)tensor_dev, (float*)buf_dev, t, C, wh, ww, mode, c->stream));
-    if (!c->tile.fused) HIP_TRY(hipStreamSynchronize(c->stream));
+    ST_TRY(tile_sync(c));
     return ST_OK;
 }
 
@@ -370,8 +339,7 @@ int st_tile_style_partials(st_ctx* c, const void* hwc, int H, int W, int is_u8, 
     if (gH <= 0 || gW <= 0) return fail(ST_ERR_ARG, "bad style image size %d x %d", gH, gW);
     for (int i = 0; i < last_blob; ++i)
         if (c->topo[i].ave) return fail(ST_ERR_ARG, "tile-sharded mode does not run average pools (layer %s); use st_set_style", c->topo[i].name.c_str());
-    int stride = 1;
-    for (int i = 0; i < last_blob; ++i) if (!c->topo[i].is_conv) stride *= 2;
+    const int stride = blob_size(c, last_blob, gH, gW).stride;
     if (hwc) {
         if (H <= 0 || W <= 0 || wy0 < 0 || wx0 < 0 || wy0 + H > gH || wx0 + W > gW || ty0 < wy0 || tx0 < wx0 || ty1 > wy0 + H || tx1 > wx0 + W ||
             ty1 <= ty0 || tx1 <= tx0)
@@ -434,15 +402,13 @@ int st_tile_style_commit(st_ctx* c)
     if (!c) return fail(ST_ERR_ARG, "ctx is NULL");
     if (c->tile.sp_last < 0 || !c->tile.sp) return fail(ST_ERR_STATE, "st_tile_style_partials first");
     HIP_TRY(hipSetDevice(c->device));
-    int gh = c->tile.sp_gH, gw = c->tile.sp_gW;
     size_t pos = 0;
     GramPlan one{}; one.bt = 128; one.splits = 1;          // the reduced sums are ONE full C x C slab
     for (int b = 0; b <= c->tile.sp_last; ++b) {
-        if (b > 0 && !c->topo[b - 1].is_conv) { gh = pooled_size(gh); gw = pooled_size(gw); }
         const int C = c->blob_c_topo(b);
         if (!c->style_gram[b]) ST_TRY(c->style_gram[b].alloc((size_t)C * C));
         ProfScope ps(c, P_GRAM_REDUCE, 0, 8.0 * C * C);
-        HIP_TRY(launch_gram_reduce(c->tile.sp + pos, nullptr, nullptr, c->style_gram[b], C, nullptr, nullptr, C, (double)C * gh * gw, one, c->stream));
+        HIP_TRY(launch_gram_reduce(c->tile.sp + pos, nullptr, nullptr, c->style_gram[b], C, nullptr, nullptr, C, blob_size(c, b, c->tile.sp_gH, c->tile.sp_gW).n, one, c->stream));
         pos += (size_t)C * C;
     }
     HIP_TRY(hipStreamSynchronize(c->stream));

@@ -10,8 +10,7 @@ import numpy as np
 from . import capi
 from .capi import check
 from .engine import Engine, OPT_ADAM, OPT_LBFGS
-from .tiling import blob_geometry
-from .transfer import weight_table, LOSS_NAMES, SCALAR_LOSS_NAMES, EPS
+from .transfer import weight_table, LOSS_NAMES, SCALAR_LOSS_NAMES
 
 F32 = np.float32
 
@@ -72,19 +71,7 @@ class HipTileBackend:
         self.engine.optimizer_reset(OPT_LBFGS if optimizer == 'lbfgs' else OPT_ADAM, step_size)
         self.engine.clear_norms()
         check(self.lib.st_tile_configure(self.ctx, grid.gH, grid.gW, w.y0, w.x0, t.y0, t.x0, t.y1, t.x1))
-        self.params = params
         self.wh, self.ww = w.y1 - w.y0, w.x1 - w.x0
-        topo = self.engine.topology
-        names = self.engine.blob_names
-        ggeo = blob_geometry(topo, grid.gH, grid.gW)
-        self.active = []
-        for r in rows:
-            cw, sw, dw = (cells[k][r] for k in LOSS_NAMES)
-            flags = tuple(abs(v) > EPS for v in (cw, sw, dw))
-            if any(flags):
-                c, gh, gw, _ = ggeo[names.index(r)]
-                self.active.append((r, names.index(r), F32(cw), F32(sw), F32(dw)) + flags + (c, c * gh * gw))
-        self.n_style = sum(1 for a in self.active if a[6])
 
     @property
     def device(self):
@@ -281,7 +268,6 @@ class HipTileBackend:
 
     def losses_need_style_norm(self):
         torch.cuda.synchronize(self.device)
-        self.p1_host = self.p1.cpu().numpy().copy() if self.p1 is not None else np.zeros(0, F32)
         p, n = c_void_p(), c_int()
         check(self.lib.st_tile_losses(self.ctx, byref(p), byref(n)))
         self.p2 = None
@@ -293,7 +279,6 @@ class HipTileBackend:
 
     def finish_losses(self):
         torch.cuda.synchronize(self.device)
-        self.s2_host = self.p2.cpu().numpy().copy() if self.p2 is not None else None
         check(self.lib.st_tile_losses_finish(self.ctx))
         self._sync()
 
@@ -377,41 +362,9 @@ class HipTileBackend:
         self.strips(nxt, rect, xt.reshape(-1), 1)
 
     def finish_trace(self):
-        """Trace scalars from the reduced sums, in the reference's fp32 order (worker.py:249-301); same layout
-        as the single-GPU engine: 6 per active layer + 8."""
+        """The trace of the evaluation whose phase buffers the caller has all-reduced in place (st_tile_trace: the finisher st_tile_step
+        uses); same layout as the single-GPU engine: 6 per active layer + 8."""
         torch.cuda.synchronize(self.device)
-        p3 = self.p3.cpu().numpy()
-        s2 = self.s2_host if self.s2_host is not None else p3[6:]
-        d2 = self._buf(2, (max(self.n_style, 1),)).cpu().numpy()
-        norms = self._buf(3, (len(self.engine.blob_names) * 3,)).cpu().numpy()
-        vals, loss, pos, k = [], F32(0), 0, 0
-        for name, b, cw, sw, dw, c_on, s_on, d_on, C, n in self.active:
-            sums = self.p1_host[pos:pos + 4]
-            pos += 4
-            v6 = [0.0] * 6
-            if c_on:
-                cn = norms[b * 3 + 0]
-                v6[0] = cw * F32(sums[0] / n) / cn
-                v6[1] = abs(cw) * np.sqrt(F32(sums[1] / n)) / cn
-                loss += v6[0]
-            if s_on:
-                sn = norms[b * 3 + 1]
-                v6[2] = sw * F32(d2[k] / (C * C)) / sn
-                v6[3] = abs(sw / sn) * np.sqrt(F32(s2[k] / n))
-                loss += v6[2]
-                pos += C * C
-                k += 1
-            if d_on:
-                dn = norms[b * 3 + 2]
-                v6[4] = -dw * F32(sums[2] / n) / dn
-                v6[5] = abs(dw) * np.sqrt(F32(sums[3] / n)) / dn
-                loss += v6[4]
-            vals += v6
-        n3 = 3.0 * self.grid.gH * self.grid.gW
-        scd_loss = loss
-        t_loss = F32(self.params['tv']) * p3[0]
-        p_loss = F32(self.params['p']) * (p3[1] / F32(self.params['p_power']))
-        total = scd_loss + t_loss + p_loss
-        vals += [scd_loss, t_loss, p_loss, np.sqrt(F32(p3[2] / n3)), np.sqrt(F32(p3[3] / n3)),
-                 np.sqrt(F32(p3[4] / n3)), total, np.sqrt(F32(p3[5] / n3))]
-        return np.asarray(vals, np.float64)
+        trace = np.zeros(self.engine.trace_len(), np.float64)
+        check(self.lib.st_tile_trace(self.ctx, trace.ctypes.data_as(c_void_p)))
+        return trace

@@ -539,4 +539,5 @@ def test_new_entry_points_refuse_null_handles_without_a_gpu():
     assert lib.st_comm_destroy(None) == 1 and lib.st_comm_barrier(None) == 1
     assert lib.st_tile_plan(None, 0, 0, None) == 1
     assert lib.st_tile_step(None, None) == 2 and lib.st_tile_get_tile(None, None) == 2
+    assert lib.st_tile_trace(None, None) == 1
     assert lib.st_vec_div(None, 1.0, None, 0) == 1

@@ -814,6 +814,84 @@ def test_tiled_multi_rank_on_one_gpu_matches_oracle(rows, cols, fused):
     assert np.allclose(full, ref[-1][0], rtol=0, atol=0.5) or np.mean(np.abs(full - ref[-1][0]) > 0.5) < 0.02
 
 
+def test_phase_driven_and_fused_tile_drivers_agree_bit_for_bit():
+    """Both drivers finish the trace through st_tile_trace from the same reduced sums: on a 1 x 1 grid the phase-by-phase driver and
+    st_tile_step give the same trace and the same iterate, bit for bit.  TILED_WEIGHTS has content-only, style-only and pool rows and a
+    style + deep-dream row: every slot kind of the objective's layout; step 1 takes the two-pass style-norm path, the others the steady one."""
+    from style_transfer2_amd import tiled, tiling
+    from style_transfer2_amd.tile_backend import HipTileBackend
+    h, w = 32, 48
+    content, style, init = _tiled_images(h, w)
+    params = oracle.he_init_weights(TILED_TOPO, 0, 0.1)
+    grid = tiling.TileGrid(h, w, 1, 1, TILED_TOPO, 5)
+    backends = [HipTileBackend(params, grid, 0, content, style, init, TILED_WEIGHTS, TILED_PARAMS, step_size=10, topology=TILED_TOPO)
+                for _ in range(2)]
+    phased = tiled.TiledTransfer(grid, 0, backends[0], tiled.Comm())
+    backends[1].comm_init_solo(0, 1)
+    fused = tiled.FusedTiledTransfer(grid, 0, backends[1])
+    for i in range(4):
+        vp, vf = phased.step(), fused.step()
+        assert vp.shape == (backends[0].engine.trace_len(),) and np.all(np.isfinite(vp)) and vp[-2] > 0
+        print('[step %d] largest relative trace difference between the drivers: %.3g' % (i, float(np.max(np.abs(vp - vf) / np.maximum(np.abs(vp), 1e-30)))))
+        assert np.array_equal(vp, vf), i
+        assert np.array_equal(phased.tile_image(), fused.tile_image()), i
+
+
+def test_phase_driven_and_fused_tile_drivers_on_two_ranks_finish_the_same_trace_on_every_rank():
+    """The 1 x 2 grid with both ranks as threads of this process: within a driver every rank finishes its trace from the same reduced
+    sums -- identical vectors; across the drivers the transports may add the ranks' shares in another order -- the bars of
+    test_tiled_multi_rank_on_one_gpu_matches_oracle."""
+    from style_transfer2_amd import tiled, tiling
+    from style_transfer2_amd.tile_backend import HipTileBackend
+    h, w, steps, world = 32, 48, 3, 2
+    content, style, init = _tiled_images(h, w)
+    params = oracle.he_init_weights(TILED_TOPO, 0, 0.1)
+    grid = tiling.TileGrid(h, w, 1, 2, TILED_TOPO, 5)
+    make = lambda r: HipTileBackend(params, grid, r, content, style, init, TILED_WEIGHTS, TILED_PARAMS, step_size=10, topology=TILED_TOPO)
+    out = {}
+    for fused in (False, True):
+        fabric, ranks = ThreadFabric(world), []
+        for r in range(world):
+            backend = make(r)
+            if fused:
+                backend.comm_init_host(r, world, lambda v, r=r: fabric.allreduce(r, v), lambda s, rc, r=r: fabric.exchange(r, s, rc))
+                ranks.append(tiled.FusedTiledTransfer(grid, r, backend))
+            else:
+                ranks.append(tiled.TiledTransfer(grid, r, backend, tiled.LocalComm(fabric, r)))
+        out[fused] = _run_ranks_as_threads(ranks, steps, fabric)
+        for step in range(steps):
+            assert np.array_equal(out[fused][0][step][1], out[fused][1][step][1]), (fused, step)
+    for step in range(steps):
+        for r in range(world):
+            (img_p, vp), (img_f, vf) = out[False][r][step], out[True][r][step]
+            assert np.isclose(vp[-2], vf[-2], rtol=1e-4) and np.isclose(vp[-1], vf[-1], rtol=1e-3), (step, r)
+            assert np.mean((img_p - img_f) ** 2) <= 1.0, (step, r)
+
+
+def test_tile_trace_refuses_a_context_without_a_complete_evaluation():
+    """st_tile_trace: ST_ERR_STATE before st_tile_configure and after st_tile_forward alone (the phase buffers hold no finished
+    evaluation, at first or again after one); the NULL context is checked without a GPU in test_boundary.py."""
+    from style_transfer2_amd import tiled, tiling
+    from style_transfer2_amd.tile_backend import HipTileBackend
+    from ctypes import c_void_p
+    h, w = 32, 48
+    content, style, init = _tiled_images(h, w)
+    params = oracle.he_init_weights(TILED_TOPO, 0, 0.1)
+    plain = st2.HipModel(params, topology=TILED_TOPO).engine
+    buf = np.zeros(64, np.float64)
+    assert plain.lib.st_tile_trace(plain._ctx, buf.ctypes.data_as(c_void_p)) == 2 and b'st_tile_configure' in plain.lib.st_last_error()
+    grid = tiling.TileGrid(h, w, 1, 1, TILED_TOPO, 5)
+    backend = HipTileBackend(params, grid, 0, content, style, init, TILED_WEIGHTS, TILED_PARAMS, step_size=10, topology=TILED_TOPO)
+    trace = lambda: backend.lib.st_tile_trace(backend.ctx, buf.ctypes.data_as(c_void_p))
+    assert trace() == 2
+    backend.forward_partials()
+    assert trace() == 2 and b'complete evaluation' in backend.lib.st_last_error()
+    tiled.TiledTransfer(grid, 0, backend, tiled.Comm()).step()
+    assert trace() == 0 and backend.lib.st_tile_trace(backend.ctx, None) == 1
+    backend.forward_partials()
+    assert trace() == 2
+
+
 def ThreadFabric(world, timeout=120.0):
     """tiled.InProcessFabric: every rank is a thread of this process (a GPU box admits six processes on its card; BASELINE configs[4]
     has eight ranks)."""
