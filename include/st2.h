@@ -165,6 +165,28 @@ int st_step_pending(st_ctx* ctx);      /* iterations begun and not yet ended (0.
  * by a re-allocation (a larger input, other rooms) stay valid for the views already handed out, for the same five further begins.
  * Refused (ST_ERR_STATE) while an iteration is in flight: its slot was sized without the room -- collect with st_step_end first. */
 int st_step_frame_room(st_ctx* ctx, size_t head_bytes, size_t tail_bytes);
+/* Iterate averaging: hand out a bias-corrected exponentially weighted mean of the iterates instead of the raw iterate (utils.DecayingMean,
+ * utils.py:49-69, which the reference keeps for Adam's moments; crowsonkb's style_transfer CLI averages its iterates this way).  After every
+ * optimizer step, Adam or L-BFGS, on the iterate x that step produced (preprocessed NCHW), in NumPy's float32 arithmetic:
+ *   mean = float(decay) * mean + float(1.0 - decay) * x   (two fp32 products and one fp32 sum, no FMA; the empty mean is 0);  items += 1
+ * and the image of st_step (out_hwc) and st_step_end is deprocess(mean / float(1.0 - decay ** items)): power and subtraction in double,
+ * rounded once, one IEEE fp32 division, then the channel mean.  x, the optimizer state, the loss and the trace are untouched -- the
+ * trajectory is that of the mode off, bit for bit -- and the raw iterate stays available from st_get_input_nchw.  st_step(ctx, NULL, ..)
+ * and every st_step_begin update the mean too; begin / end give the images of st_step bit for bit, frame rooms work unchanged.
+ * With an image wanted the update and the image are ONE launch in place of the deprocess pass; without, one extra launch per step.
+ *   decay 0.0 (default): off, the buffer is freed, every path launches what it launched without the mode.  0 < decay < 1: on, the mean is
+ *   cleared.  Anything else, NaN included: ST_ERR_ARG.  ST_ERR_STATE while a pipelined iteration is in flight.  The buffer (one image,
+ *   re-created with the input buffers when the size changes) is allocated first: when that fails the call changes nothing.
+ * The mean is CLEARED (items = 0) by this call, by st_optimizer_reset and by what replaces the iterate: st_set_input, st_set_input_nchw,
+ * st_resample_state with new_x_nchw (and a st_forward at another size, which re-creates the input buffers); KEPT across
+ * st_objective_changed, st_set_weights, st_set_content, st_set_style, st_optimizer_set_step; RESAMPLED by st_resample_state without a new
+ * image: the raw mean goes through the Lanczos tables of x (the correction is a scalar and commutes), items is kept.
+ * Tile-sharded mode: st_tile_step updates the mean over the whole window at its end, once that step's x and its refreshed apron are
+ * final; the phase-by-phase entry points (st_tile_update, st_tile_swap, ...) do NOT update it. */
+int st_set_iterate_average(st_ctx* ctx, double decay);
+/* the decay in force (0: off), the item count, and the RAW, uncorrected mean (3,H,W) of the context's image (tile-sharded: the window).
+ * Any pointer may be NULL; mean_nchw with items == 0 is ST_ERR_STATE. */
+int st_get_iterate_average(st_ctx* ctx, double* decay, int* items, float* mean_nchw);
 /* Steps so far that ran as a hipGraph replay.  Opt-in (environment ST2_GRAPH=1; ST2_GRAPH_MAX_PX=<edge>, default 768):
  * steady-state Adam steps are captured once per ping-pong parity and replayed, bit-identical to plain launches.  Measured
  * on MI355X it is no faster (the step is bound by the dependent kernels' execution latency), hence off by default. */
@@ -285,6 +307,10 @@ int st_tile_step(st_ctx* ctx, double* trace);
  * st_tile_update / st_tile_gradient under the current weights. */
 int st_tile_trace(st_ctx* ctx, double* trace);
 int st_tile_get_tile(st_ctx* ctx, float* out_hwc);                           /* this rank's tile of the current iterate, (th, tw, 3) deprocessed */
+/* this rank's tile of the corrected, deprocessed iterate average (st_set_iterate_average), (th, tw, 3): mean / corr + channel mean on the
+ * packed tile, the arithmetic of st_step's averaged image.  ST_ERR_STATE when the mode is off or the mean is empty (only st_tile_step
+ * updates it).  st_tile_get_tile keeps returning the raw iterate. */
+int st_tile_get_tile_average(st_ctx* ctx, float* out_hwc);
 
 /* ---- the style targets of a tile-sharded job, sharded as well -------------------------------------------------------------------
  * st_set_style forwards the WHOLE style image on the context that calls it; in a sharded job every rank would repeat that pass, and the

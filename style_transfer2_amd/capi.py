@@ -80,6 +80,9 @@ PROTOTYPES = {
     'st_step_end': (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_int), POINTER(c_int), c_void_p, POINTER(c_float)]),
     'st_step_pending': (c_int, [c_void_p]),
     'st_step_frame_room': (c_int, [c_void_p, c_size_t, c_size_t]),
+    'st_set_iterate_average': (c_int, [c_void_p, c_double]),
+    'st_get_iterate_average': (c_int, [c_void_p, POINTER(c_double), POINTER(c_int), c_void_p]),
+    'st_tile_get_tile_average': (c_int, [c_void_p, c_void_p]),
     'st_graph_replays': (c_int, [c_void_p, POINTER(c_longlong)]),
     'st_live_bytes': (c_int, [POINTER(c_longlong), POINTER(c_longlong)]),
     'st_lbfgs_inv_hv': (c_int, [c_void_p, c_int, POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_void_p]),

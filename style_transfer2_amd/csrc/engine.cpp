@@ -344,6 +344,8 @@ int ensure_input_buffers(st_ctx* c, int H, int W)
     c->g_cur.reset(); c->pvec.reset();
     for (int i = 0; i <= st_ctx::kCorr; ++i) { c->hs[i].reset(); c->hy[i].reset(); }
     ST_TRY(c->hwc_dev.alloc(n3));
+    c->avg.reset(); c->avg_items = 0;              // the iterate average follows the input's size and starts empty (st_resample_state puts it back)
+    if (c->avg_decay > 0) ST_TRY(c->avg.alloc(n3));
     c->H = H; c->W = W; c->cur = 0;
     // work buffers that follow the input geometry
     for (auto& p : c->inject) p.reset();
@@ -789,6 +791,7 @@ int st_set_input(st_ctx* c, const void* hwc, int H, int W, int is_u8)
     HIP_TRY(hipSetDevice(c->device));
     ST_TRY(set_input_common(c, H, W));
     iterate_overwritten(c);
+    c->avg_items = 0;        // a new iterate: its running mean starts empty
     ST_TRY(preprocess_into(c, hwc, H, W, is_u8, c->x[c->cur]));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return ST_OK;
@@ -801,6 +804,7 @@ int st_set_input_nchw(st_ctx* c, const float* x, int H, int W)
     HIP_TRY(hipSetDevice(c->device));
     ST_TRY(set_input_common(c, H, W));
     iterate_overwritten(c);
+    c->avg_items = 0;        // a new iterate: its running mean starts empty
     HIP_TRY(hipMemcpy(c->x[c->cur], x, (size_t)3 * H * W * sizeof(float), hipMemcpyHostToDevice));
     return ST_OK;
 }

@@ -259,6 +259,10 @@ struct st_ctx {
     DevBuf<float> g_cur, pvec;
     bool have_cur = false;
     float last_loss = 0.f;
+    // iterate averaging (st_set_iterate_average): utils.DecayingMean over the iterates of every optimizer step
+    DevBuf<float> avg;                             // the raw mean, (3, H, W); allocated while the mode is on and an input exists
+    double avg_decay = 0.0;                        // 0: off
+    int avg_items = 0;                             // 0: the mean is empty (the buffer's contents do not count)
     // tile-sharded mode (BASELINE config 5): this context holds ONE window of a larger image
     struct Tile : TileGeom {
         bool on = false;
@@ -395,6 +399,10 @@ int read_trace(st_ctx* c, double* trace, float* loss);
 // ---------------------------------------------------------------------------------------- engine_step.cpp
 int lbfgs_alloc(st_ctx* c);
 LbfgsArgs lbfgs_args(st_ctx* c, int apply);
+// iterate averaging: DecayingMean.__call__(x) on the current iterate, and the corrected, deprocessed mean into hwc where it is not NULL
+// (one launch, booked as P_MISC); average_corr: the divisor float(1 - decay ** items) of utils.py:64
+int average_enqueue(st_ctx* c, float* hwc);
+float average_corr(const st_ctx* c);
 // ---------------------------------------------------------------------------------------- engine_comm.cpp
 void comm_free(st_ctx* c);
 int comm_allreduce(st_ctx* c, float* buf, int n);  // in-place sum of n floats over the ranks, ordered on the engine's stream

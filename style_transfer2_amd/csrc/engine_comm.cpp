@@ -459,6 +459,9 @@ int st_tile_step(st_ctx* c, double* trace)
         if (trace) ST_TRY(st_tile_trace(c, trace));
         c->cur ^= 1;                                                            // st_tile_swap
     }
+    // iterate averaging over the whole window, now that this step's x and its refreshed apron are final (every rank then holds, on its
+    // apron, the mean its neighbours hold on their tiles)
+    if (c->avg_decay > 0) ST_TRY(average_enqueue(c, nullptr));
     c->comm.steps += 1;
     return ST_OK;
 }
@@ -476,9 +479,10 @@ int st_tile_set_style(st_ctx* c, const void* hwc, int H, int W, int is_u8, int g
     return st_tile_style_commit(c);
 }
 
-int st_tile_get_tile(st_ctx* c, float* out_hwc)
+// this rank's tile of a window tensor, packed, then interleaved with the channel means added: deprocess_k, or (corr != 0: the iterate
+// average) the staging form of launch_iterate_average, chw / corr + mean_c -- the arithmetic of the pass that hands out whole images
+static int tile_to_host(st_ctx* c, float* window, float corr, float* out_hwc)
 {
-    if (!c || !c->tile.on || !out_hwc) return fail(ST_ERR_STATE, "st_tile_configure first");
     HIP_TRY(hipSetDevice(c->device));
     const st_ctx::Tile& t = c->tile;
     const int th = t.ty1 - t.ty0, tw = t.tx1 - t.tx0;
@@ -492,12 +496,30 @@ int st_tile_get_tile(st_ctx* c, float* out_hwc)
     int rc = ST_OK;
     {
         std::vector<int> rect = {t.ty0 - t.wy0, t.tx0 - t.wx0, th, tw};
-        rc = strips(c, c->x[c->cur], 3, c->H, c->W, rect, chw, 0);
+        rc = strips(c, window, 3, c->H, c->W, rect, chw, 0);
     }
-    if (rc == ST_OK && launch_deprocess(chw, hwc, th, tw, c->stream) != hipSuccess) rc = fail(ST_ERR_HIP, "deprocess launch failed");
+    if (rc == ST_OK && corr != 0.f) {
+        IterateAverageArgs a{};
+        a.mean = chw; a.hwc = hwc; a.H = th; a.W = tw; a.corr = corr;
+        if (launch_iterate_average(a, c->stream) != hipSuccess) rc = fail(ST_ERR_HIP, "iterate average staging launch failed");
+    } else if (rc == ST_OK && launch_deprocess(chw, hwc, th, tw, c->stream) != hipSuccess) rc = fail(ST_ERR_HIP, "deprocess launch failed");
     if (rc == ST_OK && hipMemcpyAsync(out_hwc, hwc, n * sizeof(float), hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = fail(ST_ERR_HIP, "tile copy failed");
     if (hipStreamSynchronize(c->stream) != hipSuccess && rc == ST_OK) rc = fail(ST_ERR_HIP, "tile copy failed");
     return rc;
+}
+
+int st_tile_get_tile(st_ctx* c, float* out_hwc)
+{
+    if (!c || !c->tile.on || !out_hwc) return fail(ST_ERR_STATE, "st_tile_configure first");
+    return tile_to_host(c, c->x[c->cur], 0.f, out_hwc);
+}
+
+int st_tile_get_tile_average(st_ctx* c, float* out_hwc)
+{
+    if (!c || !c->tile.on || !out_hwc) return fail(ST_ERR_STATE, "st_tile_configure first");
+    if (!(c->avg_decay > 0)) return fail(ST_ERR_STATE, "iterate averaging is off: st_set_iterate_average first");
+    if (c->avg_items == 0) return fail(ST_ERR_STATE, "the iterate average is empty: only st_tile_step updates it (the phase-by-phase entry points do not)");
+    return tile_to_host(c, c->avg, average_corr(c), out_hwc);
 }
 
 }  // extern "C"

@@ -43,27 +43,34 @@ int st_resample_state(st_ctx* c, const st_resample_table* lan_x, const st_resamp
     if (adam) { ST_TRY(table_upload(bil_x, &bx)); ST_TRY(table_upload(bil_y, &by)); }
     const size_t n2 = (size_t)3 * H2 * W2, ntmp = (size_t)3 * H * W2;
     const bool keep_m = adam && !c->m_zero, keep_v = adam && !c->v_zero;
+    // the iterate average: the raw mean goes through x's Lanczos tables (the bias correction is a scalar and commutes), its item count
+    // is kept; a new image starts an empty mean
+    const bool keep_avg = c->avg_decay > 0 && c->avg_items > 0 && !new_x_nchw;
     // (an early return below frees the temporaries and tables while a launch that reads them may still be queued: hipFree waits
     // for the device first, so that is safe)
-    DevBuf<float> tx, tm, tv, tmp;
+    DevBuf<float> tx, tm, tv, ta, tmp;
     ST_TRY(tx.alloc(n2)); ST_TRY(tmp.alloc(ntmp));
     if (keep_m) ST_TRY(tm.alloc(n2));
     if (keep_v) ST_TRY(tv.alloc(n2));
+    if (keep_avg) ST_TRY(ta.alloc(n2));
     if (new_x_nchw) HIP_TRY(hipMemcpyAsync(tx, new_x_nchw, n2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     else HIP_TRY(launch_resample(c->x[c->cur], tmp, tx, 3, H, W, H2, W2, lx.t, ly.t, 0, c->stream));
     if (keep_m) HIP_TRY(launch_resample(c->m, tmp, tm, 3, H, W, H2, W2, lx.t, ly.t, 0, c->stream));
     if (keep_v) HIP_TRY(launch_resample(c->v, tmp, tv, 3, H, W, H2, W2, bx.t, by.t, 1, c->stream));   // np.maximum(0, .)
+    if (keep_avg) HIP_TRY(launch_resample(c->avg, tmp, ta, 3, H, W, H2, W2, lx.t, ly.t, 0, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const bool mz = c->m_zero, vz = c->v_zero;
-    const int i1 = c->items1, i2 = c->items2;
+    const int i1 = c->items1, i2 = c->items2, ia = c->avg_items;
     ST_TRY(ensure_input_buffers(c, H2, W2));           // frees and re-creates x, m, v, L-BFGS vectors
     c->lb_clear = true; c->have_cur = false;
     iterate_overwritten(c);                            // (a resample to the SAME size keeps the buffers)
     HIP_TRY(hipMemcpyAsync(c->x[c->cur], tx, n2 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     if (keep_m) HIP_TRY(hipMemcpyAsync(c->m, tm, n2 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     if (keep_v) HIP_TRY(hipMemcpyAsync(c->v, tv, n2 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    if (keep_avg) HIP_TRY(hipMemcpyAsync(c->avg, ta, n2 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->m_zero = mz; c->v_zero = vz; c->items1 = i1; c->items2 = i2;
+    c->avg_items = keep_avg ? ia : 0;
     return ST_OK;
 }
 

@@ -156,9 +156,66 @@ int step_enqueue(st_ctx* c)
     }
     return ST_OK;
 }
+
+// ---- iterate averaging (utils.DecayingMean, utils.py:49-69, over the iterates) ---------------------------------------------
+float average_corr(const st_ctx* c) { return (float)(1.0 - pow(c->avg_decay, (double)c->avg_items)); }      // utils.py:64, rounded once
+
+// after an optimizer step: mean = decay * mean + (1 - decay) * x, items += 1; hwc (nullable) takes deprocess(mean / corr).  On the
+// engine's stream, outside the captured step graph.
+int average_enqueue(st_ctx* c, float* hwc)
+{
+    const size_t n3 = (size_t)3 * c->H * c->W;
+    if (c->avg.cap() != n3) return fail(ST_ERR_STATE, "internal: the iterate average has no buffer of the input's size");
+    IterateAverageArgs a{};
+    a.x = c->x[c->cur]; a.mean = c->avg; a.hwc = hwc; a.H = c->H; a.W = c->W;
+    a.decay = (float)c->avg_decay; a.rest = (float)(1.0 - c->avg_decay);      // (1 - decay) in double, then fp32: NumPy with a Python scalar
+    a.first = c->avg_items == 0;
+    c->avg_items += 1;
+    a.corr = average_corr(c);
+    ProfScope ps(c, P_MISC, 0, 4.0 * n3 * (2 + (a.first ? 0 : 1) + (hwc ? 1 : 0)));      // x in, mean in (unless empty) and out, the image
+    HIP_TRY(launch_iterate_average(a, c->stream));
+    return ST_OK;
+}
 }  // namespace st2e
 
 extern "C" {
+
+int st_set_iterate_average(st_ctx* c, double decay)
+{
+    if (c) c->epoch++;       // anything but st_step may change what a step launches: captured step graphs are stale
+    if (!c) return fail(ST_ERR_ARG, "ctx is NULL");
+    if (!(decay >= 0.0 && decay < 1.0)) return fail(ST_ERR_ARG, "iterate_average decay must be 0 (off) or inside (0, 1), not %g", decay);
+    if (c->pipe.count) return fail(ST_ERR_STATE, "%d pipelined iteration(s) in flight: st_step_end before st_set_iterate_average", c->pipe.count);
+    HIP_TRY(hipSetDevice(c->device));
+    if (decay == 0.0) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        c->avg.reset();
+        c->avg_decay = 0.0; c->avg_items = 0;
+        return ST_OK;
+    }
+    const size_t n3 = (size_t)3 * c->H * c->W;
+    if (c->x[0] && c->avg.cap() != n3) {           // the buffer first: when that fails nothing has changed
+        DevBuf<float> fresh;
+        ST_TRY(fresh.alloc(n3));
+        c->avg = std::move(fresh);
+    }
+    c->avg_decay = decay; c->avg_items = 0;
+    return ST_OK;
+}
+
+int st_get_iterate_average(st_ctx* c, double* decay, int* items, float* mean_nchw)
+{
+    if (!c) return fail(ST_ERR_ARG, "ctx is NULL");
+    if (mean_nchw && c->avg_items == 0) return fail(ST_ERR_STATE, "the iterate average is empty (%s)", c->avg_decay > 0 ? "no step since it was cleared" : "the mode is off");
+    if (decay) *decay = c->avg_decay;
+    if (items) *items = c->avg_items;
+    if (mean_nchw) {
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipMemcpy(mean_nchw, c->avg, (size_t)3 * c->H * c->W * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return ST_OK;
+}
 
 // ---- optimizers
 int st_optimizer_reset(st_ctx* c, int kind, double step_size)
@@ -171,6 +228,7 @@ int st_optimizer_reset(st_ctx* c, int kind, double step_size)
     c->m_zero = c->v_zero = true;
     c->lb_clear = true;
     c->have_cur = false;
+    c->avg_items = 0;        // a new optimizer: the iterate average starts empty (st_objective_changed keeps it)
     return ST_OK;
 }
 
@@ -227,8 +285,10 @@ int st_step(st_ctx* c, float* out_hwc, double* trace, float* out_loss)
     if (c->pipe.count) return fail(ST_ERR_STATE, "%d pipelined iteration(s) in flight: st_step_end first", c->pipe.count);
     HIP_TRY(hipSetDevice(c->device));
     ST_TRY(step_enqueue(c));
+    // iterate averaging: the update rides on the image pass when an image is wanted, and is a launch of its own otherwise
+    if (c->avg_decay > 0) ST_TRY(average_enqueue(c, out_hwc ? c->hwc_dev.get() : nullptr));
     if (out_hwc) {
-        { ProfScope ps(c, P_MISC, 0, 0); HIP_TRY(launch_deprocess(c->x[c->cur], c->hwc_dev, c->H, c->W, c->stream)); }
+        if (!(c->avg_decay > 0)) { ProfScope ps(c, P_MISC, 0, 0); HIP_TRY(launch_deprocess(c->x[c->cur], c->hwc_dev, c->H, c->W, c->stream)); }
         HIP_TRY(hipMemcpyAsync(out_hwc, c->hwc_dev, (size_t)3 * c->H * c->W * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     }
     if (out_hwc || trace || out_loss) return read_trace(c, trace, out_loss);
@@ -274,7 +334,8 @@ int st_step_begin(st_ctx* c)
     }
     ST_TRY(step_enqueue(c));
     const int slot = (int)((p.head + p.count) % st_ctx::Pipe::kSlots);
-    { ProfScope ps(c, P_MISC, 0, 0); HIP_TRY(launch_deprocess(c->x[c->cur], p.hwc[slot], c->H, c->W, c->stream)); }
+    if (c->avg_decay > 0) ST_TRY(average_enqueue(c, p.hwc[slot]));
+    else { ProfScope ps(c, P_MISC, 0, 0); HIP_TRY(launch_deprocess(c->x[c->cur], p.hwc[slot], c->H, c->W, c->stream)); }
     p.tlen[slot] = c->trace_len_last; p.H[slot] = c->H; p.W[slot] = c->W;
     HIP_TRY(hipMemcpyAsync(p.trace_pin[slot], c->trace_dev, p.tlen[slot] * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipEventRecord(p.ready[slot], c->stream));

@@ -848,6 +848,82 @@ hipError_t launch_deprocess(const float* nchw, float* hwc, int H, int W, hipStre
     return hipGetLastError();
 }
 
+// -------------------------------------------------------------------------------- iterate average
+// DecayingMean (utils.py:49-69) over the iterates, and the image handed out, in one pass over four streams: the planar x and mean are
+// read, mean = decay * mean + rest * x (two products and a sum, NumPy's float32 arithmetic: this file is built with -ffp-contract=off) is
+// written, and, where an image is wanted, hwc = mean / corr + kMean[c] (one IEEE division) goes out interleaved.  UPDATE = false is the
+// staging form: `mean` is only read and divided (a packed tile on its way to the host).  VEC: a thread owns 4 consecutive pixels -- three
+// 16-byte reads of x and of mean, three 16-byte writes of mean, the 12 consecutive floats of hwc as three 16-byte writes; else one pixel.
+template <bool UPDATE, bool VEC>
+__global__ __launch_bounds__(256) void iterate_average_k(const IterateAverageArgs a)
+{
+    const size_t plane = (size_t)a.H * a.W;
+    const size_t n = VEC ? plane / 4 : plane;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        if (VEC) {
+            float4 m[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const size_t at = (size_t)c * plane + i * 4;
+                if (UPDATE) {
+                    const float4 x = *reinterpret_cast<const float4*>(a.x + at);
+                    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (!a.first) o = *reinterpret_cast<const float4*>(a.mean + at);
+                    m[c].x = a.decay * o.x + a.rest * x.x;
+                    m[c].y = a.decay * o.y + a.rest * x.y;
+                    m[c].z = a.decay * o.z + a.rest * x.z;
+                    m[c].w = a.decay * o.w + a.rest * x.w;
+                    *reinterpret_cast<float4*>(a.mean + at) = m[c];
+                } else
+                    m[c] = *reinterpret_cast<const float4*>(a.mean + at);
+            }
+            if (a.hwc) {
+                float r[3][4];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    r[c][0] = __fdiv_rn(m[c].x, a.corr) + kMean[c];
+                    r[c][1] = __fdiv_rn(m[c].y, a.corr) + kMean[c];
+                    r[c][2] = __fdiv_rn(m[c].z, a.corr) + kMean[c];
+                    r[c][3] = __fdiv_rn(m[c].w, a.corr) + kMean[c];
+                }
+                float4* out = reinterpret_cast<float4*>(a.hwc + i * 12);
+                out[0] = make_float4(r[0][0], r[1][0], r[2][0], r[0][1]);
+                out[1] = make_float4(r[1][1], r[2][1], r[0][2], r[1][2]);
+                out[2] = make_float4(r[2][2], r[0][3], r[1][3], r[2][3]);
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const size_t at = (size_t)c * plane + i;
+                float m;
+                if (UPDATE) {
+                    const float o = a.first ? 0.f : a.mean[at];
+                    m = a.decay * o + a.rest * a.x[at];
+                    a.mean[at] = m;
+                } else
+                    m = a.mean[at];
+                if (a.hwc) a.hwc[i * 3 + c] = __fdiv_rn(m, a.corr) + kMean[c];
+            }
+        }
+    }
+}
+
+hipError_t launch_iterate_average(const IterateAverageArgs& a, hipStream_t s)
+{
+    const size_t plane = (size_t)a.H * a.W;
+    if (!plane) return hipSuccess;
+    const bool vec = plane % 4 == 0 && (((uintptr_t)a.x | (uintptr_t)a.mean | (uintptr_t)a.hwc) & 15) == 0;
+    const int grid = reduce_grid(vec ? plane / 4 : plane, 256, 2048);
+    if (a.x) {
+        if (vec) iterate_average_k<true, true><<<grid, 256, 0, s>>>(a);
+        else iterate_average_k<true, false><<<grid, 256, 0, s>>>(a);
+    } else {
+        if (vec) iterate_average_k<false, true><<<grid, 256, 0, s>>>(a);
+        else iterate_average_k<false, false><<<grid, 256, 0, s>>>(a);
+    }
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------- trace scalars
 // Stage 1: one workgroup per partial-sum slot (layer x 6 + 6 image slots) -> a.sums[slot] (double).
 __global__ __launch_bounds__(256) void trace_sums_k(const TraceArgs a)

@@ -327,6 +327,12 @@ hipError_t launch_resample(const float* src, float* tmp, float* dst, int planes,
 hipError_t launch_preprocess_u8(const uint8_t* hwc, float* nchw, int H, int W, hipStream_t s);
 hipError_t launch_preprocess_f32(const float* hwc, float* nchw, int H, int W, hipStream_t s);
 hipError_t launch_deprocess(const float* nchw, float* hwc, int H, int W, hipStream_t s);
+// The running mean of the iterates (utils.DecayingMean, utils.py:49-69) and the image handed out, in one pass: mean = decay * mean +
+// rest * x in fp32 without contraction (first: the mean is empty and counts as 0, the buffer is not read), and, where hwc is not NULL,
+// hwc = mean / corr + channel mean, interleaved (H, W, 3).  x == NULL: `mean` is only read (a packed (3, H, W) tile being staged).
+// 16-byte accesses on every stream where H * W % 4 == 0 and the three pointers are 16-byte aligned, one pixel per thread otherwise.
+struct IterateAverageArgs { const float* x; float* mean; float* hwc; int H, W; float decay, rest, corr; int first; };
+hipError_t launch_iterate_average(const IterateAverageArgs& a, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
 // trace finalisation: one tiny kernel turns the partial sums of an opfunc into the trace scalars

@@ -387,6 +387,24 @@ class Engine:
             return view, trace, F32(loss.value), buf
         return view, trace, F32(loss.value)
 
+    def set_iterate_average(self, decay):
+        """0 (default): step() / step_end() hand out the raw iterate.  0 < decay < 1: they hand out the bias-corrected exponentially
+        weighted mean of the iterates (utils.DecayingMean over x after every optimizer step); the mean starts empty.  The trajectory,
+        the trace and get_input_nchw() are unchanged.  Refused while a pipelined iteration is in flight."""
+        check(self.lib.st_set_iterate_average(self._ctx, float(decay)))
+
+    def iterate_average(self, want_mean=True):
+        """(decay, items, mean): the decay in force (0.0: off), the number of iterates averaged, and the raw, uncorrected mean as a
+        (1, 3, H, W) array -- None while it is empty, or when want_mean is False."""
+        decay, items = c_double(), c_int()
+        check(self.lib.st_get_iterate_average(self._ctx, byref(decay), byref(items), None))
+        if not items.value or not want_mean:
+            return decay.value, items.value, None
+        h, w = self.input_shape()
+        mean = np.empty((1, 3, h, w), F32)
+        check(self.lib.st_get_iterate_average(self._ctx, None, None, _ptr(mean)))
+        return decay.value, items.value, mean
+
     def steps_pending(self):
         return int(self.lib.st_step_pending(self._ctx))
 

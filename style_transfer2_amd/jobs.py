@@ -38,9 +38,11 @@ def load_rgb(path):
 
 
 def run_job(transfer, content, style, iterations, size=None, style_size=None, optimizer='adam', step_size=None,
-            weights=None, params=None, init=None, seed=0, callback=None):
+            weights=None, params=None, init=None, seed=0, callback=None, iterate_average=None):
     """One whole stylisation: content/style are PIL images or HxWx3 arrays.  Returns the final HxWx3 float32
-    image.  Mirrors app.init_arrays + 'start': SetImages(reset) -> SetWeights -> SetOptimizer -> iterate."""
+    image.  Mirrors app.init_arrays + 'start': SetImages(reset) -> SetWeights -> SetOptimizer -> iterate.
+    iterate_average: a decay in (0, 1) makes every image handed out (the callback's, the result) the bias-corrected running mean of
+    the iterates (Engine.set_iterate_average); 0 turns that off; None leaves the engine as it is."""
     from .device_optimizers import AdamOptimizer, LBFGSOptimizer
     if isinstance(content, Image.Image):
         content = np.uint8(resize_to_fit(content, size or max(content.size)))
@@ -56,6 +58,8 @@ def run_job(transfer, content, style, iterations, size=None, style_size=None, op
     transfer.optimizer_cls = {'adam': AdamOptimizer, 'lbfgs': LBFGSOptimizer}[optimizer]
     transfer.set_step_size(step_size if step_size else {'adam': 10, 'lbfgs': 1}[optimizer])
     transfer.reset()
+    if iterate_average is not None:
+        transfer.engine.set_iterate_average(iterate_average)
     if not transfer.start():
         raise RuntimeError('job could not start: inconsistent images')
     image = None
@@ -71,7 +75,8 @@ def run_job(transfer, content, style, iterations, size=None, style_size=None, op
 
 
 def run_tiled_job(net_params, content, style, iterations, grid, size=None, style_size=None, weights=None, params=None, init=None,
-                  seed=0, device=0, precision='fp32', topology=None, callback=None, optimizer='adam', step_size=None, shard_style=False):
+                  seed=0, device=0, precision='fp32', topology=None, callback=None, optimizer='adam', step_size=None, shard_style=False,
+                  iterate_average=None):
     """The same job for an image no single engine holds (an 8192 x 8192 image has conv1 blobs of 17 GB each): the image is cut into
     grid = (rows, cols) tiles, every tile + apron is an engine context of THIS process on the one GPU (tiled.InProcessFabric: one
     thread per rank, the all-reduces and strip exchanges are device-to-device copies); one st_tile_step per rank and iteration, Adam or
@@ -79,6 +84,8 @@ def run_tiled_job(net_params, content, style, iterations, grid, size=None, style
     Same result as run_job where both can run (tests/test_gpu_jobs.py).  Image edges must be multiples of 16 * rows / cols
     (tiling.TileGrid).  shard_style: the style image is cut as well (tiling.style_grid over the same ranks, up to the deepest
     style-weighted blob) and every rank forwards one window of it, instead of every rank forwarding all of it.
+    iterate_average: a decay in (0, 1) makes every rank keep the running mean of its window's iterates; the stitched image is then the
+    bias-corrected mean, as run_job's is.
     Returns the stitched HxWx3 float32 image; callback(i, trace values) after every iteration."""
     from . import tiled, tiling
     from .engine import VGG19_TOPOLOGY
@@ -100,7 +107,7 @@ def run_tiled_job(net_params, content, style, iterations, grid, size=None, style
     ranks, backends = [], []
     for r in range(world):
         b = HipTileBackend(net_params, tg, r, content, None if shard_style else style, init, weights, params, step_size=step_size or {'adam': 10, 'lbfgs': 1}[optimizer],
-                           topology=topology, device=device, precision=precision, optimizer=optimizer)
+                           topology=topology, device=device, precision=precision, optimizer=optimizer, iterate_average=iterate_average)
         backends.append(b)
         b.comm_init_local(r, world, fabric)
         ranks.append(tiled.FusedTiledTransfer(tg, r, b))

@@ -39,7 +39,7 @@ torch = _LazyTorch()
 
 class HipTileBackend:
     def __init__(self, net_params, grid, rank, content, style, init, weights, params, step_size=10,
-                 topology=None, device=0, precision='fp32', use_torch=True, optimizer='adam'):
+                 topology=None, device=0, precision='fp32', use_torch=True, optimizer='adam', iterate_average=None):
         # torch bundles its own copy of the HIP runtime; when both live in one process torch's must come up FIRST.
         # The phase-by-phase driver and the host-staged test transport need torch; the in-engine iteration over RCCL
         # (comm_init_rccl + tiled.FusedTiledTransfer) does not: pass use_torch=False and the process never loads it.
@@ -70,6 +70,9 @@ class HipTileBackend:
             raise ValueError('optimizer must be adam or lbfgs')
         self.engine.optimizer_reset(OPT_LBFGS if optimizer == 'lbfgs' else OPT_ADAM, step_size)
         self.engine.clear_norms()
+        # iterate averaging (Engine.set_iterate_average): st_tile_step keeps the running mean of the window; averaged_image() reads the tile
+        if iterate_average:
+            self.engine.set_iterate_average(iterate_average)
         check(self.lib.st_tile_configure(self.ctx, grid.gH, grid.gW, w.y0, w.x0, t.y0, t.x0, t.y1, t.x1))
         self.wh, self.ww = w.y1 - w.y0, w.x1 - w.x0
 
@@ -232,6 +235,19 @@ class HipTileBackend:
         t = self.grid.tiles[self.rank]
         out = np.empty((t.y1 - t.y0, t.x1 - t.x0, 3), F32)
         check(self.lib.st_tile_get_tile(self.ctx, out.ctypes.data_as(c_void_p)))
+        return out
+
+    def averaging(self):
+        """True once the engine holds a running mean of this window's iterates (the mode is on and a fused step has run)."""
+        decay, items, _ = self.engine.iterate_average(want_mean=False)
+        return bool(decay and items)
+
+    def averaged_image(self):
+        """This rank's tile of the corrected, deprocessed iterate average (st_tile_get_tile_average): an error while the mode is off or
+        no fused step has run since the mean was cleared."""
+        t = self.grid.tiles[self.rank]
+        out = np.empty((t.y1 - t.y0, t.x1 - t.x0, 3), F32)
+        check(self.lib.st_tile_get_tile_average(self.ctx, out.ctypes.data_as(c_void_p)))
         return out
 
     def _buf(self, which, shape):

@@ -332,7 +332,9 @@ class FusedTiledTransfer:
         self.backend.step_fused_async()
 
     def tile_image(self):
-        return self.backend.tile_image()
+        """This rank's tile of the image the job hands out: the iterate, or its running mean where the backend averages the iterates
+        (HipTileBackend(iterate_average=d)) and at least one step has run."""
+        return self.backend.averaged_image() if self.backend.averaging() else self.backend.tile_image()
 
 
 class InProcessFabric:

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Headless stylisation job on one MI355X:  stylize.py content.jpg style.jpg out.png [--size 512] [--iters 500]
 --grid RxC: an image too large for one engine (beyond about 4096 x 4096) is cut into R x C tiles that all live on the one GPU
-(jobs.run_tiled_job; the image edges must divide into tiles of multiples of 16 pixels)."""
+(jobs.run_tiled_job; the image edges must divide into tiles of multiples of 16 pixels).
+--avg-decay D: the image written is the bias-corrected exponentially weighted mean of the iterates (st_set_iterate_average), not
+the last iterate."""
 import argparse
 import os
 import sys
@@ -9,48 +11,69 @@ import sys
 import numpy as np
 from PIL import Image
 
-ap = argparse.ArgumentParser()
-ap.add_argument('content'); ap.add_argument('style'); ap.add_argument('out')
-ap.add_argument('--size', type=int, default=512)
-ap.add_argument('--style-size', type=int, default=0)
-ap.add_argument('--iters', type=int, default=500)
-ap.add_argument('--optimizer', default='adam', choices=['adam', 'lbfgs'])
-ap.add_argument('--weights', default='', help='.npz or .caffemodel; default: seeded synthetic weights')
-ap.add_argument('--gpu', type=int, default=0)
-ap.add_argument('--precision', default='fp32', choices=['fp32', 'bf16', 'bf16-full'], help='st_set_precision: conv operands in fp32 or bf16')
-ap.add_argument('--conv-algo', type=int, default=None, choices=[0, 1, 2], help='st_set_conv_algo (default: the engine\'s, 1)')
-ap.add_argument('--gram-algo', type=int, default=None, choices=[0, 1], help='st_set_gram_algo (default: the engine\'s, 0)')
-ap.add_argument('--ave-pools', action='store_true', help='VGG19 with every pool an average pool (Caffe `pool: AVE`; the pooling of vgg_normalised-style weights)')
-ap.add_argument('--pool-algo', type=int, default=None, choices=[0, 1], help='st_set_pool_algo (default: the engine\'s, 0); 1 fuses average pools into the bf16 conv launches (--precision bf16)')
-ap.add_argument('--grid', default='', help='RxC: tile-shard the image over this one GPU (large images)')
-ap.add_argument('--shard-style', action='store_true', help='with --grid: cut the style image over the ranks as well (every rank forwards one window of it)')
-args = ap.parse_args()
-if args.ave_pools and args.grid:
-    ap.error('--ave-pools with --grid: tile-sharded mode does not run average pools')
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import style_transfer2_amd as st2                                   # noqa: E402
-from style_transfer2_amd import jobs, weights as st2_weights         # noqa: E402
+def avg_decay(text):
+    value = float(text)
+    if not 0.0 <= value < 1.0:
+        raise argparse.ArgumentTypeError('a decay in [0, 1) (0: off), not %r' % text)
+    return value
 
-topology = st2.VGG19_TOPOLOGY
-if args.ave_pools:
-    topology = tuple(('pool', layer[1], 'ave') if layer[0] == 'pool' else layer for layer in topology)
 
-if args.weights.endswith('.npz'):
-    params = st2_weights.load_npz(args.weights, st2.VGG19_TOPOLOGY)
-elif args.weights.endswith('.caffemodel'):
-    from style_transfer2_amd import caffemodel
-    params = caffemodel.vgg_params(caffemodel.read_caffemodel(args.weights), st2.VGG19_TOPOLOGY)
-else:
-    params = st2_weights.he_normal(st2.VGG19_TOPOLOGY, seed=0)
-if args.grid:
-    rows, cols = (int(v) for v in args.grid.split('x'))
-    image = jobs.run_tiled_job(params, jobs.load_rgb(args.content), jobs.load_rgb(args.style), args.iters, (rows, cols), size=args.size,
-                               style_size=args.style_size or None, device=args.gpu, optimizer=args.optimizer, shard_style=args.shard_style)
-else:
-    job = st2.StyleTransfer(st2.HipModel(params, topology=None if topology is st2.VGG19_TOPOLOGY else topology, device=args.gpu, precision=args.precision,
-                                         conv_algo=args.conv_algo, gram_algo=args.gram_algo, pool_algo=args.pool_algo))
-    image = jobs.run_job(job, jobs.load_rgb(args.content), jobs.load_rgb(args.style), args.iters, size=args.size,
-                         style_size=args.style_size or None, optimizer=args.optimizer)
-Image.fromarray(np.uint8(np.clip(image, 0, 255))).save(args.out)
-print('wrote', args.out, image.shape)
+def parser():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('content'); ap.add_argument('style'); ap.add_argument('out')
+    ap.add_argument('--size', type=int, default=512)
+    ap.add_argument('--style-size', type=int, default=0)
+    ap.add_argument('--iters', type=int, default=500)
+    ap.add_argument('--optimizer', default='adam', choices=['adam', 'lbfgs'])
+    ap.add_argument('--weights', default='', help='.npz or .caffemodel; default: seeded synthetic weights')
+    ap.add_argument('--gpu', type=int, default=0)
+    ap.add_argument('--precision', default='fp32', choices=['fp32', 'bf16', 'bf16-full'], help='st_set_precision: conv operands in fp32 or bf16')
+    ap.add_argument('--conv-algo', type=int, default=None, choices=[0, 1, 2], help='st_set_conv_algo (default: the engine\'s, 1)')
+    ap.add_argument('--gram-algo', type=int, default=None, choices=[0, 1], help='st_set_gram_algo (default: the engine\'s, 0)')
+    ap.add_argument('--ave-pools', action='store_true', help='VGG19 with every pool an average pool (Caffe `pool: AVE`; the pooling of vgg_normalised-style weights)')
+    ap.add_argument('--pool-algo', type=int, default=None, choices=[0, 1], help='st_set_pool_algo (default: the engine\'s, 0); 1 fuses average pools into the bf16 conv launches (--precision bf16)')
+    ap.add_argument('--grid', default='', help='RxC: tile-shard the image over this one GPU (large images)')
+    ap.add_argument('--shard-style', action='store_true', help='with --grid: cut the style image over the ranks as well (every rank forwards one window of it)')
+    ap.add_argument('--avg-decay', type=avg_decay, default=None, metavar='D',
+                    help='st_set_iterate_average: write the bias-corrected running mean of the iterates with this decay, 0 < D < 1 (default: the last iterate)')
+    return ap
+
+
+def main(argv=None):
+    ap = parser()
+    args = ap.parse_args(argv)
+    if args.ave_pools and args.grid:
+        ap.error('--ave-pools with --grid: tile-sharded mode does not run average pools')
+
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import style_transfer2_amd as st2
+    from style_transfer2_amd import jobs, weights as st2_weights
+
+    topology = st2.VGG19_TOPOLOGY
+    if args.ave_pools:
+        topology = tuple(('pool', layer[1], 'ave') if layer[0] == 'pool' else layer for layer in topology)
+
+    if args.weights.endswith('.npz'):
+        params = st2_weights.load_npz(args.weights, st2.VGG19_TOPOLOGY)
+    elif args.weights.endswith('.caffemodel'):
+        from style_transfer2_amd import caffemodel
+        params = caffemodel.vgg_params(caffemodel.read_caffemodel(args.weights), st2.VGG19_TOPOLOGY)
+    else:
+        params = st2_weights.he_normal(st2.VGG19_TOPOLOGY, seed=0)
+    if args.grid:
+        rows, cols = (int(v) for v in args.grid.split('x'))
+        image = jobs.run_tiled_job(params, jobs.load_rgb(args.content), jobs.load_rgb(args.style), args.iters, (rows, cols), size=args.size,
+                                   style_size=args.style_size or None, device=args.gpu, optimizer=args.optimizer, shard_style=args.shard_style,
+                                   iterate_average=args.avg_decay)
+    else:
+        job = st2.StyleTransfer(st2.HipModel(params, topology=None if topology is st2.VGG19_TOPOLOGY else topology, device=args.gpu, precision=args.precision,
+                                             conv_algo=args.conv_algo, gram_algo=args.gram_algo, pool_algo=args.pool_algo))
+        image = jobs.run_job(job, jobs.load_rgb(args.content), jobs.load_rgb(args.style), args.iters, size=args.size,
+                             style_size=args.style_size or None, optimizer=args.optimizer, iterate_average=args.avg_decay)
+    Image.fromarray(np.uint8(np.clip(image, 0, 255))).save(args.out)
+    print('wrote', args.out, image.shape)
+
+
+if __name__ == '__main__':
+    main()

@@ -93,6 +93,23 @@ def read_algo_keys(config):
     return kwargs
 
 
+def read_iterate_average(config):
+    """The optional config key ``iterate_average = <decay>``: with a decay in (0, 1) every ``Iterate`` carries the bias-corrected
+    exponentially weighted mean of the iterates so far (Engine.set_iterate_average) instead of the raw iterate; 0 is off.  Returns the
+    decay as a float, or None when the key is absent or empty (no call is made: the engine's default, off, stays); a value that is
+    no number or lies outside [0, 1) is a ValueError that names the key.  Pure: any mapping with ``get`` will do."""
+    raw = config.get('iterate_average', None)
+    if raw is None or str(raw).strip() == '':
+        return None
+    try:
+        value = float(str(raw).strip())
+    except ValueError:
+        value = None
+    if value is None or not 0.0 <= value < 1.0:           # (NaN fails both comparisons)
+        raise ValueError('config key iterate_average = %r: must be a decay in [0, 1) (0: off)' % (raw,))
+    return value
+
+
 def build_transfer(config):
     """Model + StyleTransfer for this worker (reference worker.py:326-332).  Exits with code 2 when the
     HIP library, the GPU or the weights are missing."""
@@ -287,6 +304,11 @@ class Worker:
         try:
             # the model first (it may sys.exit(2): reference worker.py:51-53), the sender thread only once it exists
             self.transfer = transfer if transfer is not None else build_transfer(config)
+            # iterate averaging (config key iterate_average): the Iterate images become the running mean of the iterates; their index,
+            # the trace and the order of everything on the wire stay as they are
+            decay = read_iterate_average(config)
+            if decay is not None:
+                self.transfer.engine.set_iterate_average(decay)
             async_send = str(config.get('async_iterate', '1')).lower() not in ('0', 'false', 'no')
             if async_send:
                 self.sock_out = AsyncSender(sock_out)
