@@ -3,7 +3,9 @@
 It restates, for ONE tile of a sharded image, exactly what oracle.TransferOracle does for the whole image
 (worker.py:231-310, utils.py:285-304, optimizers.py:20-27), with every reduction restricted to the tile's region
 of each blob and normalised by the GLOBAL element counts.  Used to validate the distributed algorithm on the CPU
-(gloo) against the single-process oracle, and as the checker of the HIP tile backend.
+(gloo, or ranks as threads) against the single-process oracle, and -- on a 1 x 1 grid of the whole image -- as the per-pixel
+reference of the HIP tile backend's network-side and combined gradients (seam_oracle.py, test_gpu_seams.py).
+operands='bf16' builds it over oracle.NetOracle(..., operands='bf16'): the reference of the runs with bf16 conv operands.
 """
 import numpy as np
 import torch
@@ -17,8 +19,8 @@ EPS_W = 1e-15
 
 
 class OracleTileBackend:
-    def __init__(self, topology, net_params, grid, rank, content, style, init, weights, params, step_size=10):
-        self.net = oracle.NetOracle(topology, net_params)
+    def __init__(self, topology, net_params, grid, rank, content, style, init, weights, params, step_size=10, operands='fp32'):
+        self.net = oracle.NetOracle(topology, net_params, operands=operands)
         self.grid, self.rank = grid, rank
         self.win, self.tile = grid.windows[rank], grid.tiles[rank]
         w, t = self.win, self.tile
