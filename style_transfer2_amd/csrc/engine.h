@@ -399,10 +399,14 @@ int read_trace(st_ctx* c, double* trace, float* loss);
 // ---------------------------------------------------------------------------------------- engine_step.cpp
 int lbfgs_alloc(st_ctx* c);
 LbfgsArgs lbfgs_args(st_ctx* c, int apply);
+int lbfgs_clear_history(st_ctx* c, bool gram_form);        // what lbfgs_step and the fused tile step do while c->lb_clear is set
 // iterate averaging: DecayingMean.__call__(x) on the current iterate, and the corrected, deprocessed mean into hwc where it is not NULL
 // (one launch, booked as P_MISC); average_corr: the divisor float(1 - decay ** items) of utils.py:64
 int average_enqueue(st_ctx* c, float* hwc);
 float average_corr(const st_ctx* c);
+// ---------------------------------------------------------------------------------------- engine_tile.cpp
+// pack (mode 0) / unpack (1 assign, 2 add) the rectangles (y0, x0, h, w each) of a (C, h, w) tensor; checks them against it; enqueues only
+int strips(st_ctx* c, float* tensor, int C, int h, int w, const std::vector<int>& rects, float* buf, int mode);
 // ---------------------------------------------------------------------------------------- engine_comm.cpp
 void comm_free(st_ctx* c);
 int comm_allreduce(st_ctx* c, float* buf, int n);  // in-place sum of n floats over the ranks, ordered on the engine's stream

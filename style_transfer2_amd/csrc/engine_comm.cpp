@@ -85,29 +85,6 @@ int comm_allreduce(st_ctx* c, float* buf, int n)
     return ST_OK;
 }
 
-static int strips(st_ctx* c, float* tensor, int C, int h, int w, const std::vector<int>& rects, float* buf, int mode)
-{
-    const int n = (int)rects.size() / 4;
-    size_t off = 0;
-    for (int r0 = 0; r0 < n; r0 += kMaxStripRects) {        // at most kMaxStripRects rectangles per launch
-        StripTable t{};
-        t.n = std::min(kMaxStripRects, n - r0);
-        int total = 0;
-        for (int r = 0; r < t.n; ++r) {
-            const int* q = &rects[4 * (r0 + r)];
-            t.y0[r] = q[0]; t.x0[r] = q[1]; t.h[r] = q[2]; t.w[r] = q[3];
-            if (q[0] < 0 || q[1] < 0 || q[2] <= 0 || q[3] <= 0 || q[0] + q[2] > h || q[1] + q[3] > w)
-                return fail(ST_ERR_ARG, "planned strip %d lies outside the %dx%d tensor", r0 + r, h, w);
-            t.off[r] = total;
-            total += C * q[2] * q[3];
-        }
-        t.total = total;
-        HIP_TRY(launch_strip_copy(tensor, buf + off, t, C, h, w, mode, c->stream));
-        off += (size_t)total;
-    }
-    return ST_OK;
-}
-
 // One exchange phase: pack what each neighbour gets out of `src`, one message per neighbour, unpack (assign / add) into `dst`.
 static int comm_exchange(st_ctx* c, int phase, float* src, int sh, int sw, float* dst, int dh, int dw, bool add)
 {
@@ -378,13 +355,7 @@ static int tile_lbfgs_step(st_ctx* c)
         a.n = n_t; a.n_global = (size_t)3 * t.gH * t.gW; a.x = t.lb_x; a.gsums = t.lb_sums;
         return a;
     };
-    if (c->lb_clear) {              // objective_changed / a new optimizer: sy = [], ss = [], ys = [] (optimizers.py:121-125)
-        HIP_TRY(hipMemsetAsync(c->lb_dev, 0, sizeof(LbfgsDev), s));
-        HIP_TRY(hipMemsetAsync(c->lb_gram, 0, sizeof(LbfgsGram), s));
-        c->lb_clear = false;
-        c->lb_gram_form = true;
-        c->have_cur = false;
-    }
+    if (c->lb_clear) ST_TRY(lbfgs_clear_history(c, true));
     if (!c->lb_gram_form) return fail(ST_ERR_STATE, "the history was built by the chain form: reset the optimizer before the fused tile-sharded L-BFGS");
     if (!c->have_cur) {             // optimizers.py:64-65: loss, grad at the starting point
         ST_TRY(tile_evaluate(c, false));

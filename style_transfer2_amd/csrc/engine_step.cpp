@@ -41,6 +41,19 @@ LbfgsArgs lbfgs_args(st_ctx* c, int apply)
     return a;
 }
 
+// The history to be emptied (c->lb_clear: objective_changed / a new optimizer): sy = [], ss = [], ys = [] (optimizers.py:121-125), and
+// the form the new history is built in.  In the Gram form the gradient's inner products belong to the history that was just dropped,
+// so the starting evaluation runs again; the chain form keeps the gradient it has.
+int lbfgs_clear_history(st_ctx* c, bool gram_form)
+{
+    HIP_TRY(hipMemsetAsync(c->lb_dev, 0, sizeof(LbfgsDev), c->stream));
+    HIP_TRY(hipMemsetAsync(c->lb_gram, 0, sizeof(LbfgsGram), c->stream));
+    c->lb_clear = false;
+    c->lb_gram_form = gram_form;
+    if (gram_form) c->have_cur = false;
+    return ST_OK;
+}
+
 // One LBFGSOptimizer.step (optimizers.py:62-77).  Nothing is read back: the pair count, the ring order and the
 // s.y > 1e-10 decision live on the device (lbfgs.hip), so consecutive steps queue up like Adam steps do.
 int lbfgs_step(st_ctx* c)
@@ -49,13 +62,7 @@ int lbfgs_step(st_ctx* c)
     const size_t n = (size_t)3 * c->H * c->W;
     float* x = c->x[c->cur];
     hipStream_t s = c->stream;
-    if (c->lb_clear) {              // objective_changed / a new optimizer: sy = [], ss = [], ys = [] (optimizers.py:121-125)
-        HIP_TRY(hipMemsetAsync(c->lb_dev, 0, sizeof(LbfgsDev), s));
-        HIP_TRY(hipMemsetAsync(c->lb_gram, 0, sizeof(LbfgsGram), s));
-        c->lb_clear = false;
-        c->lb_gram_form = lbfgs_wants_gram(c);
-        if (c->lb_gram_form) c->have_cur = false;      // (the gradient's inner products belong to the history that was just dropped)
-    }
+    if (c->lb_clear) ST_TRY(lbfgs_clear_history(c, lbfgs_wants_gram(c)));
     const bool gram = c->lb_gram_form;
     if (!c->have_cur) {             // optimizers.py:64-65
         ST_TRY(eval_objective(c, x, true, c->g_cur, false, nullptr));

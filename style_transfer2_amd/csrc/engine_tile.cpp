@@ -84,6 +84,32 @@ static int tile_image_pass(st_ctx* c, const float* ring_dev, bool adam, float** 
     if (n_floats) *n_floats = 6 + (c->tile.s2_in_p2 ? 0 : terms.n_style);
     return ST_OK;
 }
+
+// Pack (mode 0) the rectangles `rects` (y0, x0, h, w each) of the (C, h, w) device tensor into the contiguous buffer `buf`, or unpack
+// them from it (1 assign, 2 add), at most kMaxStripRects per launch: the one place that fills a StripTable and holds the rectangles
+// to the tensor.  Enqueues only.
+int strips(st_ctx* c, float* tensor, int C, int h, int w, const std::vector<int>& rects, float* buf, int mode)
+{
+    const int n = (int)rects.size() / 4;
+    size_t off = 0;
+    for (int r0 = 0; r0 < n; r0 += kMaxStripRects) {
+        StripTable t{};
+        t.n = std::min(kMaxStripRects, n - r0);
+        int total = 0;
+        for (int r = 0; r < t.n; ++r) {
+            const int* q = &rects[4 * (r0 + r)];
+            t.y0[r] = q[0]; t.x0[r] = q[1]; t.h[r] = q[2]; t.w[r] = q[3];
+            if (q[0] < 0 || q[1] < 0 || q[2] <= 0 || q[3] <= 0 || q[0] + q[2] > h || q[1] + q[3] > w)
+                return fail(ST_ERR_ARG, "strip %d lies outside the %dx%d tensor", r0 + r, h, w);
+            t.off[r] = total;
+            total += C * q[2] * q[3];
+        }
+        t.total = total;
+        HIP_TRY(launch_strip_copy(tensor, buf + off, t, C, h, w, mode, c->stream));
+        off += (size_t)total;
+    }
+    return ST_OK;
+}
 }  // namespace st2e
 
 extern "C" {
@@ -309,18 +335,7 @@ int st_tile_strips(st_ctx* c, void* tensor_dev, int C, int wh, int ww, int n, co
 {
     if (!c || !tensor_dev || !buf_dev || n < 0 || n > kMaxStripRects || (n && !rects) || mode < 0 || mode > 2) return fail(ST_ERR_ARG, "bad argument");
     HIP_TRY(hipSetDevice(c->device));
-    StripTable t{};
-    t.n = n;
-    int total = 0;
-    for (int r = 0; r < n; ++r) {
-        t.y0[r] = rects[4 * r]; t.x0[r] = rects[4 * r + 1]; t.h[r] = rects[4 * r + 2]; t.w[r] = rects[4 * r + 3];
-        if (t.y0[r] < 0 || t.x0[r] < 0 || t.h[r] <= 0 || t.w[r] <= 0 || t.y0[r] + t.h[r] > wh || t.x0[r] + t.w[r] > ww)
-            return fail(ST_ERR_ARG, "strip %d lies outside the %dx%d window", r, wh, ww);
-        t.off[r] = total;
-        total += C * t.h[r] * t.w[r];
-    }
-    t.total = total;
-    HIP_TRY(launch_strip_copy((float*)tensor_dev, (float*)buf_dev, t, C, wh, ww, mode, c->stream));
+    ST_TRY(strips(c, (float*)tensor_dev, C, wh, ww, std::vector<int>(rects, rects + 4 * n), (float*)buf_dev, mode));
     ST_TRY(tile_sync(c));
     return ST_OK;
 }

@@ -10,6 +10,7 @@ import numpy as np
 from . import capi
 from .capi import check
 from .engine import Engine, OPT_ADAM, OPT_LBFGS
+from .tiled import crop, local_rect, torch          # (torch: tiled's lazy import -- nothing here loads it at import time)
 from .transfer import weight_table, LOSS_NAMES, SCALAR_LOSS_NAMES
 
 F32 = np.float32
@@ -24,17 +25,6 @@ class _DevArray:
 def dev_tensor(ptr, shape, device):
     import torch
     return torch.as_tensor(_DevArray(ptr, shape), device=device)
-
-
-class _LazyTorch:
-    """torch is needed only by the phase-by-phase driver (tiled.TiledTransfer: device buffers handed to torch.distributed) and by the
-    host-staged test transport.  The in-engine iteration (st_tile_step over RCCL) never imports it: one HIP runtime in the process."""
-    def __getattr__(self, name):
-        import torch
-        return getattr(torch, name)
-
-
-torch = _LazyTorch()
 
 
 class HipTileBackend:
@@ -56,7 +46,6 @@ class HipTileBackend:
         self.device_index = device
         self.grid, self.rank = grid, rank
         w, t = grid.windows[rank], grid.tiles[rank]
-        crop = lambda im, r: np.ascontiguousarray(im[r.y0:r.y1, r.x0:r.x1])
         self.engine.set_input(crop(init, w))
         self.engine.set_content(crop(content, w))
         if style is not None:            # None: the targets come from the sharded style pass (shard_style, after comm_init_*)
@@ -94,61 +83,52 @@ class HipTileBackend:
         recvs = [(peer, float32 array to fill)].  The engine calls them from st_tile_step with its stream drained."""
         device = self.device
 
-        def on_allreduce(_user, ptr, n):
-            try:
-                t = dev_tensor(ptr, (n,), device)
-                h = t.cpu().numpy()
-                allreduce(h)
-                t.copy_(torch.from_numpy(h))
-                torch.cuda.synchronize(device)
-                return 0
-            except Exception:               # noqa: BLE001 (reported through the status code)
-                import traceback
-                traceback.print_exc()
-                return 1
+        def on_allreduce(ptr, n):
+            t = dev_tensor(ptr, (n,), device)
+            h = t.cpu().numpy()
+            allreduce(h)
+            t.copy_(torch.from_numpy(h))
+            torch.cuda.synchronize(device)
 
-        def on_exchange(_user, ns, speer, sbuf, scount, nr, rpeer, rbuf, rcount):
-            try:
-                sends = [(int(speer[i]), dev_tensor(sbuf[i], (scount[i],), device).cpu().numpy()) for i in range(ns)]
-                recvs = [(int(rpeer[j]), np.empty(rcount[j], F32)) for j in range(nr)]
-                exchange(sends, recvs)
-                for j, (_, h) in enumerate(recvs):
-                    dev_tensor(rbuf[j], (rcount[j],), device).copy_(torch.from_numpy(h))
-                torch.cuda.synchronize(device)
-                return 0
-            except Exception:               # noqa: BLE001
-                import traceback
-                traceback.print_exc()
-                return 1
-        self._callbacks = (capi.ALLREDUCE_FN(on_allreduce), capi.EXCHANGE_FN(on_exchange))       # keep the thunks alive
-        check(self.lib.st_comm_callbacks(self.ctx, int(rank), int(world), self._callbacks[0], self._callbacks[1], None))
+        def on_exchange(ns, speer, sbuf, scount, nr, rpeer, rbuf, rcount):
+            sends = [(int(speer[i]), dev_tensor(sbuf[i], (scount[i],), device).cpu().numpy()) for i in range(ns)]
+            recvs = [(int(rpeer[j]), np.empty(rcount[j], F32)) for j in range(nr)]
+            exchange(sends, recvs)
+            for j, (_, h) in enumerate(recvs):
+                dev_tensor(rbuf[j], (rcount[j],), device).copy_(torch.from_numpy(h))
+            torch.cuda.synchronize(device)
+        self._install_callbacks(rank, world, on_allreduce, on_exchange)
 
     def comm_init_local(self, rank, world, fabric):
         """Ranks that are threads of this process on this GPU (tiled.InProcessFabric): the engine's all-reduces and strip exchanges
         become device-to-device copies between the contexts' buffers -- no host staging."""
         device = self.device
 
-        def on_allreduce(_user, ptr, n):
-            try:
-                fabric.allreduce(rank, dev_tensor(ptr, (n,), device))
-                torch.cuda.synchronize(device)
-                return 0
-            except Exception:               # noqa: BLE001
-                import traceback
-                traceback.print_exc()
-                return 1
+        def on_allreduce(ptr, n):
+            fabric.allreduce(rank, dev_tensor(ptr, (n,), device))
+            torch.cuda.synchronize(device)
 
-        def on_exchange(_user, ns, speer, sbuf, scount, nr, rpeer, rbuf, rcount):
-            try:
-                sends = [(int(speer[i]), dev_tensor(sbuf[i], (scount[i],), device)) for i in range(ns)]
-                recvs = [(int(rpeer[j]), dev_tensor(rbuf[j], (rcount[j],), device)) for j in range(nr)]
-                fabric.exchange(rank, sends, recvs)
-                return 0
-            except Exception:               # noqa: BLE001
-                import traceback
-                traceback.print_exc()
-                return 1
-        self._callbacks = (capi.ALLREDUCE_FN(on_allreduce), capi.EXCHANGE_FN(on_exchange))       # keep the thunks alive
+        def on_exchange(ns, speer, sbuf, scount, nr, rpeer, rbuf, rcount):
+            sends = [(int(speer[i]), dev_tensor(sbuf[i], (scount[i],), device)) for i in range(ns)]
+            recvs = [(int(rpeer[j]), dev_tensor(rbuf[j], (rcount[j],), device)) for j in range(nr)]
+            fabric.exchange(rank, sends, recvs)
+        self._install_callbacks(rank, world, on_allreduce, on_exchange)
+
+    def _install_callbacks(self, rank, world, on_allreduce, on_exchange):
+        """The transport st_tile_step calls with its stream drained: on_allreduce(ptr, n) sums n floats at the device pointer over the
+        ranks in place; on_exchange(n_send, peers, buffers, counts, n_recv, peers, buffers, counts) delivers the packed strips.  An
+        exception in either is printed and reported to the engine through the status code."""
+        def guarded(body):
+            def thunk(_user, *args):
+                try:
+                    body(*args)
+                    return 0
+                except Exception:           # noqa: BLE001 (reported through the status code)
+                    import traceback
+                    traceback.print_exc()
+                    return 1
+            return thunk
+        self._callbacks = (capi.ALLREDUCE_FN(guarded(on_allreduce)), capi.EXCHANGE_FN(guarded(on_exchange)))     # keep the thunks alive
         check(self.lib.st_comm_callbacks(self.ctx, int(rank), int(world), self._callbacks[0], self._callbacks[1], None))
 
     def comm_init_callbacks(self, dist, rank, world):
@@ -169,8 +149,7 @@ class HipTileBackend:
         """ONE rank of a larger grid alone on a GPU (timing the per-rank compute of a multi-GPU run): the all-reduces see one rank,
         what the neighbours would send never arrives -- the receive buffers hold the zeros st_tile_plan initialised them with, so the
         timed update runs on finite data."""
-        self._callbacks = (capi.ALLREDUCE_FN(lambda user, ptr, n: 0), capi.EXCHANGE_FN(lambda *a: 0))
-        check(self.lib.st_comm_callbacks(self.ctx, int(rank), int(world), self._callbacks[0], self._callbacks[1], None))
+        self._install_callbacks(rank, world, lambda ptr, n: None, lambda *a: None)
 
     # ---- the style targets from the sharded style image (st_tile_set_style; tiling.style_grid) ---------------------------------
     def _style_share(self, style, style_grid):
@@ -231,11 +210,18 @@ class HipTileBackend:
     def barrier(self):
         check(self.lib.st_comm_barrier(self.ctx))
 
-    def tile_image(self):
-        t = self.grid.tiles[self.rank]
-        out = np.empty((t.y1 - t.y0, t.x1 - t.x0, 3), F32)
-        check(self.lib.st_tile_get_tile(self.ctx, out.ctypes.data_as(c_void_p)))
+    def _tile_rect(self):
+        """[(y0, x0, h, w)] of this rank's tile in its window: a rectangle list for strips()."""
+        return [local_rect(self.grid.tiles[self.rank], self.grid.windows[self.rank])]
+
+    def _read_tile(self, entry):
+        _, _, th, tw = self._tile_rect()[0]
+        out = np.empty((th, tw, 3), F32)
+        check(entry(self.ctx, out.ctypes.data_as(c_void_p)))
         return out
+
+    def tile_image(self):
+        return self._read_tile(self.lib.st_tile_get_tile)
 
     def averaging(self):
         """True once the engine holds a running mean of this window's iterates (the mode is on and a fused step has run)."""
@@ -245,10 +231,7 @@ class HipTileBackend:
     def averaged_image(self):
         """This rank's tile of the corrected, deprocessed iterate average (st_tile_get_tile_average): an error while the mode is off or
         no fused step has run since the mean was cleared."""
-        t = self.grid.tiles[self.rank]
-        out = np.empty((t.y1 - t.y0, t.x1 - t.x0, 3), F32)
-        check(self.lib.st_tile_get_tile_average(self.ctx, out.ctypes.data_as(c_void_p)))
-        return out
+        return self._read_tile(self.lib.st_tile_get_tile_average)
 
     def _buf(self, which, shape):
         p = c_void_p()
@@ -303,34 +286,27 @@ class HipTileBackend:
         check(self.lib.st_tile_backward(self.ctx, byref(p)))
         return dev_tensor(p.value, (3, self.wh, self.ww), self.device)
 
-    def update(self, ring):
+    def _image_pass(self, entry, ring):
         ring = ring.contiguous()
         torch.cuda.synchronize(self.device)
         self._ring = ring                                    # keep alive until the kernel has run
         p, n = c_void_p(), c_int()
-        check(self.lib.st_tile_update(self.ctx, c_void_p(ring.data_ptr()), byref(p), byref(n)))
+        check(entry(self.ctx, c_void_p(ring.data_ptr()), byref(p), byref(n)))
         self.p3 = dev_tensor(p.value, (n.value,), self.device)
         return self.p3
 
-    # ---- L-BFGS pieces (tiled.TiledTransfer, optimizer='lbfgs'): vectors are compact (3, th, tw) tile tensors ----------------
-    def _tile_rect(self):
-        t, w = self.grid.tiles[self.rank], self.grid.windows[self.rank]
-        return [(t.y0 - w.y0, t.x0 - w.x0, t.y1 - t.y0, t.x1 - t.x0)]
+    def update(self, ring):
+        return self._image_pass(self.lib.st_tile_update, ring)
 
     def gradient(self, ring):
         """The image-space pass without an optimizer (st_tile_gradient): partial sums as update() returns them; the combined
         gradient of the tile is then available from grad_tile()."""
-        ring = ring.contiguous()
-        torch.cuda.synchronize(self.device)
-        self._ring = ring
-        p, n = c_void_p(), c_int()
-        check(self.lib.st_tile_gradient(self.ctx, c_void_p(ring.data_ptr()), byref(p), byref(n)))
-        self.p3 = dev_tensor(p.value, (n.value,), self.device)
-        return self.p3
+        return self._image_pass(self.lib.st_tile_gradient, ring)
 
+    # ---- L-BFGS pieces (tiled.TiledTransfer, optimizer='lbfgs'): vectors are compact (3, th, tw) tile tensors ----------------
     def vnew(self):
-        t = self.grid.tiles[self.rank]
-        return torch.empty((3, t.y1 - t.y0, t.x1 - t.x0), dtype=torch.float32, device=self.device)
+        _, _, th, tw = self._tile_rect()[0]
+        return torch.empty((3, th, tw), dtype=torch.float32, device=self.device)
 
     def grad_tile(self):
         out = self.vnew()

@@ -15,15 +15,20 @@ of each phase is delegated to a tile backend:
 
 The HIP backend (``HipTileBackend``) keeps every tensor on the GPU; tests run the same driver over a numpy
 backend built on the CPU oracle.
+
+One plan, one evaluation.  ``fused_plans(grid, rank)`` is the only translation of the grid's three exchanges (overlap-add, ring,
+apron refresh) into per-peer rectangle lists: ``TiledTransfer`` executes them through ``_exchange``, ``FusedTiledTransfer`` hands the
+same lists to ``st_tile_plan``.  ``TiledTransfer._evaluate`` is the only statement of the phase sequence of an evaluation; Adam and
+L-BFGS differ in the image pass it ends with (engine_comm.cpp: tile_evaluate).
 """
 
 import numpy as np
 
-from .tiling import Rect
-
 
 class _LazyTorch:
-    """Only the phase-by-phase driver (TiledTransfer / Comm) uses torch; FusedTiledTransfer (st_tile_step over RCCL) does not."""
+    """torch is needed only by the phase-by-phase driver (TiledTransfer / Comm, HipTileBackend's phases: device buffers handed to
+    torch.distributed) and by the host-staged test transport.  The in-engine iteration (FusedTiledTransfer, st_tile_step over RCCL)
+    never imports it: one HIP runtime in the process."""
     def __getattr__(self, name):
         import torch as _torch
         return getattr(_torch, name)
@@ -77,6 +82,11 @@ def _local(rect, origin):
     return slice(rect.y0 - origin.y0, rect.y1 - origin.y0), slice(rect.x0 - origin.x0, rect.x1 - origin.x0)
 
 
+def local_rect(rect, origin):
+    """(y0, x0, h, w) of `rect` in the coordinates of the tensor that starts at `origin`: the form of every planned rectangle."""
+    return (rect.y0 - origin.y0, rect.x0 - origin.x0, rect.y1 - rect.y0, rect.x1 - rect.x0)
+
+
 class TiledTransfer:
     """optimizer='adam': the backend's fused image pass + Adam update (one evaluation per step).
     optimizer='lbfgs': LBFGSOptimizer (optimizers.py:49-125) over the tile-sharded image: every rank keeps its tile of x, of the
@@ -95,13 +105,12 @@ class TiledTransfer:
         self.sk, self.yk, self.syk = [], [], []
         self.lb_grad = None
         self.t = 0
-        self._refresh = grid.apron_refresh_plan()
-        self._overlap = grid.grad_overlap_plan()
-        self._ring = grid.ring_plan()
+        self.plans = fused_plans(grid, rank)
 
     # -- communication phases ------------------------------------------------------------------------------
-    # Everything one neighbour gets in a phase travels as ONE message: its rectangles are packed into a contiguous buffer
-    # (one kernel per neighbour on the HIP backend, `backend.strips`) and unpacked the same way on the other side.
+    # The three exchanges are self.plans, the lists st_tile_plan gets from FusedTiledTransfer.  Everything one neighbour gets in a phase
+    # travels as ONE message: its rectangles are packed into a contiguous buffer (one kernel per neighbour on the HIP backend,
+    # `backend.strips`) and unpacked the same way on the other side.
     MAX_RECTS = 12                              # st2_kernels.h kMaxStripRects
 
     def _pack(self, t, rects):
@@ -126,56 +135,34 @@ class TiledTransfer:
                 t[:, y:y + h, x:x + w] = piece
             pos += n
 
-    def _exchange(self, src, send_rects, dst, recv_rects, add):
-        """send_rects / recv_rects: {peer: [(y0, x0, h, w), ...]} in plan order (local coordinates of src / dst)."""
-        sends = [(peer, self._pack(src, rects)) for peer, rects in sorted(send_rects.items())]
-        recvs = [(peer, torch.empty(sum(dst.shape[0] * r[2] * r[3] for r in rects), dtype=dst.dtype, device=dst.device))
-                 for peer, rects in sorted(recv_rects.items())]
-        self.comm.exchange(sends, recvs)
-        for (peer, buf) in recvs:                   # ascending peer, plan order inside: deterministic sums
-            self._unpack(dst, recv_rects[peer], buf, add)
-
-    @staticmethod
-    def _lrect(rect, origin):
-        return (rect.y0 - origin.y0, rect.x0 - origin.x0, rect.y1 - rect.y0, rect.x1 - rect.x0)
+    def _exchange(self, phase, src, dst, add):
+        """One exchange of self.plans, as comm_exchange (engine_comm.cpp) runs it: pack what each peer gets out of `src`, one message
+        per peer; a peer == rank entry (the periodic wrap lands on this rank's own tile) is unpacked locally and never reaches
+        Comm.exchange; unpack (assign / add) into `dst`."""
+        plan = sorted(self.plans[phase].items())
+        sends = [(peer, self._pack(src, send)) for peer, (send, _) in plan if send]
+        for peer, buf in sends:
+            if peer == self.rank:
+                self._unpack(dst, self.plans[phase][peer][1], buf, add)
+        recvs = [(peer, torch.empty(sum(dst.shape[0] * r[2] * r[3] for r in recv), dtype=dst.dtype, device=dst.device))
+                 for peer, (_, recv) in plan if recv and peer != self.rank]
+        self.comm.exchange([m for m in sends if m[0] != self.rank], recvs)
+        for peer, buf in recvs:                     # ascending peer, plan order inside: deterministic sums
+            self._unpack(dst, self.plans[phase][peer][1], buf, add)
 
     def refresh_aprons(self, x):
         """x: (3, wh, ww) window tensor whose TILE part is current: fill the apron from the owners."""
-        sends, recvs = {}, {}
-        for src, dst, rect in self._refresh:
-            if src == self.rank:
-                sends.setdefault(dst, []).append(self._lrect(rect, self.window))
-            elif dst == self.rank:
-                recvs.setdefault(src, []).append(self._lrect(rect, self.window))
-        self._exchange(x, sends, x, recvs, add=False)
+        self._exchange(PLAN_REFRESH, x, x, add=False)
 
     def overlap_add(self, g):
         """g: (3, wh, ww) window gradient: add the neighbours' contributions to MY tile pixels."""
-        sends, recvs = {}, {}
-        for src, dst, rect in self._overlap:
-            if src == self.rank:
-                sends.setdefault(dst, []).append(self._lrect(rect, self.window))
-            elif dst == self.rank:
-                recvs.setdefault(src, []).append(self._lrect(rect, self.window))
-        self._exchange(g, sends, g, recvs, add=True)
+        self._exchange(PLAN_OVERLAP, g, g, add=True)
 
     def gather_ring(self, x):
         """(3, th+2, tw+2) tensor: the tile's 1-px neighbourhood under the image's periodic wrap."""
         th, tw = self.tile.y1 - self.tile.y0, self.tile.x1 - self.tile.x0
         ring = torch.zeros((3, th + 2, tw + 2), dtype=x.dtype, device=x.device)
-        sends, recvs = {}, {}
-        for dst, items in enumerate(self._ring):
-            for src, rect, ry, rx in items:
-                h, w = rect.y1 - rect.y0, rect.x1 - rect.x0
-                if src == self.rank:
-                    ys, xs = _local(rect, self.window)      # my own tile pixels, in my window
-                    if dst == self.rank:
-                        ring[:, ry:ry + h, rx:rx + w] = x[:, ys, xs]
-                    else:
-                        sends.setdefault(dst, []).append(self._lrect(rect, self.window))
-                elif dst == self.rank:
-                    recvs.setdefault(src, []).append((ry, rx, h, w))
-        self._exchange(x, sends, ring, recvs, add=False)
+        self._exchange(PLAN_RING, x, ring, add=False)
         return ring
 
     # -- the style targets from the sharded style image ---------------------------------------------------------
@@ -186,9 +173,11 @@ class TiledTransfer:
         self.comm.all_reduce(self.backend.style_partials(style, style_grid))
         self.backend.style_commit()
 
-    # -- L-BFGS over the sharded image ----------------------------------------------------------------------
-    def _evaluate(self):
-        """opfunc at the current image: the trace values; the backend's grad_tile() then holds this rank's part of the gradient."""
+    # -- one evaluation ---------------------------------------------------------------------------------------
+    def _evaluate(self, adam=False):
+        """The phases of one evaluation at the current image, the only place that states them; returns the trace values.  The image pass
+        is opfunc's (the backend's grad_tile() then holds this rank's part of the gradient) or, adam=True, the one fused with Adam's
+        update into x_next."""
         b = self.backend
         self.comm.all_reduce(b.forward_partials())
         extra = b.losses_need_style_norm()
@@ -198,9 +187,10 @@ class TiledTransfer:
         g = b.backward()
         self.overlap_add(g)
         ring = self.gather_ring(b.x_cur())
-        self.comm.all_reduce(b.gradient(ring))
+        self.comm.all_reduce(b.update(ring) if adam else b.gradient(ring))
         return b.finish_trace()
 
+    # -- L-BFGS over the sharded image ----------------------------------------------------------------------
     def _dot(self, a, c):
         """utils.dot over the whole image: partial sums of the ranks, all-reduced.  Returned as a python float holding the
         float32 sum, as scipy's sdot returns it (utils.py:29-36): the scalar arithmetic below is then done in double and rounded
@@ -256,16 +246,8 @@ class TiledTransfer:
         self.t += 1
         if self.optimizer == 'lbfgs':
             return self._lbfgs_step()
-        self.comm.all_reduce(b.forward_partials())
-        extra = b.losses_need_style_norm()
-        if extra is not None:
-            self.comm.all_reduce(extra)
-        b.finish_losses()
-        g = b.backward()
-        self.overlap_add(g)
-        ring = self.gather_ring(b.x_cur())
-        self.comm.all_reduce(b.update(ring))
-        values = b.finish_trace()
+        # (this class's own: a subclass that overrides _evaluate() wraps opfunc, the evaluation L-BFGS asks for, not Adam's update)
+        values = TiledTransfer._evaluate(self, adam=True)
         self.refresh_aprons(b.x_next())
         b.swap()
         return values
@@ -282,25 +264,22 @@ PLAN_OVERLAP, PLAN_RING, PLAN_REFRESH = 0, 1, 2          # st2.h ST_TILE_PLAN_*
 
 
 def fused_plans(grid, rank):
-    """The three strip exchanges of one iteration as st_tile_plan wants them: {phase: {peer: (send rects, recv rects)}}, rects
-    (y0, x0, h, w) in the coordinates of the tensor packed (the window) / unpacked into (the window; the ring for PLAN_RING).
-    Same plans, same order, as TiledTransfer.overlap_add / gather_ring / refresh_aprons build per step."""
-    window, tile = grid.windows[rank], grid.tiles[rank]
-
-    def lrect(rect, origin):
-        return (rect.y0 - origin.y0, rect.x0 - origin.x0, rect.y1 - rect.y0, rect.x1 - rect.x0)
+    """The three strip exchanges of one iteration, the only translation of TileGrid's plans into rectangle lists -- what
+    TiledTransfer._exchange executes and st_tile_plan is handed: {phase: {peer: (send rects, recv rects)}}, rects (y0, x0, h, w) in the
+    coordinates of the tensor packed (the window) / unpacked into (the window; the ring for PLAN_RING)."""
+    window = grid.windows[rank]
     plans = {PLAN_OVERLAP: {}, PLAN_RING: {}, PLAN_REFRESH: {}}
     for phase, plan in ((PLAN_OVERLAP, grid.grad_overlap_plan()), (PLAN_REFRESH, grid.apron_refresh_plan())):
         for src, dst, rect in plan:
             if src == rank:
-                plans[phase].setdefault(dst, ([], []))[0].append(lrect(rect, window))
+                plans[phase].setdefault(dst, ([], []))[0].append(local_rect(rect, window))
             elif dst == rank:
-                plans[phase].setdefault(src, ([], []))[1].append(lrect(rect, window))
+                plans[phase].setdefault(src, ([], []))[1].append(local_rect(rect, window))
     for dst, items in enumerate(grid.ring_plan()):
         for src, rect, ry, rx in items:
             h, w = rect.y1 - rect.y0, rect.x1 - rect.x0
             if src == rank:
-                plans[PLAN_RING].setdefault(dst, ([], []))[0].append(lrect(rect, window))
+                plans[PLAN_RING].setdefault(dst, ([], []))[0].append(local_rect(rect, window))
                 if dst == rank:                                     # the periodic wrap lands on this rank's own tile: a local copy
                     plans[PLAN_RING][dst][1].append((ry, rx, h, w))
             elif dst == rank:
@@ -455,25 +434,28 @@ class LocalComm:
             self.fabric.exchange(self.rank, list(sends), list(recvs))
 
 
-def run_in_process(ranks, steps, fabric, on_step=None):
-    """`steps` iterations of every FusedTiledTransfer in `ranks`, one thread per rank.  Returns, per rank, the trace values of every step
-    (on_step(rank, step, transfer, values) may collect more, e.g. the tile image).  A rank that raises aborts the fabric, so the others
-    leave their waits at once; if a rank thread is nevertheless still running when this returns (it sits inside the engine), the
-    RuntimeError carries ``still_running = True`` and the caller must NOT free the engine contexts."""
+def _run_ranks(bodies, fabric, in_turns=False):
+    """bodies[r]() on one thread per rank; returns what they returned.  A rank that raises aborts the fabric, so the others leave their
+    waits at once (a fabric without abort(): its barrier); ranks still running after the first bounded join are aborted and joined once
+    more.  If a rank thread is nevertheless still running when this returns (it sits inside the engine), the RuntimeError carries
+    ``still_running = True`` and the caller must NOT free the engine contexts.  in_turns: a rank starts when the one before it has
+    reached its all-reduce (InProcessFabric.take_turn)."""
     import threading
-    world = len(ranks)
-    out, errors = [None] * world, []
+    world = len(bodies)
+    out, done, errors = [None] * world, [False] * world, []
 
     def run(r):
         try:
-            res = []
-            for k in range(steps):
-                vals = ranks[r].step()
-                res.append(on_step(r, k, ranks[r], vals) if on_step else vals)
-            out[r] = res
+            if in_turns:
+                fabric.take_turn(r)
+            out[r] = bodies[r]()
+            done[r] = True
         except Exception as e:          # noqa: BLE001
             errors.append((r, repr(e)))
             fabric.abort() if hasattr(fabric, 'abort') else fabric.barrier.abort()
+        finally:
+            if in_turns:
+                fabric.end_turn(r)
     threads = [threading.Thread(target=run, args=(r,), daemon=True) for r in range(world)]
     for t in threads:
         t.start()
@@ -485,50 +467,31 @@ def run_in_process(ranks, steps, fabric, on_step=None):
         for t in threads:
             t.join(30.0)
         alive = [r for r, t in enumerate(threads) if t.is_alive()]
-    if errors or alive or any(o is None for o in out):
-        err = RuntimeError('in-process ranks failed: %s' % (errors or ('rank(s) %s did not finish' % alive)))
-        err.still_running = bool(alive)
-        raise err
-    return out
-
-
-def run_collective(calls, fabric, in_turns=False):
-    """One collective call per rank (calls[r]: a callable that ends in the fabric, e.g. HipTileBackend.shard_style), one thread each, as
-    run_in_process runs the iterations: a rank that raises aborts the fabric; ``still_running`` on the RuntimeError means a rank thread
-    is still inside the engine and the caller must NOT free the engine contexts.  in_turns: a rank starts when the one before it has
-    reached its all-reduce (InProcessFabric.take_turn).  Returns what the calls returned."""
-    import threading
-    world = len(calls)
-    out, done, errors = [None] * world, [False] * world, []
-
-    def run(r):
-        try:
-            if in_turns:
-                fabric.take_turn(r)
-            out[r] = calls[r]()
-            done[r] = True
-        except Exception as e:          # noqa: BLE001
-            errors.append((r, repr(e)))
-            fabric.abort()
-        finally:
-            if in_turns:
-                fabric.end_turn(r)
-    threads = [threading.Thread(target=run, args=(r,), daemon=True) for r in range(world)]
-    for t in threads:
-        t.start()
-    for t in threads:
-        t.join(max(300.0, 4 * fabric.timeout))
-    alive = [r for r, t in enumerate(threads) if t.is_alive()]
-    if alive:
-        fabric.abort()
-        for t in threads:
-            t.join(30.0)
-        alive = [r for r, t in enumerate(threads) if t.is_alive()]
     if errors or alive or not all(done):
         err = RuntimeError('in-process ranks failed: %s' % (errors or ('rank(s) %s did not finish' % alive)))
         err.still_running = bool(alive)
         raise err
     return out
+
+
+def run_in_process(ranks, steps, fabric, on_step=None):
+    """`steps` iterations of every transfer in `ranks` (FusedTiledTransfer or TiledTransfer), one thread per rank (_run_ranks has the
+    failure rules).  Returns, per rank, the trace values of every step (on_step(rank, step, transfer, values) may collect more, e.g.
+    the tile image)."""
+    def iterate(r):
+        res = []
+        for k in range(steps):
+            vals = ranks[r].step()
+            res.append(on_step(r, k, ranks[r], vals) if on_step else vals)
+        return res
+    return _run_ranks([lambda r=r: iterate(r) for r in range(len(ranks))], fabric)
+
+
+def run_collective(calls, fabric, in_turns=False):
+    """One collective call per rank (calls[r]: a callable that ends in the fabric, e.g. HipTileBackend.shard_style), one thread each, as
+    run_in_process runs the iterations and with the same failure rules.  in_turns: a rank starts when the one before it has reached its
+    all-reduce.  Returns what the calls returned."""
+    return _run_ranks(calls, fabric, in_turns)
 
 
 def rendezvous_unique_id(rank, world, make_id, addr=None, port=None, timeout=None):

@@ -342,29 +342,14 @@ def recut(plans, halves=False):
 
 
 def recut_driver(tt, halves=False):
-    """The same for the plan lists of a tiled.TiledTransfer (global rectangles)."""
-    def rows(r):
-        return [(i, px - r.x0, tiling.Rect(r.y0 + i, px, r.y0 + i + 1, px + pw))
-                for i in range(r.y1 - r.y0) for px, pw in _pieces(r.x0, r.x1 - r.x0, halves)]
-    tt._overlap = [(s, d, q) for s, d, r in tt._overlap for _, _, q in rows(r)]
-    tt._refresh = [(s, d, q) for s, d, r in tt._refresh for _, _, q in rows(r)]
-    tt._ring = [[(s, q, ry + dy, rx + dx) for s, r, ry, rx in items for dy, dx, q in rows(r)] for items in tt._ring]
+    """The same for a tiled.TiledTransfer: it executes the plans it holds."""
+    tt.plans = recut(tt.plans, halves)
 
 
 def driver_rects_per_peer(tt):
-    """Largest number of rectangles this rank of a tiled.TiledTransfer receives from one peer in one phase."""
-    most = 0
-    for plan in (tt._overlap, tt._refresh):
-        counts = {}
-        for src, dst, _ in plan:
-            if dst == tt.rank:
-                counts[src] = counts.get(src, 0) + 1
-        most = max([most] + list(counts.values()))
-    counts = {}
-    for src, _, _, _ in tt._ring[tt.rank]:
-        if src != tt.rank:
-            counts[src] = counts.get(src, 0) + 1
-    return max([most] + list(counts.values()))
+    """Largest number of rectangles this rank of a tiled.TiledTransfer receives from one peer (not itself) in one phase."""
+    return max_rects_per_peer({phase: {peer: ([], recv) for peer, (_, recv) in peers.items() if peer != tt.rank}
+                               for phase, peers in tt.plans.items()})
 
 
 def max_rects_per_peer(plans):

@@ -68,23 +68,21 @@ def test_bf16_oracle_tiles_round_partial_diffs_in_the_seam_band(case_id):
 # Each defect changes CPU objects of the phase driver only (its plan lists, its unpack, the grid's region of interest).  `ranks` are the
 # RecordingTransfers of one run, before they start.
 def _shift_one_overlap_receive(ranks):
-    """One overlap receive rectangle of one rank lands one column off (the sender packs what it always packed)."""
+    """One overlap receive rectangle of one rank (the first the grid plans for it) lands one column off (the sender packs what it always
+    packed)."""
     tt = ranks[-1]
-    for i, (src, dst, r) in enumerate(tt._overlap):
-        if dst == tt.rank:
-            dx = 1 if r.x1 + 1 <= tt.window.x1 else -1
-            tt._overlap[i] = (src, dst, tiling.Rect(r.y0, r.x0 + dx, r.y1, r.x1 + dx))
-            return
-    raise AssertionError('no overlap receive on rank %d' % tt.rank)
+    src = next(s for s, d, _ in tt.grid.grad_overlap_plan() if d == tt.rank)
+    recv = tt.plans[tiled.PLAN_OVERLAP][src][1]
+    y, x, h, w = recv[0]
+    recv[0] = (y, x + (1 if x + w + 1 <= tt.window.x1 - tt.window.x0 else -1), h, w)
 
 
 def _drop_the_corner_rectangle(ranks):
     """2 x 2: what the diagonal neighbour owes rank 0 (the four-corner rectangle) is in nobody's plan."""
     assert len(ranks) == 4
-    for tt in ranks:
-        n = len(tt._overlap)
-        tt._overlap = [e for e in tt._overlap if (e[0], e[1]) != (3, 0)]
-        assert len(tt._overlap) == n - 1
+    send, recv = ranks[3].plans[tiled.PLAN_OVERLAP][0][0], ranks[0].plans[tiled.PLAN_OVERLAP][3][1]
+    assert len(send) == 1 and len(recv) == 1
+    del send[0], recv[0]
 
 
 def _assign_in_place_of_add(ranks):
@@ -96,26 +94,28 @@ def _assign_in_place_of_add(ranks):
 def _ring_item_one_cell_off(ranks):
     """One received ring column of one rank lands one cell to the right."""
     tt = ranks[0]
-    items = tt._ring[tt.rank]
-    for i, (src, r, ry, rx) in enumerate(items):
+    for src, r, ry, rx in tt.grid.ring_plan()[tt.rank]:         # (the first such item the grid plans: a column, before the corners)
         if src != tt.rank and r.x1 - r.x0 == 1 and rx == 0:
-            items[i] = (src, r, ry, rx + 1)
+            recv = tt.plans[tiled.PLAN_RING][src][1]
+            i = recv.index((ry, rx, r.y1 - r.y0, 1))
+            recv[i] = (ry, rx + 1, r.y1 - r.y0, 1)
             return
     raise AssertionError('rank 0 receives no left ring column')
 
 
 def _top_ring_row_from_the_unwrapped_neighbour(ranks):
     """The top ring row of the top tiles comes from the near side of its source rank (that rank's first row: where the neighbour would be
-    without the wrap) instead of the image's last row."""
+    without the wrap) instead of the image's last row.  (Tiles are more than one row high: a one-row rectangle sent from the image's last
+    row is a top ring row or one of its corners.)"""
     grid, hit = ranks[0].grid, 0
     for tt in ranks:
-        for dst, items in enumerate(tt._ring):
+        last = grid.gH - 1 - tt.window.y0
+        for dst, (send, _) in tt.plans[tiled.PLAN_RING].items():
             if grid.tiles[dst].y0 != 0:
                 continue
-            for i, (src, r, ry, rx) in enumerate(items):
-                if ry == 0 and r.y0 == grid.gH - 1:
-                    y = grid.tiles[src].y0
-                    items[i] = (src, tiling.Rect(y, r.x0, y + 1, r.x1), ry, rx)
+            for i, (y, x, h, w) in enumerate(send):
+                if y == last and h == 1:
+                    send[i] = (tt.tile.y0 - tt.window.y0, x, h, w)
                     hit += 1
     assert hit
 
@@ -133,12 +133,10 @@ def _roi_one_cell_off(ranks):
 
 
 def _drop_one_refresh_rectangle(ranks):
-    src, dst, _ = ranks[0]._refresh[0]
-    for tt in ranks:
-        n = len(tt._refresh)
-        first = next(i for i, e in enumerate(tt._refresh) if (e[0], e[1]) == (src, dst))
-        del tt._refresh[first]
-        assert len(tt._refresh) == n - 1
+    src, dst, _ = ranks[0].grid.apron_refresh_plan()[0]
+    send, recv = ranks[src].plans[tiled.PLAN_REFRESH][dst][0], ranks[dst].plans[tiled.PLAN_REFRESH][src][1]
+    assert send and len(send) == len(recv)
+    del send[0], recv[0]
 
 
 # (defect, the cases it is tried on): the largest figure over those cases counts
@@ -226,7 +224,7 @@ def test_rectangle_counts_of_the_case_table_are_the_recorded_ones():
 @pytest.mark.parametrize('case_id', ['T2-2x2-37x50-std', 'T2-3x3-36x44-std', 'T2-1x2-16x24-std', 'T4-2x2-37x50-std'])
 def test_recut_plans_move_the_same_pixels_bit_for_bit(case_id):
     """A rectangle-list property: plans cut into single-row rectangles give the same windows, rings and sums -- played on arrays for
-    tiled.fused_plans, and through the CPU driver for its own plan lists."""
+    tiled.fused_plans, and through the CPU driver, which executes the same lists."""
     c = so.case(case_id)
     grid = so.grid_of(c)
     rng = np.random.RandomState(5)
