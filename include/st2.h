@@ -187,6 +187,53 @@ int st_set_iterate_average(st_ctx* ctx, double decay);
 /* the decay in force (0: off), the item count, and the RAW, uncorrected mean (3,H,W) of the context's image (tile-sharded: the window).
  * Any pointer may be NULL; mean_nchw with items == 0 is ST_ERR_STATE. */
 int st_get_iterate_average(st_ctx* ctx, double* decay, int* items, float* mean_nchw);
+/* ---- the content's colours (Gatys et al., "Preserving Color in Neural Artistic Style Transfer"; no reference counterpart) ---------
+ * Two independent modes, both off by default: off, every launch, result and message is what it is without them.  Throughout, x, cx and
+ * s are preprocessed planar images (mean-subtracted RGB, no channel flip, as st_set_input leaves them) and kMean is the channel mean of
+ * worker.py:34; fp32 arithmetic rounds once per operation (no FMA).
+ * Luminance-only output: the image handed out takes its luminance from the iterate and its chroma from the content image.  Per pixel,
+ * with v the iterate x (under st_set_iterate_average: v_c = mean_c / corr, the division of the averaged image):
+ *   d_c = v_c - cx_c;   l = (0.299f * d_R + 0.587f * d_G) + 0.114f * d_B;   out_c = (cx_c + kMean_c) + l
+ * -- "Y of the iterate, chroma of the content" in any luma / colour-difference space with Rec.601 luma (the luma column of the inverse
+ * transform is (1, 1, 1)).  One launch in place of the deprocess / averaging pass, one more read stream.  The optimisation, the iterate,
+ * its running mean, st_get_input_nchw and st_get_iterate_average are untouched: only the images of st_step, st_step_end,
+ * st_tile_get_tile and st_tile_get_tile_average change (tile-sharded: the chroma of the window's own content).  While the mode is on,
+ * st_step with an image wanted, st_step_begin, st_tile_get_tile and st_tile_get_tile_average return ST_ERR_STATE without a content
+ * image or with one of another size than the input, before anything is enqueued.  ST_ERR_STATE while a pipelined iteration is in flight. */
+int st_set_original_colors(st_ctx* ctx, int on);
+/* Colour mean (image scale, 0..255) and population covariance (upper triangle: RR, RG, RB, GG, GB, BB) of an image, taken as st_set_style
+ * would preprocess it: the nine sums of p_c and p_c p_k (c <= k) over the preprocessed values on the device, every product and addition
+ * in double, per thread, per workgroup and in a second stage that adds the workgroups' partial sums in a fixed order (no atomics: the
+ * same image gives the same bits); then in double on the host mean = sum / N + kMean, cov = sum_ck / N - (sum_c / N)(sum_k / N). */
+int st_image_moments(st_ctx* ctx, const void* hwc, int H, int W, int is_u8, double mean[3], double cov[6]);
+/* The ridge of the colour-matching transform, in this value scale (what linear colour transfer implementations add to both covariances). */
+#define ST_COLOR_RIDGE (1e-5 * 255.0 * 255.0)
+/* Linear colour transfer: the affine map s' = A s + b (preprocessed coordinates, A row-major) that gives the style image's pixels the
+ * content image's colour mean and covariance.  With cov + ST_COLOR_RIDGE I = L L^T (Cholesky):  A = L_c L_s^-1 (a triangular solve, no
+ * general inverse),  b = (mean_c - kMean) - A (mean_s - kMean); all of it 3 x 3 closed form in double, A and b rounded once to fp32.  A
+ * grey style image (rank-1 covariance) is a normal input: the ridge keeps A finite.  Host only, no context.  ST_ERR_ARG: a non-finite
+ * input, a covariance with a negative diagonal entry or, ridge added, without a Cholesky factor. */
+int st_color_transform(const double mean_c[3], const double cov_c[6], const double mean_s[3], const double cov_s[6], float A[9], float b[3]);
+/* An affine colour map for the style image: every later st_set_style, st_tile_style_partials and st_tile_set_style applies
+ *   s'_c = ((A[c][0] * s_R + A[c][1] * s_G) + A[c][2] * s_B) + b[c]       (fp32, in place on the device copy, before the forward)
+ * to the preprocessed style image (window).  The map is per pixel: a sharded style image needs nothing more than the same A, b on every
+ * rank.  Both NULL turns it off; one NULL or a non-finite entry is ST_ERR_ARG.  Turns the colour matching below off. */
+int st_set_style_transform(st_ctx* ctx, const float A[9], const float b[3]);
+/* The single-context convenience: while on, st_set_style takes the moments of the kept content image and of the style image itself,
+ * derives A, b as st_color_transform does and applies them; ST_ERR_STATE there without a content image.  The targets follow the content
+ * image of the moment the style is set: a later st_set_content leaves them as they are, as the reference keeps its `grams`.  Refused
+ * (ST_ERR_STATE) on a tile-sharded context, whose content is the window's and not the image's: derive A, b once for the whole images
+ * and hand them to every rank with st_set_style_transform.  Turning it on drops a transform given by st_set_style_transform. */
+int st_set_style_color_match(st_ctx* ctx, int on);
+/* *original_colors = 0 | 1; *style_match = 0 (off), 1 (st_set_style_color_match) or 2 (a transform given by st_set_style_transform);
+ * A, b: the transform last applied to a style image, or the one given and waiting to be (the identity and zero before either).  Any
+ * pointer may be NULL. */
+int st_get_color_modes(st_ctx* ctx, int* original_colors, int* style_match, float A[9], float b[3]);
+/* st_set_style for an already-preprocessed (1,3,H,W) image, the sibling of st_set_input_nchw / st_set_content_nchw.  No colour
+ * transform is applied: the image is what the caller gives. */
+int st_set_style_nchw(st_ctx* ctx, const float* x, int H, int W);
+/* Test hook: the preprocessed, recoloured image (3,H,W) exactly as st_set_style would forward it under the modes in force. */
+int st_style_recolor(st_ctx* ctx, const void* hwc, int H, int W, int is_u8, float* out_nchw);
 /* Steps so far that ran as a hipGraph replay.  Opt-in (environment ST2_GRAPH=1; ST2_GRAPH_MAX_PX=<edge>, default 768):
  * steady-state Adam steps are captured once per ping-pong parity and replayed, bit-identical to plain launches.  Measured
  * on MI355X it is no faster (the step is bound by the dependent kernels' execution latency), hence off by default. */

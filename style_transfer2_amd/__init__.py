@@ -10,7 +10,7 @@ HIP library or without a GPU raises ``HipUnavailable``.
 """
 
 from .capi import HipUnavailable, StError, lib_path, load_library           # noqa: F401
-from .engine import Engine, VGG19_TOPOLOGY                                   # noqa: F401
+from .engine import Engine, VGG19_TOPOLOGY, color_transform                                   # noqa: F401
 from .model import HipModel                                                  # noqa: F401
 from .device_optimizers import AdamOptimizer, LBFGSOptimizer                 # noqa: F401
 from .transfer import StyleTransfer, weight_table                            # noqa: F401

@@ -25,6 +25,7 @@ SOURCES = (
     ('gram.hip', ()),
     ('passes.hip', ('-ffp-contract=off',)),      # NumPy-like one-rounding-per-operation arithmetic
     ('lbfgs.hip', ('-ffp-contract=off',)),
+    ('color.hip', ('-ffp-contract=off',)),       # luminance emission, colour moments, recolour: the arithmetic of st2.h, one rounding per operation
     ('style16.hip', ()),
     ('gram16.hip', ()),
     ('gram_split.hip', ()),
@@ -38,8 +39,9 @@ SOURCES = (
     ('engine_resample.cpp', ('-x', 'hip')),
     ('engine_tile.cpp', ('-x', 'hip')),
     ('engine_comm.cpp', ('-x', 'hip')),
+    ('engine_color.cpp', ('-x', 'hip')),
 )
-HEADERS = ('st2_kernels.h', 'env.h', 'wave_reduce.h', 'engine.h', 'devbuf.h', os.path.join('..', '..', 'include', 'st2.h'))
+HEADERS = ('st2_kernels.h', 'env.h', 'wave_reduce.h', 'engine.h', 'devbuf.h', 'color_match.h', os.path.join('..', '..', 'include', 'st2.h'))
 
 
 def _hipcc():

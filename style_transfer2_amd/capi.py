@@ -83,7 +83,15 @@ PROTOTYPES = {
     'st_set_iterate_average': (c_int, [c_void_p, c_double]),
     'st_get_iterate_average': (c_int, [c_void_p, POINTER(c_double), POINTER(c_int), c_void_p]),
     'st_tile_get_tile_average': (c_int, [c_void_p, c_void_p]),
-    'st_graph_replays': (c_int, [c_void_p, POINTER(c_longlong)]),
+    'st_set_original_colors': (c_int, [c_void_p, c_int]),
+    'st_image_moments': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_double), POINTER(c_double)]),
+    'st_color_transform': (c_int, [POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_float), POINTER(c_float)]),
+    'st_set_style_transform': (c_int, [c_void_p, POINTER(c_float), POINTER(c_float)]),
+    'st_set_style_color_match': (c_int, [c_void_p, c_int]),
+    'st_get_color_modes': (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_float), POINTER(c_float)]),
+    'st_set_style_nchw': (c_int, [c_void_p, c_void_p, c_int, c_int]),
+    'st_style_recolor': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    'st_graph_replays':(c_int, [c_void_p, POINTER(c_longlong)]),
     'st_live_bytes': (c_int, [POINTER(c_longlong), POINTER(c_longlong)]),
     'st_lbfgs_inv_hv': (c_int, [c_void_p, c_int, POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_void_p]),
     'st_sync': (c_int, [c_void_p]),

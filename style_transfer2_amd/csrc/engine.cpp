@@ -857,14 +857,41 @@ int st_set_style(st_ctx* c, const void* hwc, int H, int W, int is_u8)
     if (c) c->epoch++;       // anything but st_step may change what a step launches: captured step graphs are stale
     if (!c) return fail(ST_ERR_ARG, "ctx is NULL");
     HIP_TRY(hipSetDevice(c->device));
+    ST_TRY(style_color_check(c));
     DevBuf<float> tmp;
     ST_TRY(tmp.alloc((size_t)3 * H * W));
+    int r = preprocess_into(c, hwc, H, W, is_u8, tmp);
+    if (r == ST_OK && c->style_match) r = style_recolor_enqueue(c, tmp, H, W);
+    if (r == ST_OK) r = style_from_device(c, tmp, H, W);
+    (void)hipStreamSynchronize(c->stream);       // (before tmp goes)
+    return r;
+}
+
+int st_set_style_nchw(st_ctx* c, const float* x, int H, int W)
+{
+    if (c) c->epoch++;       // anything but st_step may change what a step launches: captured step graphs are stale
+    if (!c || !x || H <= 0 || W <= 0) return fail(ST_ERR_ARG, "bad argument");
+    HIP_TRY(hipSetDevice(c->device));
+    DevBuf<float> tmp;
+    ST_TRY(tmp.alloc((size_t)3 * H * W));
+    int r = ST_OK;
+    if (hipMemcpy(tmp, x, (size_t)3 * H * W * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) r = fail(ST_ERR_HIP, "style upload failed");
+    if (r == ST_OK) r = style_from_device(c, tmp, H, W);
+    (void)hipStreamSynchronize(c->stream);       // (before tmp goes)
+    return r;
+}
+
+}  // extern "C"
+
+namespace st2e {
+// preprocessed style image on the device -> full forward, Gram of every blob (worker.py:211-218)
+int style_from_device(st_ctx* c, const float* tmp, int H, int W)
+{
     ActSet aux;                // (freed on return, after the synchronisation below)
     ActSet* a = &aux;
     const bool same = c->act.H == H && c->act.W == W && !c->act.data.empty();
     if (same) a = &c->act;
-    int r = preprocess_into(c, hwc, H, W, is_u8, tmp);
-    if (r == ST_OK) r = act_ensure(c, *a, H, W);
+    int r = act_ensure(c, *a, H, W);
     if (r == ST_OK) r = forward_range(c, *a, tmp, c->nb - 1);
     for (int i = 0; i < c->nb && r == ST_OK; ++i) {
         const int C = a->C[i], hw = a->h[i] * a->w[i];
@@ -876,6 +903,9 @@ int st_set_style(st_ctx* c, const void* hwc, int H, int W, int is_u8)
     if (r == ST_OK) { c->have_style = true; std::fill(c->style_valid.begin(), c->style_valid.end(), 1); }
     return r;
 }
+}  // namespace st2e
+
+extern "C" {
 
 // ---- measurement
 int st_profile_enable(st_ctx* c, int on)

@@ -263,6 +263,11 @@ struct st_ctx {
     DevBuf<float> avg;                             // the raw mean, (3, H, W); allocated while the mode is on and an input exists
     double avg_decay = 0.0;                        // 0: off
     int avg_items = 0;                             // 0: the mean is empty (the buffer's contents do not count)
+    // the content's colours (engine_color.cpp)
+    bool orig_colors = false;                      // st_set_original_colors: the images handed out take their chroma from content_x
+    int style_match = 0;                           // 0 off, 1 st_set_style_color_match (derive per style image), 2 st_set_style_transform (given)
+    float xf_A[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, xf_b[3] = {0, 0, 0};      // the style transform given, or the one last derived and applied
+    DevBuf<double> mom_part, mom_out;              // image_moments_k's per-workgroup partial sums and the nine sums
     // tile-sharded mode (BASELINE config 5): this context holds ONE window of a larger image
     struct Tile : TileGeom {
         bool on = false;
@@ -293,6 +298,7 @@ struct st_ctx {
         long long steps = 0;
         std::vector<float> h1, h2, h3, hd, hn;     // host side of a traced step (sized once: no allocation per step)
         DevBuf<float> tile_chw, tile_hwc;          // st_tile_get_tile's staging (kept across calls)
+        DevBuf<float> tile_cx;                     // ... and, under st_set_original_colors, the matching packed tile of content_x
     } comm;
     // profiling
     bool prof_on = false;
@@ -359,7 +365,8 @@ int preprocess_into(st_ctx* c, const void* hwc, int H, int W, int is_u8, float* 
 int set_input_common(st_ctx* c, int H, int W);
 void iterate_overwritten(st_ctx* c);
 int content_from_device(st_ctx* c, const float* xdev, int H, int W);
-int ensure_content_features(st_ctx* c);           // features of content-weighted blobs dropped by st_set_weights: recompute from the kept image
+int style_from_device(st_ctx* c, const float* xdev, int H, int W);      // style image on the device -> full forward, the target of every blob; returns with them in place
+int ensure_content_features(st_ctx* c);          // features of content-weighted blobs dropped by st_set_weights: recompute from the kept image
 // ---------------------------------------------------------------------------------------- engine_route.cpp
 // The planners only decide: no HIP call, no allocation on the device, nothing in the context changes.  Every shape predicate and
 // every per-call environment switch of the routing is read here, once per forward_range / backward_chain call (never cached: the
@@ -403,7 +410,20 @@ int lbfgs_clear_history(st_ctx* c, bool gram_form);        // what lbfgs_step an
 // iterate averaging: DecayingMean.__call__(x) on the current iterate, and the corrected, deprocessed mean into hwc where it is not NULL
 // (one launch, booked as P_MISC); average_corr: the divisor float(1 - decay ** items) of utils.py:64
 int average_enqueue(st_ctx* c, float* hwc);
+int average_advance(st_ctx* c, float* decay, float* rest, float* corr, int* first);      // items += 1; the scalars of that item's update and image
 float average_corr(const st_ctx* c);
+// ---------------------------------------------------------------------------------------- engine_color.cpp
+// luminance emission (st_set_original_colors).  luma_check: ST_ERR_STATE unless content_x exists at the input's size -- no HIP call, nothing
+// changes; luma_enqueue: the image of the current iterate into hwc in place of the deprocess pass, or, under iterate averaging, in place
+// of average_enqueue(c, hwc) with the same update of the mean (one launch, booked as P_MISC); luma_staged: a packed (3, h, w) tile `v` and
+// the matching packed tile `cx` of content_x into hwc, v divided by corr first where corr != 0
+int luma_check(const st_ctx* c);
+int luma_enqueue(st_ctx* c, float* hwc);
+int luma_staged(st_ctx* c, const float* v, const float* cx, float corr, int h, int w, float* hwc);
+// the style image on its way to the forward: refuses (ST_ERR_STATE) what colour matching cannot run on -- before anything is enqueued --
+// then derives the transform where st_set_style_color_match asks for it (waits for the stream) and recolours x (3, H, W) in place
+int style_color_check(const st_ctx* c);
+int style_recolor_enqueue(st_ctx* c, float* x, int H, int W);
 // ---------------------------------------------------------------------------------------- engine_tile.cpp
 // pack (mode 0) / unpack (1 assign, 2 add) the rectangles (y0, x0, h, w each) of a (C, h, w) tensor; checks them against it; enqueues only
 int strips(st_ctx* c, float* tensor, int C, int h, int w, const std::vector<int>& rects, float* buf, int mode);

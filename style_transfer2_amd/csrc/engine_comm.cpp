@@ -454,6 +454,7 @@ int st_tile_set_style(st_ctx* c, const void* hwc, int H, int W, int is_u8, int g
 // average) the staging form of launch_iterate_average, chw / corr + mean_c -- the arithmetic of the pass that hands out whole images
 static int tile_to_host(st_ctx* c, float* window, float corr, float* out_hwc)
 {
+    if (c->orig_colors) ST_TRY(luma_check(c));
     HIP_TRY(hipSetDevice(c->device));
     const st_ctx::Tile& t = c->tile;
     const int th = t.ty1 - t.ty0, tw = t.tx1 - t.tx0;
@@ -463,13 +464,19 @@ static int tile_to_host(st_ctx* c, float* window, float corr, float* out_hwc)
         c->comm.tile_chw.reset(); c->comm.tile_hwc.reset();
         ST_TRY(c->comm.tile_chw.alloc(n)); ST_TRY(c->comm.tile_hwc.alloc(n));
     }
+    if (c->orig_colors && n > c->comm.tile_cx.cap()) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        ST_TRY(c->comm.tile_cx.alloc(n));
+    }
     float *chw = c->comm.tile_chw, *hwc = c->comm.tile_hwc;
     int rc = ST_OK;
     {
         std::vector<int> rect = {t.ty0 - t.wy0, t.tx0 - t.wx0, th, tw};
         rc = strips(c, window, 3, c->H, c->W, rect, chw, 0);
+        if (rc == ST_OK && c->orig_colors) rc = strips(c, c->content_x, 3, c->H, c->W, rect, c->comm.tile_cx, 0);
     }
-    if (rc == ST_OK && corr != 0.f) {
+    if (rc == ST_OK && c->orig_colors) rc = luma_staged(c, chw, c->comm.tile_cx, corr, th, tw, hwc);      // the window's own content gives the chroma
+    else if (rc == ST_OK && corr != 0.f) {
         IterateAverageArgs a{};
         a.mean = chw; a.hwc = hwc; a.H = th; a.W = tw; a.corr = corr;
         if (launch_iterate_average(a, c->stream) != hipSuccess) rc = fail(ST_ERR_HIP, "iterate average staging launch failed");

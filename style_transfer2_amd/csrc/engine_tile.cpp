@@ -367,6 +367,7 @@ int st_tile_style_partials(st_ctx* c, const void* hwc, int H, int W, int is_u8, 
     HIP_TRY(hipSetDevice(c->device));
     size_t total = 0;
     for (int b = 0; b <= last_blob; ++b) { const size_t C = c->blob_c_topo(b); total += C * C; }
+    if (hwc) ST_TRY(style_color_check(c));
     if (total > 0x7fffffffu) return fail(ST_ERR_ARG, "the style partials exceed 2^31 floats");
     c->tile.sp_last = -1;
     ST_TRY(c->tile.sp.reserve(total));
@@ -380,6 +381,7 @@ int st_tile_style_partials(st_ctx* c, const void* hwc, int H, int W, int is_u8, 
         const bool same = c->act.H == H && c->act.W == W && !c->act.data.empty();
         if (same) a = &c->act;
         r = preprocess_into(c, hwc, H, W, is_u8, tmp);
+        if (r == ST_OK && c->style_match) r = style_recolor_enqueue(c, tmp, H, W);      // (a given transform: per pixel, so the window's is the image's)
         if (r == ST_OK) r = act_ensure(c, *a, H, W);
         if (r == ST_OK) r = forward_range(c, *a, tmp, last_blob);
         TileGeom g;

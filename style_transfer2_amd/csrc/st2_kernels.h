@@ -334,6 +334,22 @@ hipError_t launch_deprocess(const float* nchw, float* hwc, int H, int W, hipStre
 struct IterateAverageArgs { const float* x; float* mean; float* hwc; int H, W; float decay, rest, corr; int first; };
 hipError_t launch_iterate_average(const IterateAverageArgs& a, hipStream_t s);
 
+// The content's colours (color.hip; st2.h has the arithmetic).  Luminance emission: hwc = (cx + channel mean) + luma(v - cx), interleaved,
+// with v = x (EMIT_PLAIN; a packed tile being staged is the same form), v = mean / corr after the update of launch_iterate_average
+// (EMIT_UPDATE: x and mean in, mean out) or v = mean / corr of a mean that is only read (EMIT_STAGED).  16-byte accesses on every
+// stream where H * W % 4 == 0 and every pointer is 16-byte aligned, one pixel per thread otherwise; the grid of launch_iterate_average.
+enum { EMIT_PLAIN = 0, EMIT_UPDATE = 1, EMIT_STAGED = 2 };
+struct EmitLumaArgs { const float* x; float* mean; const float* cx; float* hwc; int H, W; float decay, rest, corr; int first, form; };
+hipError_t launch_emit_luma(const EmitLumaArgs& a, hipStream_t s);
+// The nine sums {p_R, p_G, p_B, p_R p_R, p_R p_G, p_R p_B, p_G p_G, p_G p_B, p_B p_B} over the n pixels of a planar (3, n) image, in
+// double throughout: partials is [9][kMomentBlocks] scratch, out takes the 9 sums (second stage: one thread per sum, workgroups in order)
+constexpr int kMomentSums = 9;
+constexpr int kMomentBlocks = 256;
+hipError_t launch_image_moments(const float* x, size_t n, double* partials, double* out, hipStream_t s);
+// x_c = ((A[c][0] x_R + A[c][1] x_G) + A[c][2] x_B) + b[c] in place on a planar (3, n) image; 16-byte and one-pixel paths as above
+struct RecolorArgs { float* x; size_t n; float A[9], b[3]; };
+hipError_t launch_recolor(const RecolorArgs& a, hipStream_t s);
+
 // ------------------------------------------------------------------------------------------
 // trace finalisation: one tiny kernel turns the partial sums of an opfunc into the trace scalars
 // ------------------------------------------------------------------------------------------

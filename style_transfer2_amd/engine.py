@@ -39,6 +39,25 @@ def _image_arg(image):
     return np.ascontiguousarray(arr, F32), 0
 
 
+def cov_full(upper):
+    """The six values RR, RG, RB, GG, GB, BB of the C ABI -> symmetric (3, 3) float64."""
+    rr, rg, rb, gg, gb, bb = (float(v) for v in upper)
+    return np.array(((rr, rg, rb), (rg, gg, gb), (rb, gb, bb)), np.float64)
+
+
+def color_transform(mean_c, cov_c, mean_s, cov_s):
+    """Linear colour transfer (st_color_transform; host only, no engine): (A (3, 3), b (3,)) float32 such that s' = A s + b, in
+    preprocessed coordinates, gives pixels with colour mean mean_s and covariance cov_s (3, 3) the mean mean_c and covariance cov_c."""
+    def upper(cov):
+        cov = np.asarray(cov, np.float64).reshape(3, 3)
+        return (c_double * 6)(cov[0, 0], cov[0, 1], cov[0, 2], cov[1, 1], cov[1, 2], cov[2, 2])
+    mc = (c_double * 3)(*[float(v) for v in mean_c])
+    ms = (c_double * 3)(*[float(v) for v in mean_s])
+    A, b = (c_float * 9)(), (c_float * 3)()
+    check(capi.load_library().st_color_transform(mc, upper(cov_c), ms, upper(cov_s), A, b))
+    return np.array(A[:], F32).reshape(3, 3), np.array(b[:], F32)
+
+
 class Engine:
     def __init__(self, topology=None, device=0, precision='fp32'):
         self.lib = capi.load_library()
@@ -404,6 +423,55 @@ class Engine:
         mean = np.empty((1, 3, h, w), F32)
         check(self.lib.st_get_iterate_average(self._ctx, None, None, _ptr(mean)))
         return decay.value, items.value, mean
+
+    # -- the content's colours (st2.h: luminance-only output, colour-matched style) ----------------------------------
+    def set_original_colors(self, on):
+        """True: step() / step_end() (tile-sharded: the tile readers) hand out the luminance of the iterate with the chroma of the content
+        image; the optimisation, get_input_nchw() and the running mean are untouched.  Refused while a pipelined iteration is in flight;
+        while on, a step that wants an image is refused without a content image of the input's size."""
+        check(self.lib.st_set_original_colors(self._ctx, 1 if on else 0))
+
+    def image_moments(self, image):
+        """(mean (3,), cov (3, 3)) of an HxWx3 image in float64: the colour mean in image scale and the population covariance, from sums
+        taken on the device in double in a fixed order (st_image_moments)."""
+        arr, u8 = _image_arg(image)
+        mean, cov = (c_double * 3)(), (c_double * 6)()
+        check(self.lib.st_image_moments(self._ctx, _ptr(arr), arr.shape[0], arr.shape[1], u8, mean, cov))
+        return np.array(mean[:], np.float64), cov_full(cov[:])
+
+    def set_style_transform(self, A, b):
+        """The affine colour map s' = A s + b (preprocessed coordinates) every later set_style / tile_set_style / tile_style_partials applies
+        to the style image; A = b = None turns it off."""
+        if A is None and b is None:
+            check(self.lib.st_set_style_transform(self._ctx, None, None))
+            return
+        A, b = np.ascontiguousarray(A, F32).reshape(9), np.ascontiguousarray(b, F32).reshape(3)
+        check(self.lib.st_set_style_transform(self._ctx, A.ctypes.data_as(POINTER(c_float)), b.ctypes.data_as(POINTER(c_float))))
+
+    def set_style_color_match(self, on):
+        """True: set_style gives the style image the content image's colour mean and covariance first (linear colour transfer, derived from
+        the two images' moments when the style is set).  Refused on a tile-sharded context: set_style_transform there."""
+        check(self.lib.st_set_style_color_match(self._ctx, 1 if on else 0))
+
+    def color_modes(self):
+        """(original_colors, style_match, A (3, 3), b (3,)): style_match 0 off, 1 colour matching, 2 a given transform; A, b the transform
+        last applied (or given and waiting), the identity before either."""
+        oc, sm = c_int(), c_int()
+        A, b = np.empty(9, F32), np.empty(3, F32)
+        check(self.lib.st_get_color_modes(self._ctx, byref(oc), byref(sm), A.ctypes.data_as(POINTER(c_float)), b.ctypes.data_as(POINTER(c_float))))
+        return bool(oc.value), sm.value, A.reshape(3, 3), b
+
+    def set_style_nchw(self, x):
+        """set_style for an already-preprocessed (1, 3, H, W) image; no colour transform is applied."""
+        x = np.ascontiguousarray(x, F32)
+        check(self.lib.st_set_style_nchw(self._ctx, _ptr(x), x.shape[2], x.shape[3]))
+
+    def style_recolor(self, image):
+        """Test hook: the preprocessed, recoloured (1, 3, H, W) image exactly as set_style would forward it under the modes in force."""
+        arr, u8 = _image_arg(image)
+        out = np.empty((1, 3, arr.shape[0], arr.shape[1]), F32)
+        check(self.lib.st_style_recolor(self._ctx, _ptr(arr), arr.shape[0], arr.shape[1], u8, _ptr(out)))
+        return out
 
     def steps_pending(self):
         return int(self.lib.st_step_pending(self._ctx))

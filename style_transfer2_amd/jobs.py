@@ -38,11 +38,15 @@ def load_rgb(path):
 
 
 def run_job(transfer, content, style, iterations, size=None, style_size=None, optimizer='adam', step_size=None,
-            weights=None, params=None, init=None, seed=0, callback=None, iterate_average=None):
+            weights=None, params=None, init=None, seed=0, callback=None, iterate_average=None, original_colors=None,
+            match_style_colors=None):
     """One whole stylisation: content/style are PIL images or HxWx3 arrays.  Returns the final HxWx3 float32
     image.  Mirrors app.init_arrays + 'start': SetImages(reset) -> SetWeights -> SetOptimizer -> iterate.
     iterate_average: a decay in (0, 1) makes every image handed out (the callback's, the result) the bias-corrected running mean of
-    the iterates (Engine.set_iterate_average); 0 turns that off; None leaves the engine as it is."""
+    the iterates (Engine.set_iterate_average); 0 turns that off; None leaves the engine as it is.
+    original_colors: True makes every image handed out keep the content image's colours (the iterate's luminance, the content's chroma:
+    Engine.set_original_colors); match_style_colors: True gives the style image the content image's colour mean and covariance before
+    the style targets are taken (Engine.set_style_color_match).  False turns either off; None leaves the engine as it is."""
     from .device_optimizers import AdamOptimizer, LBFGSOptimizer
     if isinstance(content, Image.Image):
         content = np.uint8(resize_to_fit(content, size or max(content.size)))
@@ -50,6 +54,10 @@ def run_job(transfer, content, style, iterations, size=None, style_size=None, op
         style = np.uint8(resize_to_fit(style, style_size or size or max(style.size)))
     if init is None:
         init = noise_image(content.shape[:2], seed)
+    if original_colors is not None:
+        transfer.engine.set_original_colors(original_colors)
+    if match_style_colors is not None:
+        transfer.engine.set_style_color_match(match_style_colors)
     transfer.set_input(init)
     transfer.set_content(content)
     transfer.set_style(style)
@@ -76,7 +84,7 @@ def run_job(transfer, content, style, iterations, size=None, style_size=None, op
 
 def run_tiled_job(net_params, content, style, iterations, grid, size=None, style_size=None, weights=None, params=None, init=None,
                   seed=0, device=0, precision='fp32', topology=None, callback=None, optimizer='adam', step_size=None, shard_style=False,
-                  iterate_average=None):
+                  iterate_average=None, original_colors=None, match_style_colors=None):
     """The same job for an image no single engine holds (an 8192 x 8192 image has conv1 blobs of 17 GB each): the image is cut into
     grid = (rows, cols) tiles, every tile + apron is an engine context of THIS process on the one GPU (tiled.InProcessFabric: one
     thread per rank, the all-reduces and strip exchanges are device-to-device copies); one st_tile_step per rank and iteration, Adam or
@@ -86,6 +94,9 @@ def run_tiled_job(net_params, content, style, iterations, grid, size=None, style
     style-weighted blob) and every rank forwards one window of it, instead of every rank forwarding all of it.
     iterate_average: a decay in (0, 1) makes every rank keep the running mean of its window's iterates; the stitched image is then the
     bias-corrected mean, as run_job's is.
+    original_colors: every rank hands out its tile with the chroma of its own window of the content image (per pixel: the stitched image
+    is run_job's).  match_style_colors: the colour moments of the WHOLE content and style images are taken once, through rank 0's engine,
+    and the transform derived from them goes to every rank (Engine.set_style_transform) before the style is set, plain or shard_style.
     Returns the stitched HxWx3 float32 image; callback(i, trace values) after every iteration."""
     from . import tiled, tiling
     from .engine import VGG19_TOPOLOGY
@@ -105,9 +116,14 @@ def run_tiled_job(net_params, content, style, iterations, grid, size=None, style
     world = rows * cols
     fabric = tiled.InProcessFabric(world, timeout=600.0)
     ranks, backends = [], []
+    # colour matching: rank 0's backend derives A, b from the whole images before it sets its style; the other ranks are given them
+    transform = (content, style) if match_style_colors else None
     for r in range(world):
         b = HipTileBackend(net_params, tg, r, content, None if shard_style else style, init, weights, params, step_size=step_size or {'adam': 10, 'lbfgs': 1}[optimizer],
-                           topology=topology, device=device, precision=precision, optimizer=optimizer, iterate_average=iterate_average)
+                           topology=topology, device=device, precision=precision, optimizer=optimizer, iterate_average=iterate_average,
+                           original_colors=original_colors, style_transform=transform)
+        if r == 0 and match_style_colors:
+            transform = b.style_transform
         backends.append(b)
         b.comm_init_local(r, world, fabric)
         ranks.append(tiled.FusedTiledTransfer(tg, r, b))

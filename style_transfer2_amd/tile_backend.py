@@ -9,7 +9,7 @@ import numpy as np
 
 from . import capi
 from .capi import check
-from .engine import Engine, OPT_ADAM, OPT_LBFGS
+from .engine import Engine, OPT_ADAM, OPT_LBFGS, color_transform
 from .tiled import crop, local_rect, torch          # (torch: tiled's lazy import -- nothing here loads it at import time)
 from .transfer import weight_table, LOSS_NAMES, SCALAR_LOSS_NAMES
 
@@ -29,7 +29,8 @@ def dev_tensor(ptr, shape, device):
 
 class HipTileBackend:
     def __init__(self, net_params, grid, rank, content, style, init, weights, params, step_size=10,
-                 topology=None, device=0, precision='fp32', use_torch=True, optimizer='adam', iterate_average=None):
+                 topology=None, device=0, precision='fp32', use_torch=True, optimizer='adam', iterate_average=None,
+                 original_colors=None, style_transform=None):
         # torch bundles its own copy of the HIP runtime; when both live in one process torch's must come up FIRST.
         # The phase-by-phase driver and the host-staged test transport need torch; the in-engine iteration over RCCL
         # (comm_init_rccl + tiled.FusedTiledTransfer) does not: pass use_torch=False and the process never loads it.
@@ -46,6 +47,21 @@ class HipTileBackend:
         self.device_index = device
         self.grid, self.rank = grid, rank
         w, t = grid.windows[rank], grid.tiles[rank]
+        # the content's colours.  original_colors: the tile readers hand out the chroma of this window's own content (per pixel, so the
+        # stitched image is the whole-image job's).  style_transform: (A, b) for Engine.set_style_transform, in force before the style is
+        # set here or by shard_style -- or (content image, style image), WHOLE images, to derive it from through this engine (colour
+        # matching itself is refused on a tile-sharded context: a window's content is not the image's)
+        if original_colors is not None:
+            self.engine.set_original_colors(original_colors)
+        self.style_transform = None
+        if style_transform is not None:
+            first, second = style_transform
+            if np.ndim(first) == 3:
+                mean_c, cov_c = self.engine.image_moments(first)
+                mean_s, cov_s = self.engine.image_moments(second)
+                first, second = color_transform(mean_c, cov_c, mean_s, cov_s)
+            self.style_transform = (first, second)
+            self.engine.set_style_transform(first, second)
         self.engine.set_input(crop(init, w))
         self.engine.set_content(crop(content, w))
         if style is not None:            # None: the targets come from the sharded style pass (shard_style, after comm_init_*)

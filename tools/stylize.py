@@ -3,7 +3,9 @@
 --grid RxC: an image too large for one engine (beyond about 4096 x 4096) is cut into R x C tiles that all live on the one GPU
 (jobs.run_tiled_job; the image edges must divide into tiles of multiples of 16 pixels).
 --avg-decay D: the image written is the bias-corrected exponentially weighted mean of the iterates (st_set_iterate_average), not
-the last iterate."""
+the last iterate.
+--original-colors: the image written keeps the content image's colours (the iterate's luminance, the content's chroma).
+--match-style-colors: the style image is given the content image's colour mean and covariance before the style targets are taken."""
 import argparse
 import os
 import sys
@@ -37,6 +39,9 @@ def parser():
     ap.add_argument('--shard-style', action='store_true', help='with --grid: cut the style image over the ranks as well (every rank forwards one window of it)')
     ap.add_argument('--avg-decay', type=avg_decay, default=None, metavar='D',
                     help='st_set_iterate_average: write the bias-corrected running mean of the iterates with this decay, 0 < D < 1 (default: the last iterate)')
+    ap.add_argument('--original-colors', action='store_true', help='st_set_original_colors: keep the content image\'s colours (luminance of the result, chroma of the content)')
+    ap.add_argument('--match-style-colors', action='store_true',
+                    help='st_set_style_color_match (with --grid: st_set_style_transform on every rank): linear colour transfer of the content\'s colours onto the style image')
     return ap
 
 
@@ -65,12 +70,14 @@ def main(argv=None):
         rows, cols = (int(v) for v in args.grid.split('x'))
         image = jobs.run_tiled_job(params, jobs.load_rgb(args.content), jobs.load_rgb(args.style), args.iters, (rows, cols), size=args.size,
                                    style_size=args.style_size or None, device=args.gpu, optimizer=args.optimizer, shard_style=args.shard_style,
-                                   iterate_average=args.avg_decay)
+                                   iterate_average=args.avg_decay, original_colors=args.original_colors or None,
+                                   match_style_colors=args.match_style_colors or None)
     else:
         job = st2.StyleTransfer(st2.HipModel(params, topology=None if topology is st2.VGG19_TOPOLOGY else topology, device=args.gpu, precision=args.precision,
                                              conv_algo=args.conv_algo, gram_algo=args.gram_algo, pool_algo=args.pool_algo))
         image = jobs.run_job(job, jobs.load_rgb(args.content), jobs.load_rgb(args.style), args.iters, size=args.size,
-                             style_size=args.style_size or None, optimizer=args.optimizer, iterate_average=args.avg_decay)
+                             style_size=args.style_size or None, optimizer=args.optimizer, iterate_average=args.avg_decay,
+                             original_colors=args.original_colors or None, match_style_colors=args.match_style_colors or None)
     Image.fromarray(np.uint8(np.clip(image, 0, 255))).save(args.out)
     print('wrote', args.out, image.shape)
 

@@ -110,6 +110,36 @@ def read_iterate_average(config):
     return value
 
 
+COLOR_KEYS = ('original_colors', 'style_color_match')
+
+
+def read_color_keys(config):
+    """The optional config keys ``original_colors = 0|1`` (every ``Iterate`` keeps the content image's colours: the iterate's luminance,
+    the content's chroma; Engine.set_original_colors) and ``style_color_match = 0|1`` (the style image is given the content image's
+    colour mean and covariance before the style targets are taken; Engine.set_style_color_match).  Returns {key: bool} of the keys that
+    are present (an absent or empty key makes no call: the engine's default, off, stays); any other value is a ValueError that names
+    the key.  Pure: any mapping with ``get`` will do."""
+    found = {}
+    for key in COLOR_KEYS:
+        raw = config.get(key, None)
+        if raw is None or str(raw).strip() == '':
+            continue
+        if str(raw).strip() not in ('0', '1'):
+            raise ValueError('config key %s = %r: must be 0 or 1' % (key, raw))
+        found[key] = str(raw).strip() == '1'
+    return found
+
+
+def apply_color_keys(transfer, config):
+    """read_color_keys(config) onto the transfer's engine.  The wire format stays as it is: only the pixels of Iterate.image change."""
+    keys = read_color_keys(config)
+    if 'original_colors' in keys:
+        transfer.engine.set_original_colors(keys['original_colors'])
+    if 'style_color_match' in keys:
+        transfer.engine.set_style_color_match(keys['style_color_match'])
+    return transfer
+
+
 def build_transfer(config):
     """Model + StyleTransfer for this worker (reference worker.py:326-332).  Exits with code 2 when the
     HIP library, the GPU or the weights are missing."""
@@ -139,7 +169,7 @@ def build_transfer(config):
                                      % weights_path)
         model = st2.HipModel(params, topology=None if topology == st2.VGG19_TOPOLOGY else topology, device=max(gpu, 0),
                              precision=config.get('precision', 'fp32'), **read_algo_keys(config))
-        return st2.StyleTransfer(model)
+        return apply_color_keys(st2.StyleTransfer(model), config)
     except Exception as err:  # HipUnavailable, StError, OSError ...
         print(BACKEND_MSG % err, file=sys.stderr)
         sys.exit(2)
@@ -303,7 +333,8 @@ class Worker:
         self._shutting_down = False
         try:
             # the model first (it may sys.exit(2): reference worker.py:51-53), the sender thread only once it exists
-            self.transfer = transfer if transfer is not None else build_transfer(config)
+            # (a transfer handed in gets the colour keys here; build_transfer applies them to the one it makes)
+            self.transfer = apply_color_keys(transfer, config) if transfer is not None else build_transfer(config)
             # iterate averaging (config key iterate_average): the Iterate images become the running mean of the iterates; their index,
             # the trace and the order of everything on the wire stay as they are
             decay = read_iterate_average(config)
