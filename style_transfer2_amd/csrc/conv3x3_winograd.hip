@@ -100,6 +100,68 @@ constexpr unsigned kOOB = 0xffffffffu;
 
 __device__ __forceinline__ float f4c(const float4& v, int i) { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; }
 
+// The operands of the specialised epilogues (conv3x3_wino_body, EPI != 0; RS: the half-tile builds) and their loads.  The loads of ALL
+// batches are issued ahead of the first store: vmcnt counts loads and stores together, in issue order, so written batch by batch (load,
+// compute, store) the wait for a batch's operands was also a wait for the write acknowledgements of the previous batch's stores, and
+// then for a memory round trip of its own -- NEB times in a row, with nothing co-resident to hide them.  The first of them go out under
+// the LAST chunk's MFMAs: its clumps carry no U load after k-pair 0, no input transform and no DMA, so the vector-memory slot is idle
+// there and the U ring retires a set per k-pair; the rest right after the loop.
+// A load GROUP is the four loads of one operand of one batch (four accumulator rows): bias (dwords) in the forward kinds, mask and inject
+// (16 bytes each) in the data-gradient kinds; batch by batch, so that the first batch's operands are also the first to land.
+// (A type of its own, empty for EPI == 0, so that the builds with the generic epilogue compile to the code they always were.)
+template <int EPI, bool RS> struct WinoEpiOps {
+    static constexpr bool E_FWD = EPI == 1 || EPI == 2, E_MASK = EPI == 3;
+    static constexpr int NEB = RS ? 2 : 4;                  // batches: the wave finishes 4 NEB accumulator rows (half tile: rows 8 ph .. 8 ph + 7)
+    static constexpr int NG = E_MASK ? 2 * NEB : NEB;       // load groups
+    static constexpr int UNDER = NG < 4 ? NG : 4;           // ... of which under the loop: one per clump, in the last UNDER clumps of the last chunk
+    int mw, dm0, odd;                                       // the lane's first channel of the slice; the wave's first row in it (half tile: 16 ph)
+    bool live, has_inj;
+    unsigned row0, plane4, out_bytes;
+    float mk[E_MASK ? NEB : 1][E_MASK ? 4 : 1][4], ij[E_FWD ? 1 : NEB][E_FWD ? 1 : 4][4], bs[E_FWD ? NEB : 1][E_FWD ? 4 : 1];
+
+    __device__ __forceinline__ void init(const WinoKArgs& a, int lane, int yw, int x0, int m0, int ph, unsigned plane)
+    {
+        odd = lane & 1;
+        const int gy = yw + 2 * ((lane & 31) >> 4) + odd;   // this lane's row after the epilogue's row swap
+        const int gx4 = x0 + 2 * (lane & 14);               // first of the lane pair's 4 pixels (16-byte aligned)
+        live = gx4 < a.W && gy < a.H;
+        mw = m0 + 4 * (lane >> 5);
+        dm0 = RS ? 16 * ph : 0;
+        has_inj = a.inject != nullptr;
+        plane4 = plane * 4u;
+        out_bytes = (unsigned)a.M * plane4;
+        row0 = ((unsigned)mw * plane + (live ? (unsigned)gy * a.W + gx4 : 0u)) * 4u;
+    }
+    // A row's byte offset is the lane's base plus a wave-uniform step, or out of range (the lane is outside the image, the row beyond M):
+    // a few instructions and no branch, so that it is computed where it is used (in a clump, and again for the store) instead of kept.
+    __device__ __forceinline__ unsigned row_off(const WinoKArgs& a, int ebl, int ee) const
+    {
+        const int dm = dm0 + 8 * ebl + ee;                  // wave-uniform; the row is mw + dm
+        return (live & (mw + dm < a.M)) ? row0 + (unsigned)dm * plane4 : kOOB;
+    }
+    __device__ __forceinline__ void load(const WinoKArgs& a, int g)       // (g: a compile-time constant wherever this is called)
+    {
+        const int ebl = E_MASK ? g >> 1 : g;
+        const bool mask = E_MASK && (g & 1) == 0;
+        // ("absent" = a zero-size resource: without an injected diff the loads return 0)
+        const __amdgpu_buffer_rsrc_t rs = E_FWD ? __builtin_amdgcn_make_buffer_rsrc((void*)a.bias, 0, (unsigned)a.M * 4u, 0x00020000)
+                                        : mask ? __builtin_amdgcn_make_buffer_rsrc((void*)a.mask_src, 0, out_bytes, 0x00020000)
+                                               : __builtin_amdgcn_make_buffer_rsrc((void*)a.inject, 0, has_inj ? out_bytes : 0u, 0x00020000);
+#pragma unroll
+        for (int ee = 0; ee < 4; ++ee) {
+            if constexpr (E_FWD) {
+                bs[ebl][ee] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (mw + dm0 + 8 * ebl + ee) * 4, 0, 0));      // (beyond M: out of range, 0)
+            } else {
+                const uint4 v = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, row_off(a, ebl, ee), 0, 0));
+                float (&d4)[4] = mask ? mk[E_MASK ? ebl : 0][E_MASK ? ee : 0] : ij[ebl][ee];
+                d4[0] = __builtin_bit_cast(float, v.x); d4[1] = __builtin_bit_cast(float, v.y); d4[2] = __builtin_bit_cast(float, v.z); d4[3] = __builtin_bit_cast(float, v.w);
+            }
+        }
+        asm volatile("" ::: "memory");                      // keeps the loads here
+    }
+};
+template <bool RS> struct WinoEpiOps<0, RS> {};
+
 // WM waves along m (32 channels each) x TG tile groups (32 tiles = 4 rows x 32 columns each), WM * TG = 4:
 //   <4,1>: 128 channels x  4 rows x 32 columns      <2,2>: 64 channels x 8 rows x 32 columns
 // With TG = 2 the two waves that share a channel slice load the same U lines together (one L2 fetch), and every
@@ -150,7 +212,9 @@ __device__ __forceinline__ float f4c(const float4& v, int i) { return i == 0 ? v
 //                the channel range" = an out-of-range offset): no branch around a load or store, no 64-bit address arithmetic.  The
 //                arithmetic is the generic epilogue's, operation for operation: results are the same bits.  Measured on the split-operand
 //                kernel first (conv3x3_wino_split.hip: 135 -> ~50 instructions per accumulator row, 12.9 k -> 6.9 k cycles); here the
-//                generic epilogue was ~3 200 instructions per wave after the last MFMA for ~900 of essential work.
+//                generic epilogue was ~3 200 instructions per wave after the last MFMA for ~900 of essential work.  Their operand loads
+//                (bias, mask, injected diff of every accumulator row) all go out ahead of the first store, the first of them under the
+//                last chunk's MFMAs (WinoEpiOps above): headline job 142.26 -> 143.74 it/s, same-box A/B.
 template <int WM, int TG, int DIAG = 0, bool QUAD = true, bool PS = false, bool W8 = false, bool H4 = false, bool UNPOOL = false, bool BIG = false,
           bool NOOUT = false, int EPI = 0>
 __device__ __forceinline__ void conv3x3_wino_body(const WinoKArgs& a)
@@ -420,6 +484,10 @@ __device__ __forceinline__ void conv3x3_wino_body(const WinoKArgs& a)
     unsigned long long t0 = 0, r0 = 0;
     if (DIAG) { t0 = __builtin_amdgcn_s_memtime(); r0 = __builtin_amdgcn_s_memrealtime(); }
 
+    // specialised epilogues: what their operand loads need (the first of them are issued under the last chunk's MFMAs)
+    WinoEpiOps<EPI, RS> eo;
+    if constexpr (EPI != 0) eo.init(a, lane, y0 + 4 * wave_g, x0, mt * BM + wave_m * 32, ph, plane);
+
     // One chunk = 4 k-pairs x 16 MFMAs.  With one wave per SIMD nothing this wave issues overlaps its own MFMAs
     // (measured: a bare MFMA stream runs at 64.0 cycles each, every instruction in between adds ~3 cycles plus ~9 per
     // interrupted MFMA pair), so the auxiliary work is kept minimal and CLUMPED: one clump per k-pair, right after
@@ -451,6 +519,12 @@ __device__ __forceinline__ void conv3x3_wino_body(const WinoKArgs& a)
                         b_fetch(cur ^ 1, 0, 0);
                     }
                     if (MORE || kpl == 0) u_fill(kp + 3);
+                    if constexpr (EPI != 0) {
+                        if constexpr (!MORE) {                            // the last chunk: a group of epilogue operand loads where the U loads were
+                            constexpr int UNDER = WinoEpiOps<EPI, RS>::UNDER;
+                            if (kpl >= 4 - UNDER) eo.load(a, kpl - (4 - UNDER));
+                        }
+                    }
                     if (MORE && do_xf) {
                         if (kpl == 0) xf_read(raw_s[cur ^ 1] + x_raw);
                         if (kpl == 1) { up_expand(); pin(); xf_math(); pin(); }
@@ -470,6 +544,18 @@ __device__ __forceinline__ void conv3x3_wino_body(const WinoKArgs& a)
         for (; c + 2 < nch; ++c) chunk(c, T{}, T{});
         if (c + 1 < nch) { chunk(c, T{}, F{}); ++c; }
         chunk(c, F{}, F{});
+    }
+    if constexpr (EPI != 0) {
+        if constexpr (!RS && EPI == 2) {
+            // (the pooling kinds: the accumulators stay put until here -- it keeps their reads out of the last k-pair's MFMAs)
+#pragma unroll
+            for (int p = 0; p < NACC; ++p) asm volatile("" : "+a"(acc[p]));
+        }
+#pragma unroll
+        for (int g = WinoEpiOps<EPI, RS>::UNDER; g < WinoEpiOps<EPI, RS>::NG; ++g) eo.load(a, g);   // the rest of the operand loads: still ahead of every store
+        asm volatile("" : "+v"(eo.row0));    // (a value the compiler cannot see through: the stores' offsets are computed again, not kept)
+        // (without the fence the scheduler sinks the loads below the first batches' arithmetic and reads every accumulator early: spills)
+        __builtin_amdgcn_sched_barrier(0);
     }
 
     unsigned long long t_loop_end = 0;
@@ -610,21 +696,12 @@ __device__ __forceinline__ void conv3x3_wino_body(const WinoKArgs& a)
     }
   } else if constexpr (EPI != 0) {
     // ---- specialised epilogues (see EPI above): the generic one below, kind by kind, through buffer accesses
+    // (the operand loads of every batch are out: WinoEpiOps::load, under the last chunk and right after the loop)
     constexpr bool E_FWD = EPI == 1 || EPI == 2, E_POOL = EPI == 2, E_MASK = EPI == 3;
+    constexpr int NEB = RS ? 2 : 4;
     typedef unsigned wn_u32x4 __attribute__((ext_vector_type(4)));
-    const int t31 = lane & 31, khalf = lane >> 5;
-    const int odd = lane & 1;
-    const int gy = y0 + 4 * wave_g + 2 * (t31 >> 4) + odd;          // this lane's row after the swap
-    const int gx4 = x0 + 2 * (t31 & 14);                            // first of the pair's 4 pixels (16-byte aligned)
-    const bool live = gx4 < a.W && gy < a.H;
-    const int mw = mt * BM + wave_m * 32 + 4 * khalf;
-    const unsigned pix = live ? (unsigned)gy * a.W + gx4 : 0u;
-    const unsigned out_bytes = (unsigned)a.M * plane * 4u;
-    const bool has_inj = a.inject != nullptr;
-    const __amdgpu_buffer_rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc((void*)a.out, 0, NOOUT ? 0u : out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_mk = __builtin_amdgcn_make_buffer_rsrc((void*)a.mask_src, 0, E_MASK ? out_bytes : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_ij = __builtin_amdgcn_make_buffer_rsrc((void*)a.inject, 0, (!E_FWD && has_inj) ? out_bytes : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_bs = __builtin_amdgcn_make_buffer_rsrc((void*)a.bias, 0, E_FWD ? (unsigned)a.M * 4u : 0u, 0x00020000);
+    const int t31 = lane & 31;
+    const __amdgpu_buffer_rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc((void*)a.out, 0, NOOUT ? 0u : eo.out_bytes, 0x00020000);
     // the fused pool: the lane's 2x2 tile IS one pooling window; a window clipped by the bottom edge keeps its first row only
     const int ty2 = y0 + 4 * wave_g + 2 * (t31 >> 4), tx2 = x0 + 2 * (t31 & 15);
     const bool plive = E_POOL && tx2 < a.W && ty2 < a.H, prow1 = ty2 + 1 < a.H;
@@ -632,31 +709,16 @@ __device__ __forceinline__ void conv3x3_wino_body(const WinoKArgs& a)
     const unsigned ppix = plive ? (unsigned)(ty2 >> 1) * a.pool_w + (tx2 >> 1) : 0u;
     const __amdgpu_buffer_rsrc_t rs_po = __builtin_amdgcn_make_buffer_rsrc((void*)a.pool_out, 0, E_POOL ? (unsigned)a.M * pplane * 4u : 0u, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_pa = __builtin_amdgcn_make_buffer_rsrc((void*)a.pool_amap, 0, (E_POOL && a.pool_amap) ? (unsigned)a.M * pplane : 0u, 0x00020000);
-    constexpr int NEB = RS ? 2 : 4;                         // H4: this wave finishes accumulator rows 8 ph .. 8 ph + 7
+    // Compute / store phase: the arithmetic and the stores of the batches, in the order they always had.
 #pragma unroll
     for (int ebl = 0; ebl < NEB; ++ebl) {
-        const int eb = RS ? 2 * ph + ebl : ebl;
-        const int mb = mw + 8 * eb;                         // rows mb .. mb+3 (e = 4 eb + 0..3)
-        unsigned off[4];
-        float mk[E_MASK ? 4 : 1][4], ij[E_FWD ? 1 : 4][4], bs[E_FWD ? 4 : 1];
+        const int mb = eo.mw + eo.dm0 + 8 * ebl;
+        if constexpr (!RS && !E_POOL) {
+            // the accumulators are read batch by batch, each behind this point: left alone, the output transforms of all sixteen rows are
+            // vectorised together and every accumulator is read ahead of the loads, next to 8 NEB landing quads (register moves, spills).
+            // (Not the pooling kinds: their rows branch, and every block behind such a point reads all 256 registers again.)
 #pragma unroll
-        for (int ee = 0; ee < 4; ++ee) {
-            off[ee] = (live && mb + ee < a.M) ? ((unsigned)(mb + ee) * plane + pix) * 4u : kOOB;
-            if constexpr (E_FWD) bs[ee] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_bs, (mb + ee) * 4, 0, 0));      // (beyond M: out of range, 0)
-        }
-        if constexpr (E_MASK) {
-#pragma unroll
-            for (int ee = 0; ee < 4; ++ee) {
-                const uint4 v = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs_mk, off[ee], 0, 0));
-                mk[ee][0] = __builtin_bit_cast(float, v.x); mk[ee][1] = __builtin_bit_cast(float, v.y); mk[ee][2] = __builtin_bit_cast(float, v.z); mk[ee][3] = __builtin_bit_cast(float, v.w);
-            }
-        }
-        if constexpr (!E_FWD) {
-#pragma unroll
-            for (int ee = 0; ee < 4; ++ee) {
-                const uint4 v = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs_ij, off[ee], 0, 0));
-                ij[ee][0] = __builtin_bit_cast(float, v.x); ij[ee][1] = __builtin_bit_cast(float, v.y); ij[ee][2] = __builtin_bit_cast(float, v.z); ij[ee][3] = __builtin_bit_cast(float, v.w);
-            }
+            for (int p = 0; p < NACC; ++p) asm volatile("" : "+a"(acc[p]));
         }
 #pragma unroll
         for (int ee = 0; ee < 4; ++ee) {
@@ -664,7 +726,7 @@ __device__ __forceinline__ void conv3x3_wino_body(const WinoKArgs& a)
             float y00, y01, y10, y11;
             out_xf(e, y00, y01, y10, y11);
             if constexpr (E_POOL) {
-                const float b = bs[E_FWD ? ee : 0];
+                const float b = eo.bs[E_FWD ? ebl : 0][E_FWD ? ee : 0];
                 float pm = y00 > y01 ? y00 : y01;
                 const float p1 = y10 > y11 ? y10 : y11, pm2 = pm > p1 ? pm : p1;
                 pm = prow1 ? pm2 : pm;
@@ -678,27 +740,28 @@ __device__ __forceinline__ void conv3x3_wino_body(const WinoKArgs& a)
             }
             if constexpr (NOOUT) continue;
             // give away the row this lane does not keep, receive the partner's part of the row it keeps (quad_perm 1,0,3,2)
-            const float s0 = odd ? y00 : y10, s1 = odd ? y01 : y11;
+            const float s0 = eo.odd ? y00 : y10, s1 = eo.odd ? y01 : y11;
             const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s0), 0xB1, 0xf, 0xf, true));
             const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s1), 0xB1, 0xf, 0xf, true));
             float o[4];
-            o[0] = odd ? r0 : y00; o[1] = odd ? r1 : y01; o[2] = odd ? y10 : r0; o[3] = odd ? y11 : r1;
+            o[0] = eo.odd ? r0 : y00; o[1] = eo.odd ? r1 : y01; o[2] = eo.odd ? y10 : r0; o[3] = eo.odd ? y11 : r1;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if constexpr (E_FWD) {
-                    o[j] += bs[E_FWD ? ee : 0];
+                    o[j] += eo.bs[E_FWD ? ebl : 0][E_FWD ? ee : 0];
                     o[j] = o[j] > 0.f ? o[j] : 0.f;
                 } else {
-                    if constexpr (E_MASK) o[j] = mk[E_MASK ? ee : 0][j] > 0.f ? o[j] : 0.f;
-                    const float oi = o[j] + ij[E_FWD ? 0 : ee][j];
-                    o[j] = has_inj ? oi : o[j];
+                    if constexpr (E_MASK) o[j] = eo.mk[E_MASK ? ebl : 0][E_MASK ? ee : 0][j] > 0.f ? o[j] : 0.f;
+                    const float oi = o[j] + eo.ij[E_FWD ? 0 : ebl][E_FWD ? 0 : ee][j];
+                    o[j] = eo.has_inj ? oi : o[j];
                 }
             }
             wn_u32x4 ov;
 #pragma unroll
             for (int j = 0; j < 4; ++j) ov[j] = __builtin_bit_cast(unsigned, o[j]);
-            __builtin_amdgcn_raw_buffer_store_b128(ov, rs_o, off[ee], 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(ov, rs_o, eo.row_off(a, ebl, ee), 0, 0);
         }
+        __builtin_amdgcn_sched_barrier(0);
     }
   } else {
     // ---- epilogue: output transform (in-lane), then bias / ReLU / mask / inject.
