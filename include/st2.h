@@ -110,6 +110,20 @@ int st_backward(st_ctx* ctx, int n, const int* blob_index, const float* const* d
 /* gram_matrix (worker.py:109-114) of a blob of the last st_forward: out is C*C.  Contracts the fp32 blob: refused, as
  * st_get_blob refuses it, for a blob the last evaluation did not write in fp32. */
 int st_gram(st_ctx* ctx, int index, float* out);
+/* Test hook: what the LAST objective evaluation (st_opfunc with or without out_grad, st_step*, or the tile-sharded phases up to
+ * st_tile_losses_finish) left for blob `index` in the context's own work buffers.  Any pointer may be NULL.
+ *   D      C*C    G - G_style exactly as the style-gradient launch read it (row-major, row padding stripped)
+ *   raw_S  C*h*w  c2 * D @ F unscaled, c2 = float(2 / (C C n)): it exists only after the first evaluation since reset() / st_clear_norms
+ *                 (tile-sharded: after st_tile_style_raw)
+ *   diff   C*h*w  the injected layer diff: content + style + deep-dream terms (tile-sharded: the window's blob, zero outside the tile's region)
+ *   norms  3      the c, s, d norms of the blob as that evaluation used them; 0 for a term the blob does not carry
+ * It waits for the stream and copies; nothing in the context changes (no allocation, a captured step graph stays valid).  D and raw_S
+ * live in ONE buffer each for all layers, so the hook refuses (ST_ERR_STATE, the message says why) rather than hand out another layer's
+ * data: any pointer before an evaluation has completed, after the iterate was resized (st_set_input* / st_forward at another size,
+ * st_resample_state), or for a blob that carried no weight; D or raw_S for a blob that was not the style layer evaluated last; raw_S
+ * after an evaluation that knew the style norm; diff where the style term rode on the data-gradient conv above the blob (bf16 flow with
+ * a gradient wanted, ST2_STYLE_FUSE: nothing was written) or after st_backward overwrote it. */
+int st_get_layer_terms(st_ctx* ctx, int index, float* D, float* raw_S, float* diff, float norms[3]);
 
 /* ---- image slots: StyleTransfer.set_input / set_content / set_style (worker.py:191-218) ------- */
 /* preprocess (worker.py:63-66) + upload.  is_u8: 1 = uint8 HWC, 0 = float32 HWC. */

@@ -336,6 +336,7 @@ int ensure_input_buffers(st_ctx* c, int H, int W)
     // the activations are those of the old geometry (blob "data" may be one of the buffers freed below; st_backward sizes its
     // work buffers by the new one): the hooks refuse until the next forward
     c->act.valid_to = -1;
+    if (c->lt.any) { c->lt.any = false; c->lt.resized = true; }      // (st_get_layer_terms: the inject buffers and stmp go below)
     const size_t n3 = (size_t)3 * H * W;
     for (int i = 0; i < 2; ++i) ST_TRY(c->x[i].alloc(n3));
     ST_TRY(c->grad.alloc(n3));
@@ -751,6 +752,7 @@ int st_backward(st_ctx* c, int n, const int* blob_index, const float* const* dif
         if (!c->inject[b]) ST_TRY(c->inject[b].alloc(nb));
         HIP_TRY(hipMemcpyAsync(c->inject[b], diffs[i], nb * sizeof(float), hipMemcpyHostToDevice, c->stream));
         c->inject_roi_zero[b] = 0;
+        if ((int)c->lt.diff.size() == c->nb) c->lt.diff[b] = LT_OVERWRITTEN;
         inj[b] = c->inject[b];
         top = std::max(top, b);
     }

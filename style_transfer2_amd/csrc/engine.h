@@ -146,6 +146,23 @@ struct StyleTerm {
     bool reads32, reads16, missing32;              // copies of the blob the term reads; missing32: it reads the fp32 blob and the forward skipped it
     bool book;                                     // the launches are booked with the profiler (the phases of a tile-sharded iteration are not)
 };
+
+// ------------------------------------------------------------------------------------- layer terms (test hook)
+// What the last objective evaluation left in the work buffers, for st_get_layer_terms.  dbuf (D) and stmp (the unscaled style
+// gradient) are ONE buffer each for all layers: the record says whose data they hold.  Host bookkeeping only -- nothing here is
+// read by a launch.
+enum LtDiff : char { LT_NONE, LT_WRITTEN, LT_RODE_ON_CONV, LT_OVERWRITTEN };
+struct LayerTerms {
+    bool any = false;                              // an evaluation has completed, and the buffers still have its geometry
+    bool resized = false;                          // ... it had, until the iterate was resized
+    int style_blob = -1;                           // the style layer evaluated last: dbuf holds its D
+    int raw_blob = -1;                             // ... and stmp its unscaled gradient (a first evaluation of that layer), else -1
+    std::vector<size_t> n;                         // per blob: elements of its diff in that evaluation (0: the blob carried no weight)
+    std::vector<int> C;
+    std::vector<char> diff;                        // per blob: LtDiff of inject[b]
+    std::vector<char> norm_ok;                     // per blob * 3: the norm was known when the evaluation ended
+    void begin(int nb) { any = resized = false; style_blob = raw_blob = -1; n.assign(nb, 0); C.assign(nb, 0); diff.assign(nb, LT_NONE); norm_ok.assign((size_t)nb * 3, 0); }
+};
 }  // namespace st2e
 
 using namespace st2e;
@@ -197,6 +214,7 @@ struct st_ctx {
     // that conv has run) and, during one objective evaluation, the operands handed to backward_chain
     std::vector<DevBuf<unsigned short>> sfuse_w;
     std::vector<const unsigned short*> sf_in, sf_w;
+    LayerTerms lt;                                 // test hook st_get_layer_terms: whose data dbuf, stmp and the inject buffers hold
     DevBuf<float> conv_scratch;                    // split-K partial sums of Winograd launches
     // hipGraph replay of the steady-state Adam step (launch-bound regime: small images)
     unsigned long long epoch = 0;                  // bumped by every API call that can change what a step launches

@@ -72,6 +72,7 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
     std::vector<const float*> inj(c->nb, nullptr);
     std::fill(c->cnt.begin(), c->cnt.end(), 0);
     c->sf_in.assign(c->nb, nullptr); c->sf_w.assign(c->nb, nullptr);
+    c->lt.begin(c->nb);
     for (const ObjTerm& ot : terms.t) {
         const ActiveLayer& al = ot.al;
         const int b = ot.b, C = ot.C;
@@ -116,8 +117,14 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
                 c->norm_valid[b * 3 + 1] = 1;
                 ProfScope ps(c, P_VECTOR, 0, 4.0 * n * 3);
                 HIP_TRY(launch_scaled_accumulate(c->stmp, c->inject[b], al.sw, nrm + 1, wrote, n, c->stream));
+                c->lt.raw_blob = b;
             }
+            c->lt.style_blob = b;
+            if (c->lt.raw_blob != b) c->lt.raw_blob = -1;
         }
+        c->lt.n[b] = n; c->lt.C[b] = C;
+        c->lt.diff[b] = c->sf_w[b] ? LT_RODE_ON_CONV : LT_WRITTEN;
+        for (int k = 0; k < 3; ++k) c->lt.norm_ok[b * 3 + k] = c->norm_valid[b * 3 + k];
         inj[b] = (c->sf_w[b] && !wrote) ? nullptr : c->inject[b];          // (a fused style term writes nothing into the inject buffer)
     }
 
@@ -163,6 +170,7 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
         ProfScope ps(c, P_FINALIZE, 0, 0);
         HIP_TRY(launch_finalize_trace(t, c->stream));
     }
+    c->lt.any = true;
     return ST_OK;
 }
 
@@ -214,6 +222,42 @@ int st_clear_norms(st_ctx* c)
     if (c) c->epoch++;       // anything but st_step may change what a step launches: captured step graphs are stale
     if (!c) return fail(ST_ERR_ARG, "ctx is NULL");
     std::fill(c->norm_valid.begin(), c->norm_valid.end(), 0);
+    return ST_OK;
+}
+
+// test hook: what the last evaluation left for a blob.  Reads only: no epoch bump (a captured step graph stays valid), no allocation.
+int st_get_layer_terms(st_ctx* c, int index, float* D, float* raw_S, float* diff, float norms[3])
+{
+    if (!c || index < 0 || index >= c->nb) return fail(ST_ERR_ARG, "bad argument");
+    const LayerTerms& lt = c->lt;
+    const char* name = c->blob_names[index].c_str();
+    if (!lt.any)
+        return fail(ST_ERR_STATE, lt.resized ? "the iterate was resized after the last evaluation: its work buffers are gone; evaluate again"
+                                             : "no objective evaluation has completed on this context");
+    if (!lt.n[index]) return fail(ST_ERR_STATE, "blob %d (%s) carried no weight in the last evaluation", index, name);
+    if ((D || raw_S) && lt.style_blob != index) {
+        if (lt.style_blob < 0) return fail(ST_ERR_STATE, "the last evaluation had no style term: no D and no style gradient of blob %d (%s)", index, name);
+        return fail(ST_ERR_STATE, "D and the unscaled style gradient are one buffer each for all layers: they hold those of blob %d (%s), the style layer evaluated last, not of blob %d (%s)",
+                    lt.style_blob, c->blob_names[lt.style_blob].c_str(), index, name);
+    }
+    if (raw_S && lt.raw_blob != index)
+        return fail(ST_ERR_STATE, "the last evaluation of blob %d (%s) knew its style norm and scaled the gradient in the kernel's epilogue: the unscaled one exists only after the first evaluation since reset() / st_clear_norms", index, name);
+    if (diff && lt.diff[index] == LT_RODE_ON_CONV)
+        return fail(ST_ERR_STATE, "the style term of blob %d (%s) rode on the data-gradient conv above it: nothing was written into its diff (ST2_STYLE_FUSE=0, or an evaluation without gradient, materialises it)", index, name);
+    if (diff && lt.diff[index] == LT_OVERWRITTEN)
+        return fail(ST_ERR_STATE, "st_backward has overwritten the diff of blob %d (%s) since the last evaluation", index, name);
+    if (diff && (lt.diff[index] != LT_WRITTEN || !c->inject[index])) return fail(ST_ERR_STATE, "blob %d (%s) has no diff of the last evaluation", index, name);
+    if ((D && !c->dbuf) || (raw_S && !c->stmp)) return fail(ST_ERR_STATE, "internal: the buffer of blob %d (%s) is gone", index, name);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const size_t C = (size_t)lt.C[index], n = lt.n[index];
+    if (D) HIP_TRY(hipMemcpy2D(D, C * sizeof(float), c->dbuf, (size_t)conv_mpad((int)C) * sizeof(float), C * sizeof(float), C, hipMemcpyDeviceToHost));
+    if (raw_S) HIP_TRY(hipMemcpy(raw_S, c->stmp, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (diff) HIP_TRY(hipMemcpy(diff, c->inject[index], n * sizeof(float), hipMemcpyDeviceToHost));
+    if (norms) {
+        HIP_TRY(hipMemcpy(norms, c->norms + index * 3, 3 * sizeof(float), hipMemcpyDeviceToHost));
+        for (int k = 0; k < 3; ++k) if (!lt.norm_ok[index * 3 + k]) norms[k] = 0.f;      // (a term the blob does not carry has no norm)
+    }
     return ST_OK;
 }
 

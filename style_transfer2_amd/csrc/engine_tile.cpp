@@ -137,6 +137,7 @@ int st_tile_forward(st_ctx* c, float** dev_ptr, int* n_floats)
     ST_TRY(tile_begin(c, terms));
     ActSet& a = c->act;
     c->tile.evaluated = false;
+    c->lt.begin(c->nb);
     ST_TRY(ensure_content_features(c));
     ST_TRY(c->tile.p1.reserve(std::max<size_t>(terms.n1, 1)));
     HIP_TRY(hipMemsetAsync(c->tile.p1, 0, std::max<size_t>(terms.n1, 1) * sizeof(float), c->stream));
@@ -194,6 +195,7 @@ int st_tile_losses_finish(st_ctx* c)
     ST_TRY(tile_begin(c, terms));
     ActSet& a = c->act;
     const bool two_step = c->tile.s2_in_p2;
+    if ((int)c->lt.n.size() != c->nb) c->lt.begin(c->nb);      // (st_tile_forward starts the record; a caller out of order gets a fresh one)
     for (const ObjTerm& t : terms.t) {
         const ActiveLayer& al = t.al;
         const int b = t.b, C = t.C;
@@ -221,8 +223,13 @@ int st_tile_losses_finish(st_ctx* c)
                 ST_TRY(c->tile.p3.reserve(6 + kMaxTraceLayers));
                 HIP_TRY(launch_sum_partials(c->s2_part[b], np, c->tile.p3 + 6 + t.k, c->stream));
             }
+            c->lt.style_blob = b;
+            if (c->lt.raw_blob != b) c->lt.raw_blob = -1;
         }
+        c->lt.n[b] = t.n; c->lt.C[b] = C; c->lt.diff[b] = LT_WRITTEN;
+        for (int k = 0; k < 3; ++k) c->lt.norm_ok[b * 3 + k] = c->norm_valid[b * 3 + k];
     }
+    c->lt.any = true;
     return ST_OK;
 }
 
@@ -240,6 +247,7 @@ int st_tile_style_raw(st_ctx* c)
         int np = 0;
         ST_TRY(style_grad(c, a, style_term(c, a, t.b, t.region()), c->stmp, c2, 0, t.al.sw, 0, &np));
         HIP_TRY(launch_sum_partials(c->s2_part[t.b], np, c->tile.p2 + t.k, c->stream));
+        c->lt.style_blob = c->lt.raw_blob = t.b;
     }
     return ST_OK;
 }

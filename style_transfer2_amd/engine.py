@@ -200,6 +200,28 @@ class Engine:
         check(self.lib.st_gram(self._ctx, self._index[name], _ptr(out)))
         return out
 
+    def layer_terms(self, name, want=('D', 'raw_S', 'diff', 'norms')):
+        """Test hook (st_get_layer_terms): what the last objective evaluation left for a blob -- a dict with the entries of `want`:
+        'D' (C, C) = G - G_style as the style-gradient launch read it, 'raw_S' (1, C, h, w) the unscaled style gradient (first
+        evaluation after reset() only), 'diff' (1, C, h, w) the injected layer diff, 'norms' (3,) = c, s, d.  StError where the shared
+        buffers no longer (or never did) hold that blob's data."""
+        unknown = set(want) - {'D', 'raw_S', 'diff', 'norms'}
+        if unknown:
+            raise ValueError('unknown layer term(s) %s' % sorted(unknown))
+        shape = self.blob_shape(name, *self.input_shape())
+        out = {}
+        if 'D' in want:
+            out['D'] = np.empty((shape[0], shape[0]), F32)
+        for k in ('raw_S', 'diff'):
+            if k in want:
+                out[k] = np.empty((1,) + shape, F32)
+        norms = (c_float * 3)()
+        check(self.lib.st_get_layer_terms(self._ctx, self._index[name], _ptr(out.get('D')), _ptr(out.get('raw_S')),
+                                          _ptr(out.get('diff')), norms if 'norms' in want else None))
+        if 'norms' in want:
+            out['norms'] = np.array(norms[:], F32)
+        return out
+
     # -- image slots -------------------------------------------------------------------------------
     def set_input(self, image):
         arr, u8 = _image_arg(image)

@@ -541,3 +541,6 @@ def test_new_entry_points_refuse_null_handles_without_a_gpu():
     assert lib.st_tile_step(None, None) == 2 and lib.st_tile_get_tile(None, None) == 2
     assert lib.st_tile_trace(None, None) == 1
     assert lib.st_vec_div(None, 1.0, None, 0) == 1
+    # the layer-terms hook: bound with the header's six arguments, and a NULL context is an argument error with a message
+    assert 'st_get_layer_terms' in capi.PROTOTYPES and len(capi.PROTOTYPES['st_get_layer_terms'][1]) == 6
+    assert lib.st_get_layer_terms(None, 0, None, None, None, None) == 1 and b'bad argument' in lib.st_last_error()
