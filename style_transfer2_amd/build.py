@@ -25,7 +25,8 @@ SOURCES = (
     ('gram.hip', ()),
     ('passes.hip', ('-ffp-contract=off',)),      # NumPy-like one-rounding-per-operation arithmetic
     ('lbfgs.hip', ('-ffp-contract=off',)),
-    ('color.hip', ('-ffp-contract=off',)),       # luminance emission, colour moments, recolour: the arithmetic of st2.h, one rounding per operation
+    ('color.hip', ('-ffp-contract=off',)),       # colour moments, recolour: the arithmetic of st2.h, one rounding per operation
+    ('emit.hip', ('-ffp-contract=off',)),        # the image handed out (plain, averaged, luminance): NumPy's float32 arithmetic
     ('style16.hip', ()),
     ('gram16.hip', ()),
     ('gram_split.hip', ()),
@@ -40,8 +41,9 @@ SOURCES = (
     ('engine_tile.cpp', ('-x', 'hip')),
     ('engine_comm.cpp', ('-x', 'hip')),
     ('engine_color.cpp', ('-x', 'hip')),
+    ('engine_emit.cpp', ('-x', 'hip')),
 )
-HEADERS = ('st2_kernels.h', 'env.h', 'wave_reduce.h', 'engine.h', 'devbuf.h', 'color_match.h', os.path.join('..', '..', 'include', 'st2.h'))
+HEADERS = ('st2_kernels.h', 'env.h', 'wave_reduce.h', 'engine.h', 'devbuf.h', 'color_match.h', 'emit_plan.h', 'channel_mean.h', os.path.join('..', '..', 'include', 'st2.h'))
 
 
 def _hipcc():

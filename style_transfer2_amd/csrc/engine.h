@@ -425,19 +425,16 @@ int read_trace(st_ctx* c, double* trace, float* loss);
 int lbfgs_alloc(st_ctx* c);
 LbfgsArgs lbfgs_args(st_ctx* c, int apply);
 int lbfgs_clear_history(st_ctx* c, bool gram_form);        // what lbfgs_step and the fused tile step do while c->lb_clear is set
-// iterate averaging: DecayingMean.__call__(x) on the current iterate, and the corrected, deprocessed mean into hwc where it is not NULL
-// (one launch, booked as P_MISC); average_corr: the divisor float(1 - decay ** items) of utils.py:64
-int average_enqueue(st_ctx* c, float* hwc);
-int average_advance(st_ctx* c, float* decay, float* rest, float* corr, int* first);      // items += 1; the scalars of that item's update and image
-float average_corr(const st_ctx* c);
+float average_corr(const st_ctx* c);              // iterate averaging: the divisor float(1 - decay ** items) of utils.py:64
+// ---------------------------------------------------------------------------------------- engine_emit.cpp
+// Emission (emit_plan.h): the image a reader hands out, and DecayingMean.__call__(x) on the current iterate where a step advances the
+// iterate average.  emit_preflight: the plan for `reader` (EmitReader; want_image: st_step's out_hwc), or the plan's refusal as a status
+// and a message -- no HIP call, nothing changes: every reader asks before it enqueues anything.  emit_enqueue: the plan's one launch,
+// booked as P_MISC with the bytes of its streams (plan.book), or nothing; staged_v / staged_cx: the packed (3, h, w) tiles of a tile reader in place
+// of the context's own tensors (NULL: those, at h = H, w = W)
+int emit_preflight(const st_ctx* c, int reader, bool want_image, EmitPlan* plan);
+int emit_enqueue(st_ctx* c, const EmitPlan& plan, float* hwc, const float* staged_v, const float* staged_cx, int h, int w);
 // ---------------------------------------------------------------------------------------- engine_color.cpp
-// luminance emission (st_set_original_colors).  luma_check: ST_ERR_STATE unless content_x exists at the input's size -- no HIP call, nothing
-// changes; luma_enqueue: the image of the current iterate into hwc in place of the deprocess pass, or, under iterate averaging, in place
-// of average_enqueue(c, hwc) with the same update of the mean (one launch, booked as P_MISC); luma_staged: a packed (3, h, w) tile `v` and
-// the matching packed tile `cx` of content_x into hwc, v divided by corr first where corr != 0
-int luma_check(const st_ctx* c);
-int luma_enqueue(st_ctx* c, float* hwc);
-int luma_staged(st_ctx* c, const float* v, const float* cx, float corr, int h, int w, float* hwc);
 // the style image on its way to the forward: refuses (ST_ERR_STATE) what colour matching cannot run on -- before anything is enqueued --
 // then derives the transform where st_set_style_color_match asks for it (waits for the stream) and recolours x (3, H, W) in place
 int style_color_check(const st_ctx* c);

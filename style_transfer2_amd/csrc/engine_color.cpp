@@ -1,45 +1,9 @@
-// The content's colours (include/st2.h): luminance-only emission and the colour-matched style image, on paths the engine already owns --
-// the one interleaving pass that hands an image out, and the device copy of the style image on its way to the forward.
+// The content's colours (include/st2.h): the colour-matched style image, on the device copy of the style image on its way to the forward,
+// and the setters (the luminance-only output is a form of the emission pass, engine_emit.cpp).
 #include "engine.h"
 #include "color_match.h"
 
 namespace st2e {
-// ---- luminance emission -------------------------------------------------------------------------------------------------------
-int luma_check(const st_ctx* c)
-{
-    if (!c->have_content || !c->content_x)
-        return fail(ST_ERR_STATE, "original colours: no content image to take the chroma from (st_set_content, or st_set_original_colors(ctx, 0))");
-    if (c->cH != c->H || c->cW != c->W)
-        return fail(ST_ERR_STATE, "original colours: the content image is %d x %d, the input %d x %d", c->cH, c->cW, c->H, c->W);
-    return ST_OK;
-}
-
-int luma_enqueue(st_ctx* c, float* hwc)
-{
-    const size_t n3 = (size_t)3 * c->H * c->W;
-    EmitLumaArgs a{};
-    a.x = c->x[c->cur]; a.cx = c->content_x; a.hwc = hwc; a.H = c->H; a.W = c->W; a.form = EMIT_PLAIN;
-    double streams = 3;                            // x and the content in, the image out
-    if (c->avg_decay > 0) {                        // average_enqueue's update; the image is the corrected mean's
-        a.form = EMIT_UPDATE; a.mean = c->avg;
-        ST_TRY(average_advance(c, &a.decay, &a.rest, &a.corr, &a.first));
-        streams += a.first ? 1 : 2;
-    }
-    ProfScope ps(c, P_MISC, 0, 4.0 * n3 * streams);
-    HIP_TRY(launch_emit_luma(a, c->stream));
-    return ST_OK;
-}
-
-int luma_staged(st_ctx* c, const float* v, const float* cx, float corr, int h, int w, float* hwc)
-{
-    EmitLumaArgs a{};
-    a.cx = cx; a.hwc = hwc; a.H = h; a.W = w;
-    if (corr != 0.f) { a.form = EMIT_STAGED; a.mean = const_cast<float*>(v); a.corr = corr; }      // (only read in this form)
-    else { a.form = EMIT_PLAIN; a.x = v; }
-    if (launch_emit_luma(a, c->stream) != hipSuccess) return fail(ST_ERR_HIP, "luminance staging launch failed");
-    return ST_OK;
-}
-
 // ---- moments and the style transform --------------------------------------------------------------------------------------------
 // the nine sums of a planar (3, n) device image -> mean, cov; waits for the stream
 static int moments_of(st_ctx* c, const float* x, size_t n, double mean[3], double cov[6])

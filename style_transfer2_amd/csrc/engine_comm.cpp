@@ -417,6 +417,8 @@ int st_tile_step(st_ctx* c, double* trace)
     if (!c || !c->tile.on) return fail(ST_ERR_STATE, "st_tile_configure first");
     if (!comm_ready(c)) return fail(ST_ERR_STATE, "st_comm_init (or st_comm_callbacks) first");
     if (c->opt_kind != ST_OPT_ADAM && c->opt_kind != ST_OPT_LBFGS) return fail(ST_ERR_STATE, "no optimizer: call st_optimizer_reset first");
+    EmitPlan emit;
+    ST_TRY(emit_preflight(c, EMIT_TILE_STEP, false, &emit));
     HIP_TRY(hipSetDevice(c->device));
     const int wh = c->H, ww = c->W;
     struct Unfuse { st_ctx* c; ~Unfuse() { c->tile.fused = false; } } unfuse{c};
@@ -432,7 +434,7 @@ int st_tile_step(st_ctx* c, double* trace)
     }
     // iterate averaging over the whole window, now that this step's x and its refreshed apron are final (every rank then holds, on its
     // apron, the mean its neighbours hold on their tiles)
-    if (c->avg_decay > 0) ST_TRY(average_enqueue(c, nullptr));
+    ST_TRY(emit_enqueue(c, emit, nullptr, nullptr, nullptr, c->H, c->W));
     c->comm.steps += 1;
     return ST_OK;
 }
@@ -450,12 +452,14 @@ int st_tile_set_style(st_ctx* c, const void* hwc, int H, int W, int is_u8, int g
     return st_tile_style_commit(c);
 }
 
-// this rank's tile of a window tensor, packed, then interleaved with the channel means added: deprocess_k, or (corr != 0: the iterate
-// average) the staging form of launch_iterate_average, chw / corr + mean_c -- the arithmetic of the pass that hands out whole images
-static int tile_to_host(st_ctx* c, float* window, float corr, float* out_hwc)
+// this rank's tile of the iterate (EMIT_TILE_X) or of the iterate average (EMIT_TILE_AVERAGE), packed, then through the pass that hands
+// out whole images (emit_enqueue: the same arithmetic)
+static int tile_to_host(st_ctx* c, int reader, float* out_hwc)
 {
-    if (c->orig_colors) ST_TRY(luma_check(c));
+    EmitPlan emit;
+    ST_TRY(emit_preflight(c, reader, true, &emit));
     HIP_TRY(hipSetDevice(c->device));
+    const bool luma = emit.colour == EMIT_LUMA;
     const st_ctx::Tile& t = c->tile;
     const int th = t.ty1 - t.ty0, tw = t.tx1 - t.tx0;
     const size_t n = (size_t)3 * th * tw;
@@ -464,7 +468,7 @@ static int tile_to_host(st_ctx* c, float* window, float corr, float* out_hwc)
         c->comm.tile_chw.reset(); c->comm.tile_hwc.reset();
         ST_TRY(c->comm.tile_chw.alloc(n)); ST_TRY(c->comm.tile_hwc.alloc(n));
     }
-    if (c->orig_colors && n > c->comm.tile_cx.cap()) {
+    if (luma && n > c->comm.tile_cx.cap()) {
         HIP_TRY(hipStreamSynchronize(c->stream));
         ST_TRY(c->comm.tile_cx.alloc(n));
     }
@@ -472,15 +476,10 @@ static int tile_to_host(st_ctx* c, float* window, float corr, float* out_hwc)
     int rc = ST_OK;
     {
         std::vector<int> rect = {t.ty0 - t.wy0, t.tx0 - t.wx0, th, tw};
-        rc = strips(c, window, 3, c->H, c->W, rect, chw, 0);
-        if (rc == ST_OK && c->orig_colors) rc = strips(c, c->content_x, 3, c->H, c->W, rect, c->comm.tile_cx, 0);
+        rc = strips(c, reader == EMIT_TILE_AVERAGE ? c->avg : c->x[c->cur], 3, c->H, c->W, rect, chw, 0);
+        if (rc == ST_OK && luma) rc = strips(c, c->content_x, 3, c->H, c->W, rect, c->comm.tile_cx, 0);      // the window's own content gives the chroma
     }
-    if (rc == ST_OK && c->orig_colors) rc = luma_staged(c, chw, c->comm.tile_cx, corr, th, tw, hwc);      // the window's own content gives the chroma
-    else if (rc == ST_OK && corr != 0.f) {
-        IterateAverageArgs a{};
-        a.mean = chw; a.hwc = hwc; a.H = th; a.W = tw; a.corr = corr;
-        if (launch_iterate_average(a, c->stream) != hipSuccess) rc = fail(ST_ERR_HIP, "iterate average staging launch failed");
-    } else if (rc == ST_OK && launch_deprocess(chw, hwc, th, tw, c->stream) != hipSuccess) rc = fail(ST_ERR_HIP, "deprocess launch failed");
+    if (rc == ST_OK) rc = emit_enqueue(c, emit, hwc, chw, luma ? c->comm.tile_cx.get() : nullptr, th, tw);
     if (rc == ST_OK && hipMemcpyAsync(out_hwc, hwc, n * sizeof(float), hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = fail(ST_ERR_HIP, "tile copy failed");
     if (hipStreamSynchronize(c->stream) != hipSuccess && rc == ST_OK) rc = fail(ST_ERR_HIP, "tile copy failed");
     return rc;
@@ -489,15 +488,13 @@ static int tile_to_host(st_ctx* c, float* window, float corr, float* out_hwc)
 int st_tile_get_tile(st_ctx* c, float* out_hwc)
 {
     if (!c || !c->tile.on || !out_hwc) return fail(ST_ERR_STATE, "st_tile_configure first");
-    return tile_to_host(c, c->x[c->cur], 0.f, out_hwc);
+    return tile_to_host(c, EMIT_TILE_X, out_hwc);
 }
 
 int st_tile_get_tile_average(st_ctx* c, float* out_hwc)
 {
     if (!c || !c->tile.on || !out_hwc) return fail(ST_ERR_STATE, "st_tile_configure first");
-    if (!(c->avg_decay > 0)) return fail(ST_ERR_STATE, "iterate averaging is off: st_set_iterate_average first");
-    if (c->avg_items == 0) return fail(ST_ERR_STATE, "the iterate average is empty: only st_tile_step updates it (the phase-by-phase entry points do not)");
-    return tile_to_host(c, c->avg, average_corr(c), out_hwc);
+    return tile_to_host(c, EMIT_TILE_AVERAGE, out_hwc);
 }
 
 }  // extern "C"

@@ -166,30 +166,6 @@ int step_enqueue(st_ctx* c)
 
 // ---- iterate averaging (utils.DecayingMean, utils.py:49-69, over the iterates) ---------------------------------------------
 float average_corr(const st_ctx* c) { return (float)(1.0 - pow(c->avg_decay, (double)c->avg_items)); }      // utils.py:64, rounded once
-
-// one more item: the scalars of its update and of the image handed out after it (shared with the luminance emission, engine_color.cpp)
-int average_advance(st_ctx* c, float* decay, float* rest, float* corr, int* first)
-{
-    if (c->avg.cap() != (size_t)3 * c->H * c->W) return fail(ST_ERR_STATE, "internal: the iterate average has no buffer of the input's size");
-    *decay = (float)c->avg_decay; *rest = (float)(1.0 - c->avg_decay);        // (1 - decay) in double, then fp32: NumPy with a Python scalar
-    *first = c->avg_items == 0;
-    c->avg_items += 1;
-    *corr = average_corr(c);
-    return ST_OK;
-}
-
-// after an optimizer step: mean = decay * mean + (1 - decay) * x, items += 1; hwc (nullable) takes deprocess(mean / corr).  On the
-// engine's stream, outside the captured step graph.
-int average_enqueue(st_ctx* c, float* hwc)
-{
-    const size_t n3 = (size_t)3 * c->H * c->W;
-    IterateAverageArgs a{};
-    a.x = c->x[c->cur]; a.mean = c->avg; a.hwc = hwc; a.H = c->H; a.W = c->W;
-    ST_TRY(average_advance(c, &a.decay, &a.rest, &a.corr, &a.first));
-    ProfScope ps(c, P_MISC, 0, 4.0 * n3 * (2 + (a.first ? 0 : 1) + (hwc ? 1 : 0)));      // x in, mean in (unless empty) and out, the image
-    HIP_TRY(launch_iterate_average(a, c->stream));
-    return ST_OK;
-}
 }  // namespace st2e
 
 extern "C" {
@@ -297,15 +273,13 @@ int st_step(st_ctx* c, float* out_hwc, double* trace, float* out_loss)
     if (!c) return fail(ST_ERR_ARG, "ctx is NULL");
     if (!c->x[0]) return fail(ST_ERR_STATE, "no input image");
     if (c->pipe.count) return fail(ST_ERR_STATE, "%d pipelined iteration(s) in flight: st_step_end first", c->pipe.count);
-    const bool luma = c->orig_colors && out_hwc;       // luminance emission: refused before anything is enqueued
-    if (luma) ST_TRY(luma_check(c));
+    EmitPlan emit;
+    ST_TRY(emit_preflight(c, EMIT_STEP, out_hwc != nullptr, &emit));       // refused before anything is enqueued
     HIP_TRY(hipSetDevice(c->device));
     ST_TRY(step_enqueue(c));
     // iterate averaging: the update rides on the image pass when an image is wanted, and is a launch of its own otherwise
-    if (luma) ST_TRY(luma_enqueue(c, c->hwc_dev));
-    else if (c->avg_decay > 0) ST_TRY(average_enqueue(c, out_hwc ? c->hwc_dev.get() : nullptr));
+    ST_TRY(emit_enqueue(c, emit, c->hwc_dev, nullptr, nullptr, c->H, c->W));
     if (out_hwc) {
-        if (!luma && !(c->avg_decay > 0)) { ProfScope ps(c, P_MISC, 0, 0); HIP_TRY(launch_deprocess(c->x[c->cur], c->hwc_dev, c->H, c->W, c->stream)); }
         HIP_TRY(hipMemcpyAsync(out_hwc, c->hwc_dev, (size_t)3 * c->H * c->W * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     }
     if (out_hwc || trace || out_loss) return read_trace(c, trace, out_loss);
@@ -321,7 +295,8 @@ int st_step_begin(st_ctx* c)
     if (!c->x[0]) return fail(ST_ERR_STATE, "no input image");
     st_ctx::Pipe& p = c->pipe;
     if (p.count >= 2) return fail(ST_ERR_STATE, "two iterations are already in flight: st_step_end first");
-    if (c->orig_colors) ST_TRY(luma_check(c));
+    EmitPlan emit;
+    ST_TRY(emit_preflight(c, EMIT_STEP_BEGIN, true, &emit));
     HIP_TRY(hipSetDevice(c->device));
     const size_t n3 = (size_t)3 * c->H * c->W;
     if (!p.copy) {
@@ -352,9 +327,7 @@ int st_step_begin(st_ctx* c)
     }
     ST_TRY(step_enqueue(c));
     const int slot = (int)((p.head + p.count) % st_ctx::Pipe::kSlots);
-    if (c->orig_colors) ST_TRY(luma_enqueue(c, p.hwc[slot]));
-    else if (c->avg_decay > 0) ST_TRY(average_enqueue(c, p.hwc[slot]));
-    else { ProfScope ps(c, P_MISC, 0, 0); HIP_TRY(launch_deprocess(c->x[c->cur], p.hwc[slot], c->H, c->W, c->stream)); }
+    ST_TRY(emit_enqueue(c, emit, p.hwc[slot], nullptr, nullptr, c->H, c->W));
     p.tlen[slot] = c->trace_len_last; p.H[slot] = c->H; p.W[slot] = c->W;
     HIP_TRY(hipMemcpyAsync(p.trace_pin[slot], c->trace_dev, p.tlen[slot] * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipEventRecord(p.ready[slot], c->stream));

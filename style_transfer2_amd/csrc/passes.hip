@@ -6,10 +6,11 @@
 //   average pool fwd/bwd        prototxt `pool: AVE`             (Caffe ceil mode, clipped-window divisor)
 //   content / deep-dream terms  worker.py:249-256, 271-277
 //   TV + p-norm + combine + Adam  utils.py:285-304, worker.py:279-297, optimizers.py:20-27
-//   pre / deprocess             worker.py:63-71
+//   preprocess                  worker.py:63-66                  (deprocess and the other images handed out: emit.hip)
 //   trace scalars               worker.py:236-301, utils.py:257-282
 //   BLAS-1 for L-BFGS           utils.py:29-46, optimizers.py:62-108
 #include "st2_kernels.h"
+#include "channel_mean.h"
 #include "wave_reduce.h"
 #include <float.h>
 #include <math.h>
@@ -808,9 +809,7 @@ hipError_t launch_resample(const float* src, float* tmp, float* dst, int planes,
     return hipGetLastError();
 }
 
-// -------------------------------------------------------------------------------- pre / deprocess
-__constant__ float kMean[3] = {123.68f, 116.779f, 103.939f};   // worker.py:34
-
+// -------------------------------------------------------------------------------- preprocess (emit.hip hands images out)
 template <typename T>
 __global__ __launch_bounds__(256) void preprocess_k(const T* __restrict__ hwc, float* __restrict__ nchw, int H, int W)
 {
@@ -822,16 +821,6 @@ __global__ __launch_bounds__(256) void preprocess_k(const T* __restrict__ hwc, f
     }
 }
 
-__global__ __launch_bounds__(256) void deprocess_k(const float* __restrict__ nchw, float* __restrict__ hwc, int H, int W)
-{
-    const size_t plane = (size_t)H * W;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < plane * 3; i += (size_t)gridDim.x * 256) {
-        const int c = (int)(i % 3);
-        const size_t p = i / 3;
-        hwc[i] = nchw[(size_t)c * plane + p] + kMean[c];
-    }
-}
-
 hipError_t launch_preprocess_u8(const uint8_t* hwc, float* nchw, int H, int W, hipStream_t s)
 {
     preprocess_k<uint8_t><<<reduce_grid((size_t)H * W * 3, 1024, 8192), 256, 0, s>>>(hwc, nchw, H, W);
@@ -840,87 +829,6 @@ hipError_t launch_preprocess_u8(const uint8_t* hwc, float* nchw, int H, int W, h
 hipError_t launch_preprocess_f32(const float* hwc, float* nchw, int H, int W, hipStream_t s)
 {
     preprocess_k<float><<<reduce_grid((size_t)H * W * 3, 1024, 8192), 256, 0, s>>>(hwc, nchw, H, W);
-    return hipGetLastError();
-}
-hipError_t launch_deprocess(const float* nchw, float* hwc, int H, int W, hipStream_t s)
-{
-    deprocess_k<<<reduce_grid((size_t)H * W * 3, 1024, 8192), 256, 0, s>>>(nchw, hwc, H, W);
-    return hipGetLastError();
-}
-
-// -------------------------------------------------------------------------------- iterate average
-// DecayingMean (utils.py:49-69) over the iterates, and the image handed out, in one pass over four streams: the planar x and mean are
-// read, mean = decay * mean + rest * x (two products and a sum, NumPy's float32 arithmetic: this file is built with -ffp-contract=off) is
-// written, and, where an image is wanted, hwc = mean / corr + kMean[c] (one IEEE division) goes out interleaved.  UPDATE = false is the
-// staging form: `mean` is only read and divided (a packed tile on its way to the host).  VEC: a thread owns 4 consecutive pixels -- three
-// 16-byte reads of x and of mean, three 16-byte writes of mean, the 12 consecutive floats of hwc as three 16-byte writes; else one pixel.
-template <bool UPDATE, bool VEC>
-__global__ __launch_bounds__(256) void iterate_average_k(const IterateAverageArgs a)
-{
-    const size_t plane = (size_t)a.H * a.W;
-    const size_t n = VEC ? plane / 4 : plane;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        if (VEC) {
-            float4 m[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const size_t at = (size_t)c * plane + i * 4;
-                if (UPDATE) {
-                    const float4 x = *reinterpret_cast<const float4*>(a.x + at);
-                    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (!a.first) o = *reinterpret_cast<const float4*>(a.mean + at);
-                    m[c].x = a.decay * o.x + a.rest * x.x;
-                    m[c].y = a.decay * o.y + a.rest * x.y;
-                    m[c].z = a.decay * o.z + a.rest * x.z;
-                    m[c].w = a.decay * o.w + a.rest * x.w;
-                    *reinterpret_cast<float4*>(a.mean + at) = m[c];
-                } else
-                    m[c] = *reinterpret_cast<const float4*>(a.mean + at);
-            }
-            if (a.hwc) {
-                float r[3][4];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    r[c][0] = __fdiv_rn(m[c].x, a.corr) + kMean[c];
-                    r[c][1] = __fdiv_rn(m[c].y, a.corr) + kMean[c];
-                    r[c][2] = __fdiv_rn(m[c].z, a.corr) + kMean[c];
-                    r[c][3] = __fdiv_rn(m[c].w, a.corr) + kMean[c];
-                }
-                float4* out = reinterpret_cast<float4*>(a.hwc + i * 12);
-                out[0] = make_float4(r[0][0], r[1][0], r[2][0], r[0][1]);
-                out[1] = make_float4(r[1][1], r[2][1], r[0][2], r[1][2]);
-                out[2] = make_float4(r[2][2], r[0][3], r[1][3], r[2][3]);
-            }
-        } else {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const size_t at = (size_t)c * plane + i;
-                float m;
-                if (UPDATE) {
-                    const float o = a.first ? 0.f : a.mean[at];
-                    m = a.decay * o + a.rest * a.x[at];
-                    a.mean[at] = m;
-                } else
-                    m = a.mean[at];
-                if (a.hwc) a.hwc[i * 3 + c] = __fdiv_rn(m, a.corr) + kMean[c];
-            }
-        }
-    }
-}
-
-hipError_t launch_iterate_average(const IterateAverageArgs& a, hipStream_t s)
-{
-    const size_t plane = (size_t)a.H * a.W;
-    if (!plane) return hipSuccess;
-    const bool vec = plane % 4 == 0 && (((uintptr_t)a.x | (uintptr_t)a.mean | (uintptr_t)a.hwc) & 15) == 0;
-    const int grid = reduce_grid(vec ? plane / 4 : plane, 256, 2048);
-    if (a.x) {
-        if (vec) iterate_average_k<true, true><<<grid, 256, 0, s>>>(a);
-        else iterate_average_k<true, false><<<grid, 256, 0, s>>>(a);
-    } else {
-        if (vec) iterate_average_k<false, true><<<grid, 256, 0, s>>>(a);
-        else iterate_average_k<false, false><<<grid, 256, 0, s>>>(a);
-    }
     return hipGetLastError();
 }
 

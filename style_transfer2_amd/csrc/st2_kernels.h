@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "emit_plan.h"
+
 namespace st2 {
 
 constexpr int kMaxPartials = 1024;   // grid cap (= partial-sum slots) of every reducing kernel
@@ -323,24 +325,17 @@ struct ResampleTable { const int* lo; const int* n; const double* k; int kmax; }
 hipError_t launch_resample(const float* src, float* tmp, float* dst, int planes, int h_in, int w_in, int h_out, int w_out,
                            const ResampleTable& tx, const ResampleTable& ty, int clamp0, hipStream_t s);
 
-// pre/deprocess, worker.py:63-71
+// preprocess, worker.py:63-66 (deprocess, worker.py:68-71, is the plain form of the emission below)
 hipError_t launch_preprocess_u8(const uint8_t* hwc, float* nchw, int H, int W, hipStream_t s);
 hipError_t launch_preprocess_f32(const float* hwc, float* nchw, int H, int W, hipStream_t s);
-hipError_t launch_deprocess(const float* nchw, float* hwc, int H, int W, hipStream_t s);
-// The running mean of the iterates (utils.DecayingMean, utils.py:49-69) and the image handed out, in one pass: mean = decay * mean +
-// rest * x in fp32 without contraction (first: the mean is empty and counts as 0, the buffer is not read), and, where hwc is not NULL,
-// hwc = mean / corr + channel mean, interleaved (H, W, 3).  x == NULL: `mean` is only read (a packed (3, H, W) tile being staged).
-// 16-byte accesses on every stream where H * W % 4 == 0 and the three pointers are 16-byte aligned, one pixel per thread otherwise.
-struct IterateAverageArgs { const float* x; float* mean; float* hwc; int H, W; float decay, rest, corr; int first; };
-hipError_t launch_iterate_average(const IterateAverageArgs& a, hipStream_t s);
-
-// The content's colours (color.hip; st2.h has the arithmetic).  Luminance emission: hwc = (cx + channel mean) + luma(v - cx), interleaved,
-// with v = x (EMIT_PLAIN; a packed tile being staged is the same form), v = mean / corr after the update of launch_iterate_average
-// (EMIT_UPDATE: x and mean in, mean out) or v = mean / corr of a mean that is only read (EMIT_STAGED).  16-byte accesses on every
-// stream where H * W % 4 == 0 and every pointer is 16-byte aligned, one pixel per thread otherwise; the grid of launch_iterate_average.
-enum { EMIT_PLAIN = 0, EMIT_UPDATE = 1, EMIT_STAGED = 2 };
-struct EmitLumaArgs { const float* x; float* mean; const float* cx; float* hwc; int H, W; float decay, rest, corr; int first, form; };
-hipError_t launch_emit_luma(const EmitLumaArgs& a, hipStream_t s);
+// Emission (emit.hip; emit_plan.h decides the form): the image hwc (H, W, 3) of v, where v is x (EMIT_X; a packed tile being staged is the
+// same form), mean / corr after mean = decay * mean + rest * x in fp32 without contraction (EMIT_MEAN_UPDATED: x and mean in, mean out;
+// first: the mean is empty and counts as 0, the buffer is not read; hwc == NULL: the update-only launch, which writes nothing but the mean)
+// or mean / corr of a mean that is only read (EMIT_MEAN_READ).  hwc = v + channel mean (EMIT_ADD_MEAN), or (cx + channel mean) +
+// luma(v - cx) (EMIT_LUMA; st2.h has the arithmetic).  Pointers a form does not use are NULL.  16-byte accesses on every stream where
+// H * W % 4 == 0 and every non-null pointer is 16-byte aligned, one pixel per thread otherwise; at most 2048 workgroups of 256 threads.
+struct EmitArgs { int source, colour; const float* x; float* mean; const float* cx; float* hwc; int H, W; float decay, rest, corr; int first; };
+hipError_t launch_emit(const EmitArgs& a, hipStream_t s);
 // The nine sums {p_R, p_G, p_B, p_R p_R, p_R p_G, p_R p_B, p_G p_G, p_G p_B, p_B p_B} over the n pixels of a planar (3, n) image, in
 // double throughout: partials is [9][kMomentBlocks] scratch, out takes the 9 sums (second stage: one thread per sum, workgroups in order)
 constexpr int kMomentSums = 9;

@@ -1,10 +1,10 @@
 """The content's colours on the real engine (``pytest -m gpu``): luminance-only output (st_set_original_colors) and the colour-matched
-style image (st_set_style_color_match / st_set_style_transform).  The kernels of csrc/color.hip are held BIT FOR BIT to the NumPy float32
-restatements in tests/color_oracle.py (emission fed with get_input_nchw() and get_content_nchw(); recolour fed with the engine's A, b),
+style image (st_set_style_color_match / st_set_style_transform).  The luminance forms of csrc/emit.hip and the kernels of csrc/color.hip
+are held BIT FOR BIT to the NumPy float32 restatements in tests/color_oracle.py (emission fed with get_input_nchw() and get_content_nchw(); recolour fed with the engine's A, b),
 the moments to float64 NumPy within the bound of a double summation, the transform to the float64 oracle within 1 ulp of fp32.
 
 Sizes: 16 x 32 (plane a multiple of 4: the 16-byte path), 18 x 34 (plane a multiple of 4, width not: the 16-byte path across row ends),
-17 x 33 (odd plane: the one-pixel-per-thread path).  emit_luma_k is launched on the grid of iterate_average_k, at most 2048 workgroups of
+17 x 33 (odd plane: the one-pixel-per-thread path).  emit_k (csrc/emit.hip) is launched on at most 2048 workgroups of
 256 threads: a thread strides on to further pixels from 2048 * 256 = 524288 pixels on the one-pixel path -- 725 x 725 = 525625, odd, is the
 smallest square beyond it -- and from four times as many on the 16-byte path -- 1450 x 1448 = 2099600 (a multiple of 4) against 2097152.
 image_moments_k runs at most 256 workgroups of 256 threads, one pixel per thread and pass: 257 x 256 pixels exceed one pass.

@@ -6,14 +6,15 @@ contract (W untimed steps, then blocks of exactly K steps bracketed by device sy
 
     resident    step(want_image=False): nothing is read back; mode on adds one launch per step (x, mean in; mean out)
     pipelined   step_begin / step_end with one iteration ahead, as the worker loop runs: every iterate crosses to pinned host
-                memory; mode on REPLACES the deprocess launch (x, mean in; mean, image out)
+                memory; mode on makes the emission launch (emit_k) update the mean on the way (x, mean in; mean, image out)
 
     python tools/bench_average.py
     python tools/bench_average.py --tree ../parent-checkout      # the same blocks on another (built) checkout of the project, e.g. the
                                                                  # parent commit; an engine without the mode runs the off-blocks only
 One JSON line: median it/s and the spread (min, max) of the blocks per loop and mode, and, from st_profile_read over one more block
-of profiled steps per loop (events around every launch: not the timed run), the mean duration of the `misc` launch of a step -- the new
-pass with the mode on, the deprocess pass of the pipelined loop with it off -- and the GB/s of its algorithmic traffic."""
+of profiled steps per loop (events around every launch: not the timed run), the mean duration of the `misc` launch of a step -- the
+averaging forms of emit_k with the mode on, its plain form in the pipelined loop with it off -- and the GB/s of its algorithmic traffic where
+the launch books it (the plain form of a step is booked without bytes: tests/golden/route_fingerprints.json records it so)."""
 import argparse
 import json
 import os

@@ -6,14 +6,15 @@ contract (W untimed steps, then blocks of exactly K steps bracketed by device sy
 
     resident    step(want_image=False): nothing is read back, so no image is emitted and the mode launches nothing: the control
     pipelined   step_begin / step_end with one iteration ahead, as the worker loop runs: every iterate crosses to pinned host
-                memory; mode on REPLACES the deprocess launch by emit_luma_k (x, content in; image out)
+                memory; mode on makes the emission launch (emit_k) the luminance form (x, content in; image out) instead of the plain one
 
     python tools/bench_colors.py
     python tools/bench_colors.py --tree ../parent-checkout --modes off     # the same blocks on another (built) checkout of the project,
                                                                            # e.g. the parent commit, which has no such mode
 One JSON line: median it/s and the spread (min, max) of the blocks per loop and mode, and, from st_profile_read over one more block
-of profiled steps per loop (events around every launch: not the timed run), the mean duration of the `misc` launch of a step -- emit_luma_k
-with the mode on, deprocess_k with it off -- and the GB/s of its algorithmic traffic where the launch books it."""
+of profiled steps per loop (events around every launch: not the timed run), the mean duration of the `misc` launch of a step -- emit_k's
+luminance form with the mode on, its plain form with it off -- and the GB/s of its algorithmic traffic where the launch books it (the plain
+form of a step is booked without bytes: tests/golden/route_fingerprints.json records it so)."""
 import argparse
 import json
 import os

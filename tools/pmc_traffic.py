@@ -32,7 +32,8 @@ LOAD_WIDTH = (
     ('pack_act16_k', 4),
     ('lbfgs_', 16),
     ('scaled_accumulate_k', 4), ('vec_', 4), ('lincomb_k', 4), ('strip_copy_k', 4),
-    ('preprocess_k', 4), ('deprocess_k', 4), ('resample_', 4), ('clamp0_copy_k', 4),
+    ('preprocess_k', 4), ('emit_k<0, 0, true>', 16), ('emit_k<0, 0, false>', 4),       # (emission, plain form: x in, image out)
+    ('resample_', 4), ('clamp0_copy_k', 4),
     ('__amd_rocclr_copyBuffer', 16), ('__amd_rocclr_fillBuffer', 16),
 )
 
