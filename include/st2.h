@@ -145,7 +145,7 @@ int st_input_shape(st_ctx* ctx, int* H, int* W);
 int st_set_weights(st_ctx* ctx, int n_rows, const int* blob_index, const float* content,
                    const float* style, const float* deepdream, const double params[4]);
 int st_clear_norms(st_ctx* ctx);                          /* the `norms` half of reset() */
-/* number of trace scalars an evaluation produces: 6 per active layer + 8 */
+/* number of trace scalars an evaluation produces: 6 per active layer + 8 (+ 2 while st_set_laplacian is on) */
 int st_trace_len(st_ctx* ctx);
 /* evaluates opfunc at the current input; out_grad (3,H,W) may be NULL (return_grad=False) */
 int st_opfunc(st_ctx* ctx, float* out_loss, float* out_grad, double* trace);
@@ -248,6 +248,39 @@ int st_get_color_modes(st_ctx* ctx, int* original_colors, int* style_match, floa
 int st_set_style_nchw(st_ctx* ctx, const float* x, int H, int W);
 /* Test hook: the preprocessed, recoloured image (3,H,W) exactly as st_set_style would forward it under the modes in force. */
 int st_style_recolor(st_ctx* ctx, const void* hwc, int H, int W, int is_u8, float* out_nchw);
+/* ---- the Laplacian-steered content term (Li, Xu, Nie, Liu: "Laplacian-Steered Neural Style Transfer", ACM MM 2017) ----------------
+ * An image-space term like TV and the p-norm; no reference counterpart, this text is the definition.  With u = x / 255 and uc = cx / 255
+ * (x, cx: the preprocessed planar iterate and content image) a level is a pool size p in {1, 2, 4, 8, 16, 32} and a finite non-zero
+ * weight w; at most three levels, with distinct p.  Per level and channel:
+ *   P(u)[i, j]   the mean of u over the window [i p, (i + 1) p) x [j p, (j + 1) p) clipped to the image, divided by the clipped window's
+ *                pixel count (Caffe's AVE rule); ceil(H / p) x ceil(W / p) cells; p = 1: the identity
+ *   D(q)[i, j]   sum of q[i, j] - q[n] over those of the four neighbours n that exist (the graph Laplacian of the grid: a constant gives
+ *                0, nothing wraps, D is symmetric, a 1 x 1 grid gives 0)
+ *   E = D(P(u)) - T with the target T = D(P(uc));  loss = w * sum E^2 over channels and cells
+ *   g_lap[c, y, x] = sum over levels of w * 2 * D(E)[c, y / p, x / p] / count(y / p, x / p), the derivative with respect to u, added to
+ *                the image gradient as it is: grad = ((scd + tv_w g_tv) + p_w g_p) + g_lap, one fp32 value per pixel, added last
+ * fp32 arithmetic, one rounding per operation: u = x / 255 (IEEE division); a window's sum from the sums of its four quarters as
+ * (a + b) + (c + d), down to single pixels, pixels outside the image counting 0; one IEEE division by the count; D accumulates
+ * q - q[n] from 0 in the order up, down, left, right; E = D - T; a level's term of g_lap is (w * (2 * D(E))) / count, the levels are
+ * added in their order from 0.  Sums of E^2 and g_lap^2 are taken in double per thread, fp32 per workgroup, double across workgroups.
+ * The trace gains two scalars while the term is on: its image part is [scd_loss, t_loss, p_loss, l_loss, scd_grad, tv_grad, p_grad,
+ * l_grad, loss, grad] with l_loss = sum over levels, in their order, of w * float(sum E^2), added to loss after p_loss, and
+ * l_grad = sqrt(float(sum g_lap^2 / (3 H W))).  With the term off the trace is what it was.
+ *
+ * st_set_laplacian: n_levels = 0 is off, the default: the buffers are freed and every path launches what it launched before.
+ * ST_ERR_ARG: a pool size outside the set, two levels with one pool size, more than three levels, a zero, NaN or infinite weight.
+ * ST_ERR_STATE: while a pipelined iteration is in flight; with levels on a tile-configured context (st_tile_configure refuses a
+ * context with the term on).  The buffers are allocated first: when that fails nothing has changed.  The targets are taken here when a
+ * content image of the input's size exists, and again before the next evaluation whenever the content image (st_set_content*,
+ * st_resample_content) or the input's size changed since.  An evaluation (st_opfunc, st_step, st_step_begin) with the term on returns
+ * ST_ERR_STATE without a content image or with one of another size than the input, before anything is enqueued. */
+int st_set_laplacian(st_ctx* ctx, int n_levels, const int* pool, const double* weight);
+/* the levels in force; pool / weight take n_levels entries (room for 3); any pointer may be NULL */
+int st_get_laplacian(st_ctx* ctx, int* n_levels, int* pool, double* weight);
+/* Test hook, reads only: T (3, hp, wp) and E (3, hp, wp) of `level` (an index into the levels in force) from the last evaluation, and
+ * the summed g_lap (3, H, W), the same at every level index.  Any pointer may be NULL.  ST_ERR_STATE, the message saying why: before an
+ * evaluation with the term on, after the input was resized, and for grad_nchw after an evaluation without a gradient. */
+int st_get_laplacian_terms(st_ctx* ctx, int level, float* target, float* diff, float* grad_nchw);
 /* Steps so far that ran as a hipGraph replay.  Opt-in (environment ST2_GRAPH=1; ST2_GRAPH_MAX_PX=<edge>, default 768):
  * steady-state Adam steps are captured once per ping-pong parity and replayed, bit-identical to plain launches.  Measured
  * on MI355X it is no faster (the step is bound by the dependent kernels' execution latency), hence off by default. */

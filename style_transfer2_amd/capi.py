@@ -92,6 +92,9 @@ PROTOTYPES = {
     'st_get_color_modes': (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_float), POINTER(c_float)]),
     'st_set_style_nchw': (c_int, [c_void_p, c_void_p, c_int, c_int]),
     'st_style_recolor': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    'st_set_laplacian': (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_double)]),
+    'st_get_laplacian': (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_double)]),
+    'st_get_laplacian_terms': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     'st_graph_replays':(c_int, [c_void_p, POINTER(c_longlong)]),
     'st_live_bytes': (c_int, [POINTER(c_longlong), POINTER(c_longlong)]),
     'st_lbfgs_inv_hv': (c_int, [c_void_p, c_int, POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_void_p]),

@@ -38,7 +38,9 @@ int fail(int code, const char* fmt, ...);
 enum ProfClass { P_CONV_FWD, P_CONV_DGRAD, P_POOL_FWD, P_POOL_BWD, P_GRAM, P_GRAM_REDUCE, P_STYLE_GRAD,
                  P_LAYER_ELEM, P_IMAGE_PASS, P_FINALIZE, P_VECTOR, P_MISC, P_CONV_FWD_WINO, P_CONV_DGRAD_WINO,
                  P_CONV_FWD_BF16, P_CONV_DGRAD_BF16, P_COMM, P_GRAM_BF16, P_STYLE_GRAD_BF16, P_CONV_FWD_WSPLIT, P_CONV_DGRAD_WSPLIT, P_STYLE_FUSED_BF16,
-                 P_AVEPOOL_FWD, P_AVEPOOL_BWD, P_GRAM_SPLIT, P_STYLE_GRAD_SPLIT, P_AVEPOOL_BWD_MAP16, P_COUNT };
+                 P_AVEPOOL_FWD, P_AVEPOOL_BWD, P_GRAM_SPLIT, P_STYLE_GRAD_SPLIT, P_AVEPOOL_BWD_MAP16,
+                 P_LAP_POOL, P_LAP_STENCIL, P_LAP_GRAD,      // the launches of the Laplacian term (laplacian.hip), the targets' included
+                 P_COUNT };
 extern const char* const kProfNames[P_COUNT];
 struct ProfRec { int cls; hipEvent_t a, b; double flops, bytes; };
 
@@ -286,6 +288,20 @@ struct st_ctx {
     int style_match = 0;                           // 0 off, 1 st_set_style_color_match (derive per style image), 2 st_set_style_transform (given)
     float xf_A[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, xf_b[3] = {0, 0, 0};      // the style transform given, or the one last derived and applied
     DevBuf<double> mom_part, mom_out;              // image_moments_k's per-workgroup partial sums and the nine sums
+    // the Laplacian-steered content term (st_set_laplacian; engine_laplacian.cpp, laplacian_plan.h)
+    struct Lap {
+        int n = 0;                                 // levels; 0: off, and every buffer below is empty
+        int pool[kLapMaxLevels] = {0, 0, 0};
+        double weight[kLapMaxLevels] = {0, 0, 0};
+        LapPlan plan{};                            // of the geometry the buffers were sized for (plan.n == 0: none yet)
+        DevBuf<float> q, t, e;                     // per level, back to back (LapLevel::off): pooled iterate / content, targets T, differences E
+        DevBuf<float> g;                           // g_lap, (3, H, W)
+        DevBuf<float> part;                        // kLapPartRows * kMaxPartials
+        bool targets_ok = false;                   // t holds D(P(content_x / 255)) of the current content image at the plan's size
+        int cnt_e = 0, cnt_g = 0;                  // partial counts of the last evaluation
+        bool evaluated = false, have_grad = false; // e (and g) hold the last evaluation's
+        bool resized = false;                      // ... they did, until the input was resized
+    } lap;
     // tile-sharded mode (BASELINE config 5): this context holds ONE window of a larger image
     struct Tile : TileGeom {
         bool on = false;
@@ -439,6 +455,14 @@ int emit_enqueue(st_ctx* c, const EmitPlan& plan, float* hwc, const float* stage
 // then derives the transform where st_set_style_color_match asks for it (waits for the stream) and recolours x (3, H, W) in place
 int style_color_check(const st_ctx* c);
 int style_recolor_enqueue(st_ctx* c, float* x, int H, int W);
+// ---------------------------------------------------------------------------------------- engine_laplacian.cpp
+// The Laplacian term of an evaluation.  lap_preflight: the refusals (no content image, one of another size than the input), ST_OK with
+// the term off -- no HIP call, nothing changes: every evaluation asks before it enqueues anything.  lap_forward: buffers of the input's
+// size, the targets where the content or the size changed since they were taken, then pool and stencil on x.  lap_backward: g_lap
+int lap_preflight(const st_ctx* c);
+int lap_forward(st_ctx* c, const float* x);
+int lap_backward(st_ctx* c);
+void lap_input_resized(st_ctx* c);                // the input has a new size: the term's buffers are those of the old one
 // ---------------------------------------------------------------------------------------- engine_tile.cpp
 // pack (mode 0) / unpack (1 assign, 2 add) the rectangles (y0, x0, h, w each) of a (C, h, w) tensor; checks them against it; enqueues only
 int strips(st_ctx* c, float* tensor, int C, int h, int w, const std::vector<int>& rects, float* buf, int mode);

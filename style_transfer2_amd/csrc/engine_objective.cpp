@@ -55,6 +55,7 @@ ImagePassArgs image_pass_args(const st_ctx* c, const float* x, const float* scd,
 int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, bool adam, float* x_next)
 {
     if (!c->x[0]) return fail(ST_ERR_STATE, "no input image");
+    ST_TRY(lap_preflight(c));
     ST_TRY(act_ensure(c, c->act, c->H, c->W));
     ActSet& a = c->act;
     ObjTerms terms;
@@ -140,11 +141,19 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
         }
     }
 
+    // the Laplacian term (st_set_laplacian): E per level and its sums; with a gradient, g_lap for the image pass to add after p_w g_p
+    const bool lap = c->lap.n > 0;
+    if (lap) {
+        ST_TRY(lap_forward(c, x));
+        if (want_grad) ST_TRY(lap_backward(c));
+    }
+
     {
         const ImagePassArgs ip = image_pass_args(c, x, scd, want_grad ? grad_out : nullptr, adam, x_next);
+        const float* g_lap = lap && want_grad ? c->lap.g.get() : nullptr;
         const double n3 = 3.0 * c->H * c->W;
-        ProfScope ps(c, P_IMAGE_PASS, 0, 4.0 * n3 * (adam ? 7 : 3));
-        HIP_TRY(launch_image_pass(ip, &c->image_cnt, c->stream));
+        ProfScope ps(c, P_IMAGE_PASS, 0, 4.0 * n3 * ((adam ? 7 : 3) + (g_lap ? 1 : 0)));
+        HIP_TRY(launch_image_pass(ip, &c->image_cnt, c->stream, g_lap));
     }
 
     {
@@ -166,9 +175,16 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
         t.tv_w = c->tv_w; t.p_w = c->p_w; t.p_pow = c->p_pow; t.have_grad = want_grad;
         t.out = c->trace_dev;
         t.sums = c->trace_sums;
-        c->trace_len_last = t.n_layers * 6 + 8;
+        c->trace_len_last = t.n_layers * 6 + 8 + (lap ? 2 : 0);
         ProfScope ps(c, P_FINALIZE, 0, 0);
         HIP_TRY(launch_finalize_trace(t, c->stream));
+        if (lap) {                // l_loss and l_grad join the image part of the trace
+            TraceLapArgs tl{};
+            tl.levels = c->lap.n; tl.part = c->lap.part; tl.count_e = c->lap.cnt_e; tl.count_g = want_grad ? c->lap.cnt_g : 0;
+            for (int l = 0; l < c->lap.n; ++l) tl.w[l] = c->lap.plan.lv[l].w;
+            tl.image_n = t.image_n; tl.have_grad = want_grad; tl.image_out = c->trace_dev + t.n_layers * 6;
+            HIP_TRY(launch_trace_lap(tl, c->stream));
+        }
     }
     c->lt.any = true;
     return ST_OK;
@@ -261,12 +277,14 @@ int st_get_layer_terms(st_ctx* c, int index, float* D, float* raw_S, float* diff
     return ST_OK;
 }
 
-int st_trace_len(st_ctx* c) { return c ? (int)c->active.size() * 6 + 8 : 0; }
+int st_trace_len(st_ctx* c) { return c ? (int)c->active.size() * 6 + 8 + (c->lap.n ? 2 : 0) : 0; }
 
 int st_opfunc(st_ctx* c, float* out_loss, float* out_grad, double* trace)
 {
     if (c) c->epoch++;       // anything but st_step may change what a step launches: captured step graphs are stale
     if (!c) return fail(ST_ERR_ARG, "ctx is NULL");
+    if (!c->x[0]) return fail(ST_ERR_STATE, "no input image");
+    ST_TRY(lap_preflight(c));                                 // refused before anything is enqueued
     HIP_TRY(hipSetDevice(c->device));
     ST_TRY(eval_objective(c, c->x[c->cur], out_grad != nullptr, c->grad, false, nullptr));
     if (out_grad) HIP_TRY(hipMemcpyAsync(out_grad, c->grad, (size_t)3 * c->H * c->W * sizeof(float), hipMemcpyDeviceToHost, c->stream));

@@ -275,6 +275,7 @@ int st_step(st_ctx* c, float* out_hwc, double* trace, float* out_loss)
     if (c->pipe.count) return fail(ST_ERR_STATE, "%d pipelined iteration(s) in flight: st_step_end first", c->pipe.count);
     EmitPlan emit;
     ST_TRY(emit_preflight(c, EMIT_STEP, out_hwc != nullptr, &emit));       // refused before anything is enqueued
+    ST_TRY(lap_preflight(c));
     HIP_TRY(hipSetDevice(c->device));
     ST_TRY(step_enqueue(c));
     // iterate averaging: the update rides on the image pass when an image is wanted, and is a launch of its own otherwise
@@ -297,6 +298,7 @@ int st_step_begin(st_ctx* c)
     if (p.count >= 2) return fail(ST_ERR_STATE, "two iterations are already in flight: st_step_end first");
     EmitPlan emit;
     ST_TRY(emit_preflight(c, EMIT_STEP_BEGIN, true, &emit));
+    ST_TRY(lap_preflight(c));
     HIP_TRY(hipSetDevice(c->device));
     const size_t n3 = (size_t)3 * c->H * c->W;
     if (!p.copy) {
@@ -304,7 +306,7 @@ int st_step_begin(st_ctx* c)
         for (int i = 0; i < st_ctx::Pipe::kSlots; ++i) {
             HIP_TRY(hipEventCreateWithFlags(&p.ready[i], hipEventDisableTiming));
             HIP_TRY(hipEventCreateWithFlags(&p.done[i], hipEventDisableTiming));
-            ST_TRY(p.trace_pin[i].alloc(kMaxTraceLayers * 6 + 8));
+            ST_TRY(p.trace_pin[i].alloc(kMaxTraceLayers * 6 + 8 + 2));
         }
     }
     p.begins += 1;

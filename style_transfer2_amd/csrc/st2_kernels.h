@@ -6,10 +6,12 @@
 #include <stdint.h>
 
 #include "emit_plan.h"
+#include "laplacian_plan.h"
 
 namespace st2 {
 
 constexpr int kMaxPartials = 1024;   // grid cap (= partial-sum slots) of every reducing kernel
+static_assert(kLapMaxBlocks == kMaxPartials, "laplacian_plan.h sizes its partial-sum rows like every reducing kernel");
 constexpr int kConvCC = 4;           // K granularity of the packed conv weights (staged chunk = 4 or 8)
 constexpr int kCoutQuantum = 64;     // conv weights are zero-padded to a multiple of this many outputs
 
@@ -303,7 +305,9 @@ struct ImagePassArgs {
     const float* dyn = nullptr;   // optional device {corr1, corr2, step} overriding the by-value ones (hipGraph replays)
 };
 hipError_t launch_set_scalars3(float* dst, float a, float b, float c, hipStream_t s);
-hipError_t launch_image_pass(const ImagePassArgs& a, int* n_partial, hipStream_t s);
+// lap: optional g_lap (3,H,W) of the Laplacian term (laplacian.hip), added after p_w g_p -- image_pass_lap_k runs instead of image_pass_k,
+// whose arguments and instruction stream stay what they are
+hipError_t launch_image_pass(const ImagePassArgs& a, int* n_partial, hipStream_t s, const float* lap = nullptr);
 // Tile-sharded variant: the tile [ty, ty+th) x [tx, tx+tw) of a window image of pitch ww; neighbours outside
 // the tile come from `ring` ([3][th+2][tw+2], the periodic-wrap neighbourhood gathered from the owners).
 struct ImageTileArgs {
@@ -346,6 +350,21 @@ struct RecolorArgs { float* x; size_t n; float A[9], b[3]; };
 hipError_t launch_recolor(const RecolorArgs& a, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
+// Laplacian-steered content term (laplacian.hip; laplacian_plan.h has the geometry and the grids).  Per level l: pool size 1 << shift[l],
+// hp[l] x wp[l] cells, its (3, hp, wp) block at off[l] floats in each of the pooled (q), target (t) and difference (e) buffers.
+// ------------------------------------------------------------------------------------------
+struct LapPoolArgs { const float* x; float* q; int H, W, n, max_shift, tiles_y, tiles_x; int shift[kLapMaxLevels], hp[kLapMaxLevels], wp[kLapMaxLevels]; size_t off[kLapMaxLevels]; };
+// q = mean of x / 255 over each cell, for every level, in one read of x; 16-byte loads where W % 4 == 0 and x is 16-byte aligned
+hipError_t launch_lap_pool(const LapPoolArgs& a, int grid, hipStream_t s);
+// e == NULL: t = D(q) (the targets); else e = D(q) - t and part[l][block] = the workgroup's sum of e^2 (rows of kLapMaxBlocks; `grid` slots each)
+struct LapStencilArgs { const float* q; float* t; float* e; float* part; int n; int hp[kLapMaxLevels], wp[kLapMaxLevels]; size_t off[kLapMaxLevels]; };
+hipError_t launch_lap_stencil(const LapStencilArgs& a, int grid, hipStream_t s);
+// g[c, y, x] = sum over levels of (w * (2 * D(e)[c, y / p, x / p])) / count, part[block] = the workgroup's sum of g^2; 16-byte stores
+// where W % 4 == 0 and g is aligned (grid_vec workgroups), one pixel per thread otherwise (grid)
+struct LapGradArgs { const float* e; float* g; float* part; int H, W, n; int shift[kLapMaxLevels], hp[kLapMaxLevels], wp[kLapMaxLevels]; size_t off[kLapMaxLevels]; float w[kLapMaxLevels]; };
+hipError_t launch_lap_grad(const LapGradArgs& a, int grid, int grid_vec, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------
 // trace finalisation: one tiny kernel turns the partial sums of an opfunc into the trace scalars
 // ------------------------------------------------------------------------------------------
 constexpr int kMaxTraceLayers = 24;
@@ -372,6 +391,12 @@ struct TraceArgs {
     double* sums;                // scratch: n_layers*6 + 6 doubles
 };
 hipError_t launch_finalize_trace(const TraceArgs& a, hipStream_t s);
+// The Laplacian term's part of the trace (laplacian.hip), after launch_finalize_trace on the same `out`: the image part [scd_loss, t_loss,
+// p_loss, scd_grad, tv_grad, p_grad, loss, grad] becomes [scd_loss, t_loss, p_loss, l_loss, scd_grad, tv_grad, p_grad, l_grad,
+// loss + l_loss, grad] with l_loss = sum over levels, in their order, of w * float(sum E^2) and l_grad = sqrt(float(sum g_lap^2 /
+// image_n)) (0 without a gradient).  part: rows of kLapMaxBlocks partials -- sum E^2 per level (count_e each), then sum g_lap^2 (count_g)
+struct TraceLapArgs { int levels; const float* part; int count_e, count_g; float w[kLapMaxLevels]; double image_n; int have_grad; float* image_out; };
+hipError_t launch_trace_lap(const TraceLapArgs& a, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
 // Fixed-step L-BFGS as a device-resident state machine (lbfgs.hip), optimizers.py:49-125, utils.py:29-46

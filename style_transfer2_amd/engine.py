@@ -483,6 +483,40 @@ class Engine:
         check(self.lib.st_get_color_modes(self._ctx, byref(oc), byref(sm), A.ctypes.data_as(POINTER(c_float)), b.ctypes.data_as(POINTER(c_float))))
         return bool(oc.value), sm.value, A.reshape(3, 3), b
 
+    # -- the Laplacian-steered content term (st2.h: st_set_laplacian) ---------------------------------------------------
+    def set_laplacian(self, levels):
+        """levels: a sequence of (pool, weight) pairs -- at most three, pool sizes distinct and from {1, 2, 4, 8, 16, 32}, weights finite
+        and non-zero; empty or None turns the term off (the default).  While on, every evaluation adds sum over levels of
+        w * sum (D(P(x / 255)) - D(P(content / 255))) ** 2 to the loss and its gradient to the image gradient, and the trace has two more
+        scalars.  Refused while a pipelined iteration is in flight and on a tile-configured context."""
+        levels = [tuple(lv) for lv in (levels or ())]
+        if any(len(lv) != 2 for lv in levels):
+            raise ValueError('a Laplacian level is a (pool, weight) pair')
+        n = len(levels)
+        pool = (c_int * max(n, 1))(*[int(p) for p, _ in levels])
+        weight = (c_double * max(n, 1))(*[float(w) for _, w in levels])
+        check(self.lib.st_set_laplacian(self._ctx, n, pool, weight))
+
+    def laplacian(self):
+        """The levels in force as a list of (pool, weight) pairs; empty: the term is off."""
+        n, pool, weight = c_int(), (c_int * 3)(), (c_double * 3)()
+        check(self.lib.st_get_laplacian(self._ctx, byref(n), pool, weight))
+        return [(int(pool[i]), float(weight[i])) for i in range(n.value)]
+
+    def laplacian_terms(self, level, want_grad=True):
+        """Test hook: (T, E, g_lap) of the last evaluation -- the target and the difference of `level` (an index into laplacian()), each
+        (3, hp, wp), and the summed gradient term (1, 3, H, W), None when want_grad is False."""
+        levels = self.laplacian()
+        h, w = self.input_shape()
+        if not 0 <= level < max(len(levels), 1):
+            raise ValueError('level %d of %d' % (level, len(levels)))
+        p = levels[level][0] if levels else 1
+        hp, wp = -(-h // p), -(-w // p)
+        target, diff = np.empty((3, hp, wp), F32), np.empty((3, hp, wp), F32)
+        grad = np.empty((1, 3, h, w), F32) if want_grad else None
+        check(self.lib.st_get_laplacian_terms(self._ctx, level, _ptr(target), _ptr(diff), _ptr(grad)))
+        return target, diff, grad
+
     def set_style_nchw(self, x):
         """set_style for an already-preprocessed (1, 3, H, W) image; no colour transform is applied."""
         x = np.ascontiguousarray(x, F32)

@@ -39,14 +39,17 @@ def load_rgb(path):
 
 def run_job(transfer, content, style, iterations, size=None, style_size=None, optimizer='adam', step_size=None,
             weights=None, params=None, init=None, seed=0, callback=None, iterate_average=None, original_colors=None,
-            match_style_colors=None):
+            match_style_colors=None, laplacian=None):
     """One whole stylisation: content/style are PIL images or HxWx3 arrays.  Returns the final HxWx3 float32
     image.  Mirrors app.init_arrays + 'start': SetImages(reset) -> SetWeights -> SetOptimizer -> iterate.
     iterate_average: a decay in (0, 1) makes every image handed out (the callback's, the result) the bias-corrected running mean of
     the iterates (Engine.set_iterate_average); 0 turns that off; None leaves the engine as it is.
     original_colors: True makes every image handed out keep the content image's colours (the iterate's luminance, the content's chroma:
     Engine.set_original_colors); match_style_colors: True gives the style image the content image's colour mean and covariance before
-    the style targets are taken (Engine.set_style_color_match).  False turns either off; None leaves the engine as it is."""
+    the style targets are taken (Engine.set_style_color_match).  False turns either off; None leaves the engine as it is.
+    laplacian: a list of (pool, weight) pairs turns the Laplacian-steered content term on (Engine.set_laplacian: the edges and fine
+    structure of the content image are held through the Laplacians of the pooled images); an empty list turns it off; None leaves
+    the engine as it is."""
     from .device_optimizers import AdamOptimizer, LBFGSOptimizer
     if isinstance(content, Image.Image):
         content = np.uint8(resize_to_fit(content, size or max(content.size)))
@@ -68,6 +71,8 @@ def run_job(transfer, content, style, iterations, size=None, style_size=None, op
     transfer.reset()
     if iterate_average is not None:
         transfer.engine.set_iterate_average(iterate_average)
+    if laplacian is not None:
+        transfer.set_laplacian(laplacian)
     if not transfer.start():
         raise RuntimeError('job could not start: inconsistent images')
     image = None
@@ -84,7 +89,7 @@ def run_job(transfer, content, style, iterations, size=None, style_size=None, op
 
 def run_tiled_job(net_params, content, style, iterations, grid, size=None, style_size=None, weights=None, params=None, init=None,
                   seed=0, device=0, precision='fp32', topology=None, callback=None, optimizer='adam', step_size=None, shard_style=False,
-                  iterate_average=None, original_colors=None, match_style_colors=None):
+                  iterate_average=None, original_colors=None, match_style_colors=None, laplacian=None):
     """The same job for an image no single engine holds (an 8192 x 8192 image has conv1 blobs of 17 GB each): the image is cut into
     grid = (rows, cols) tiles, every tile + apron is an engine context of THIS process on the one GPU (tiled.InProcessFabric: one
     thread per rank, the all-reduces and strip exchanges are device-to-device copies); one st_tile_step per rank and iteration, Adam or
@@ -97,7 +102,11 @@ def run_tiled_job(net_params, content, style, iterations, grid, size=None, style
     original_colors: every rank hands out its tile with the chroma of its own window of the content image (per pixel: the stitched image
     is run_job's).  match_style_colors: the colour moments of the WHOLE content and style images are taken once, through rank 0's engine,
     and the transform derived from them goes to every rank (Engine.set_style_transform) before the style is set, plain or shard_style.
+    laplacian: the Laplacian term does not run tile-sharded (st_set_laplacian refuses a tile-configured context): any levels, here or
+    in params['laplacian'], are a ValueError before anything is built.
     Returns the stitched HxWx3 float32 image; callback(i, trace values) after every iteration."""
+    if laplacian or (params and params.get('laplacian')):
+        raise ValueError('the Laplacian term does not run tile-sharded: use run_job, or drop the levels')
     from . import tiled, tiling
     from .engine import VGG19_TOPOLOGY
     from .tile_backend import HipTileBackend

@@ -180,6 +180,13 @@ class StyleTransfer:
         self.rows, self.cells = weight_table(weights)
         self.params = params
         self._push_weights()
+        if 'laplacian' in params:                           # optional: (pool, weight) pairs; without the key the setting stays
+            self.engine.set_laplacian(params['laplacian'])
+        self.objective_changed()
+
+    def set_laplacian(self, levels):
+        """The Laplacian-steered content term (Engine.set_laplacian): a list of (pool, weight) pairs, empty or None for off."""
+        self.engine.set_laplacian(levels)
         self.objective_changed()
 
     def _push_weights(self):
@@ -203,14 +210,20 @@ class StyleTransfer:
                 if flag:
                     t('%s_%s_loss' % (layer, tag), v[off])
                     t('%s_%s_grad' % (layer, tag), v[off + 1])
-        g = values[6 * len(active):]
+        g = list(values[6 * len(active):])
+        lap = len(g) == 10                                  # the Laplacian term is on: l_loss follows p_loss, l_grad follows p_grad
+        l_loss, l_grad = (g.pop(3), g.pop(6)) if lap else (None, None)
         t('scd_loss', g[0])
         t('t_loss', g[1])
         t('p_loss', g[2])
+        if lap:
+            t('l_loss', l_loss)
         if with_grad:
             t('scd_grad', g[3])
             t('t_grad', g[4])
             t('p_grad', g[5])
+            if lap:
+                t('l_grad', l_grad)
             t('time', time.perf_counter())
         t('loss', g[6])
         if with_grad:

@@ -42,18 +42,26 @@ def parser():
     ap.add_argument('--original-colors', action='store_true', help='st_set_original_colors: keep the content image\'s colours (luminance of the result, chroma of the content)')
     ap.add_argument('--match-style-colors', action='store_true',
                     help='st_set_style_color_match (with --grid: st_set_style_transform on every rank): linear colour transfer of the content\'s colours onto the style image')
+    ap.add_argument('--laplacian', default='', metavar='P:W,...',
+                    help='st_set_laplacian: the Laplacian-steered content term, levels as POOL:WEIGHT such as 4:100,16:100 (at most three; pool sizes 1, 2, 4, 8, 16, 32); not with --grid')
     return ap
 
 
 def main(argv=None):
     ap = parser()
     args = ap.parse_args(argv)
+    if args.laplacian and args.grid:
+        ap.error('--laplacian with --grid: tile-sharded mode does not run the Laplacian term')
     if args.ave_pools and args.grid:
         ap.error('--ave-pools with --grid: tile-sharded mode does not run average pools')
 
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import style_transfer2_amd as st2
-    from style_transfer2_amd import jobs, weights as st2_weights
+    from style_transfer2_amd import jobs, laplacian, weights as st2_weights
+    try:
+        levels = laplacian.parse_levels(args.laplacian) if args.laplacian else None
+    except ValueError as err:
+        ap.error('--laplacian %s: %s' % (args.laplacian, err))
 
     topology = st2.VGG19_TOPOLOGY
     if args.ave_pools:
@@ -77,7 +85,8 @@ def main(argv=None):
                                              conv_algo=args.conv_algo, gram_algo=args.gram_algo, pool_algo=args.pool_algo))
         image = jobs.run_job(job, jobs.load_rgb(args.content), jobs.load_rgb(args.style), args.iters, size=args.size,
                              style_size=args.style_size or None, optimizer=args.optimizer, iterate_average=args.avg_decay,
-                             original_colors=args.original_colors or None, match_style_colors=args.match_style_colors or None)
+                             original_colors=args.original_colors or None, match_style_colors=args.match_style_colors or None,
+                             laplacian=levels)
     Image.fromarray(np.uint8(np.clip(image, 0, 255))).save(args.out)
     print('wrote', args.out, image.shape)
 

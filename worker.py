@@ -110,6 +110,21 @@ def read_iterate_average(config):
     return value
 
 
+def read_laplacian(config):
+    """The optional config key ``laplacian = 4:W,16:W``: the Laplacian-steered content term (Engine.set_laplacian) with the given
+    (pool size, weight) levels -- at most three, pool sizes distinct and from 1, 2, 4, 8, 16, 32, weights finite and non-zero; ``0`` or
+    ``off`` is off.  Returns the list of levels, or None when the key is absent or empty (no call is made: the engine's default, off,
+    stays); a malformed value is a ValueError that names the key.  Pure: any mapping with ``get`` will do."""
+    raw = config.get('laplacian', None)
+    if raw is None or str(raw).strip() == '':
+        return None
+    from style_transfer2_amd.laplacian import parse_levels
+    try:
+        return parse_levels(raw)
+    except ValueError as err:
+        raise ValueError('config key laplacian = %r: %s (expected POOL:WEIGHT,... such as 4:100,16:100)' % (raw, err)) from None
+
+
 COLOR_KEYS = ('original_colors', 'style_color_match')
 
 
@@ -340,6 +355,11 @@ class Worker:
             decay = read_iterate_average(config)
             if decay is not None:
                 self.transfer.engine.set_iterate_average(decay)
+            # the Laplacian term (config key laplacian): two more trace scalars, l_loss and l_grad; SetWeights may change it later
+            # through params['laplacian']
+            levels = read_laplacian(config)
+            if levels is not None:
+                self.transfer.engine.set_laplacian(levels)
             async_send = str(config.get('async_iterate', '1')).lower() not in ('0', 'false', 'no')
             if async_send:
                 self.sock_out = AsyncSender(sock_out)
