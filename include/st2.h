@@ -145,7 +145,7 @@ int st_input_shape(st_ctx* ctx, int* H, int* W);
 int st_set_weights(st_ctx* ctx, int n_rows, const int* blob_index, const float* content,
                    const float* style, const float* deepdream, const double params[4]);
 int st_clear_norms(st_ctx* ctx);                          /* the `norms` half of reset() */
-/* number of trace scalars an evaluation produces: 6 per active layer + 8 (+ 2 while st_set_laplacian is on) */
+/* number of trace scalars an evaluation produces: 6 per active layer + 8 (+ 2 while st_set_laplacian is on, + 2 while st_set_anchor is) */
 int st_trace_len(st_ctx* ctx);
 /* evaluates opfunc at the current input; out_grad (3,H,W) may be NULL (return_grad=False) */
 int st_opfunc(st_ctx* ctx, float* out_loss, float* out_grad, double* trace);
@@ -281,6 +281,44 @@ int st_get_laplacian(st_ctx* ctx, int* n_levels, int* pool, double* weight);
  * the summed g_lap (3, H, W), the same at every level index.  Any pointer may be NULL.  ST_ERR_STATE, the message saying why: before an
  * evaluation with the term on, after the input was resized, and for grad_nchw after an evaluation without a gradient. */
 int st_get_laplacian_terms(st_ctx* ctx, int level, float* target, float* diff, float* grad_nchw);
+/* ---- the anchor term: a per-pixel weighted pull toward a given image ------------------------------------------------------------
+ * An image-space term like TV, the p-norm and the Laplacian term; no reference counterpart, this text is the definition.  It is what
+ * temporal consistency between the frames of a sequence (Ruder, Dosovitskiy, Brox: "Artistic Style Transfer for Videos", GCPR 2016:
+ * the previous stylised frame, warped by the optical flow, weighted by the flow's reliability), protected regions and an
+ * auxiliary-image regulariser are made of.  Symbols: u = x / 255, ua = ax / 255 (x: the preprocessed planar iterate; ax: the
+ * preprocessed planar anchor image of the input's size, (3, H, W)); m: an optional (H, W) fp32 map, every value finite and >= 0,
+ * shared by the three channels, absent meaning 1 everywhere; w: a weight that is finite and non-zero, as a double and as a float.
+ *   d = u - ua
+ *   loss  = w * sum over c, y, x of m[y, x] * d^2
+ *   g_anc = w * (2 * (m * d))     the derivative with respect to u, added to the image gradient as it is (no 1 / 255 chain factor,
+ *                                 like g_tv, g_p and g_lap)
+ *   grad  = ((scd + tv_w g_tv) + p_w g_p) + extra,  extra = g_lap + g_anc with the Laplacian term on (one fp32 addition, g_lap
+ *                                 first), else g_anc
+ * fp32 arithmetic, one rounding per operation, in the order written: x / 255 and ax / 255 are IEEE divisions; e = m * d (without a
+ * map there is no multiplication and e = d); the factor 2 comes next, then w as a float.  The sums of e * d (each product
+ * (double)e * (double)d) and of g_anc^2 are taken in double per thread, fp32 per workgroup and double across workgroups, exactly as the
+ * Laplacian term's.  While the term is on the trace gains two scalars; its image part becomes [scd_loss, t_loss, p_loss, (l_loss,)
+ * a_loss, scd_grad, tv_grad, p_grad, (l_grad,) a_grad, loss, grad] with a_loss = w * float(sum e d), added to loss last, after l_loss,
+ * and a_grad = sqrt(float(sum g_anc^2 / (3 H W))), 0 for an evaluation without a gradient; grad is the rms of the combined gradient.
+ * With the term off every trace is what it was.
+ *
+ * st_set_anchor: hwc (H, W, 3), uint8 or float32, is preprocessed on the device as st_set_content's image is; hwc == NULL is off, the
+ * default: every buffer of the term is freed and every path launches what it launched before.  mask_hw: H * W floats or NULL.
+ * st_set_anchor_nchw takes the preprocessed planes (3, H, W) instead.
+ * ST_ERR_ARG: a zero, NaN, infinite, float-underflowing or float-overflowing weight; a map value that is negative, NaN or infinite
+ * (the map is scanned on the host here); H or W < 1.  ST_ERR_STATE: while a pipelined iteration is in flight; on a tile-configured
+ * context (st_tile_configure refuses a context with the term on).  The buffers are allocated and filled first: when that fails
+ * nothing has changed.  The anchor does not follow the input: after st_set_input* or st_resample_state to another size it stays, and
+ * every evaluation (st_opfunc, st_step, st_step_begin) returns ST_ERR_STATE naming both sizes, before anything is enqueued, until an
+ * anchor of the new size is set or the term is turned off. */
+int st_set_anchor(st_ctx* ctx, const void* hwc, int H, int W, int is_u8, const float* mask_hw, double weight);
+int st_set_anchor_nchw(st_ctx* ctx, const float* ax, int H, int W, const float* mask_hw, double weight);
+/* the term in force (H = W = 0 while it is off); any pointer may be NULL */
+int st_get_anchor(st_ctx* ctx, int* on, int* H, int* W, int* has_mask, double* weight);
+/* Test hook, reads only: the anchor planes (3, H, W) and the map (H, W) the last evaluation read, and `extra` (3, H, W) as it left it.
+ * Any pointer may be NULL.  ST_ERR_STATE, the message saying why: with the term off, before an evaluation with the term on, after the
+ * input was resized, for mask_hw without a map, and for extra_nchw after an evaluation without a gradient. */
+int st_get_anchor_terms(st_ctx* ctx, float* anchor_nchw, float* mask_hw, float* extra_nchw);
 /* Steps so far that ran as a hipGraph replay.  Opt-in (environment ST2_GRAPH=1; ST2_GRAPH_MAX_PX=<edge>, default 768):
  * steady-state Adam steps are captured once per ping-pong parity and replayed, bit-identical to plain launches.  Measured
  * on MI355X it is no faster (the step is bound by the dependent kernels' execution latency), hence off by default. */

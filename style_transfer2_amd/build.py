@@ -28,6 +28,7 @@ SOURCES = (
     ('color.hip', ('-ffp-contract=off',)),       # colour moments, recolour: the arithmetic of st2.h, one rounding per operation
     ('emit.hip', ('-ffp-contract=off',)),        # the image handed out (plain, averaged, luminance): NumPy's float32 arithmetic
     ('laplacian.hip', ('-ffp-contract=off',)),   # the Laplacian term: pool, stencil, gradient, one rounding per operation
+    ('anchor.hip', ('-ffp-contract=off',)),      # the anchor term: one pass, one rounding per operation
     ('style16.hip', ()),
     ('gram16.hip', ()),
     ('gram_split.hip', ()),
@@ -44,8 +45,9 @@ SOURCES = (
     ('engine_color.cpp', ('-x', 'hip')),
     ('engine_emit.cpp', ('-x', 'hip')),
     ('engine_laplacian.cpp', ('-x', 'hip')),
+    ('engine_anchor.cpp', ('-x', 'hip')),
 )
-HEADERS = ('st2_kernels.h', 'env.h', 'wave_reduce.h', 'engine.h', 'devbuf.h', 'color_match.h', 'emit_plan.h', 'laplacian_plan.h', 'image_pass_kernel.inc', 'channel_mean.h', os.path.join('..', '..', 'include', 'st2.h'))
+HEADERS = ('st2_kernels.h', 'env.h', 'wave_reduce.h', 'engine.h', 'devbuf.h', 'color_match.h', 'emit_plan.h', 'laplacian_plan.h', 'anchor_plan.h', 'image_pass_kernel.inc', 'channel_mean.h', os.path.join('..', '..', 'include', 'st2.h'))
 
 
 def _hipcc():

@@ -40,6 +40,7 @@ enum ProfClass { P_CONV_FWD, P_CONV_DGRAD, P_POOL_FWD, P_POOL_BWD, P_GRAM, P_GRA
                  P_CONV_FWD_BF16, P_CONV_DGRAD_BF16, P_COMM, P_GRAM_BF16, P_STYLE_GRAD_BF16, P_CONV_FWD_WSPLIT, P_CONV_DGRAD_WSPLIT, P_STYLE_FUSED_BF16,
                  P_AVEPOOL_FWD, P_AVEPOOL_BWD, P_GRAM_SPLIT, P_STYLE_GRAD_SPLIT, P_AVEPOOL_BWD_MAP16,
                  P_LAP_POOL, P_LAP_STENCIL, P_LAP_GRAD,      // the launches of the Laplacian term (laplacian.hip), the targets' included
+                 P_ANCHOR,                                   // anchor_k, the one launch of the anchor term (anchor.hip)
                  P_COUNT };
 extern const char* const kProfNames[P_COUNT];
 struct ProfRec { int cls; hipEvent_t a, b; double flops, bytes; };
@@ -302,6 +303,19 @@ struct st_ctx {
         bool evaluated = false, have_grad = false; // e (and g) hold the last evaluation's
         bool resized = false;                      // ... they did, until the input was resized
     } lap;
+    // the anchor term (st_set_anchor; engine_anchor.cpp, anchor_plan.h)
+    struct Anchor {
+        bool on = false;                           // off: every buffer below is empty
+        double weight = 0;
+        bool has_mask = false;
+        AnchorPlan plan{};                         // of the anchor's size -- the anchor does not follow the input
+        DevBuf<float> ax, m;                       // the preprocessed anchor (3, H, W), the map (H, W) when there is one
+        DevBuf<float> extra;                       // g_lap + g_anc, or g_anc: what the image pass adds after p_w g_p
+        DevBuf<float> part;                        // kAnchorPartRows * kMaxPartials
+        int cnt = 0;                               // partial count of the last evaluation
+        bool evaluated = false, have_grad = false; // extra holds the last evaluation's
+        bool resized = false;                      // ... it did, until the input was resized
+    } anchor;
     // tile-sharded mode (BASELINE config 5): this context holds ONE window of a larger image
     struct Tile : TileGeom {
         bool on = false;
@@ -463,6 +477,15 @@ int lap_preflight(const st_ctx* c);
 int lap_forward(st_ctx* c, const float* x);
 int lap_backward(st_ctx* c);
 void lap_input_resized(st_ctx* c);                // the input has a new size: the term's buffers are those of the old one
+// ---------------------------------------------------------------------------------------- engine_anchor.cpp
+// The anchor term of an evaluation.  anchor_preflight: the refusals (a tile-configured context, an anchor of another size than the
+// input), ST_OK with the term off -- no HIP call, nothing changes: every evaluation asks before it enqueues anything.  anchor_eval: the
+// one launch, after the Laplacian term's; g_lap: that term's gradient or NULL; *extra: what launch_image_pass takes as `lap` (NULL for an
+// evaluation without a gradient).  anchor_trace: a_loss and a_grad into the image part of the trace at image_out
+int anchor_preflight(const st_ctx* c);
+int anchor_eval(st_ctx* c, const float* x, bool want_grad, const float* g_lap, const float** extra);
+int anchor_trace(st_ctx* c, bool want_grad, bool with_lap, float* image_out);
+void anchor_input_resized(st_ctx* c);             // the input has a new size: `extra` is that of an evaluation at the old one
 // ---------------------------------------------------------------------------------------- engine_tile.cpp
 // pack (mode 0) / unpack (1 assign, 2 add) the rectangles (y0, x0, h, w each) of a (C, h, w) tensor; checks them against it; enqueues only
 int strips(st_ctx* c, float* tensor, int C, int h, int w, const std::vector<int>& rects, float* buf, int mode);

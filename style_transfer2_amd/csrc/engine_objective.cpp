@@ -56,6 +56,7 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
 {
     if (!c->x[0]) return fail(ST_ERR_STATE, "no input image");
     ST_TRY(lap_preflight(c));
+    ST_TRY(anchor_preflight(c));
     ST_TRY(act_ensure(c, c->act, c->H, c->W));
     ActSet& a = c->act;
     ObjTerms terms;
@@ -148,12 +149,16 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
         if (want_grad) ST_TRY(lap_backward(c));
     }
 
+    // the anchor term (st_set_anchor): one launch; with a gradient it leaves extra = g_lap + g_anc (or g_anc), which takes g_lap's place
+    const float* extra = lap && want_grad ? c->lap.g.get() : nullptr;
+    const bool anchor = c->anchor.on;
+    if (anchor) ST_TRY(anchor_eval(c, x, want_grad, extra, &extra));
+
     {
         const ImagePassArgs ip = image_pass_args(c, x, scd, want_grad ? grad_out : nullptr, adam, x_next);
-        const float* g_lap = lap && want_grad ? c->lap.g.get() : nullptr;
         const double n3 = 3.0 * c->H * c->W;
-        ProfScope ps(c, P_IMAGE_PASS, 0, 4.0 * n3 * ((adam ? 7 : 3) + (g_lap ? 1 : 0)));
-        HIP_TRY(launch_image_pass(ip, &c->image_cnt, c->stream, g_lap));
+        ProfScope ps(c, P_IMAGE_PASS, 0, 4.0 * n3 * ((adam ? 7 : 3) + (extra ? 1 : 0)));
+        HIP_TRY(launch_image_pass(ip, &c->image_cnt, c->stream, extra));
     }
 
     {
@@ -175,7 +180,7 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
         t.tv_w = c->tv_w; t.p_w = c->p_w; t.p_pow = c->p_pow; t.have_grad = want_grad;
         t.out = c->trace_dev;
         t.sums = c->trace_sums;
-        c->trace_len_last = t.n_layers * 6 + 8 + (lap ? 2 : 0);
+        c->trace_len_last = t.n_layers * 6 + 8 + (lap ? 2 : 0) + (anchor ? 2 : 0);
         ProfScope ps(c, P_FINALIZE, 0, 0);
         HIP_TRY(launch_finalize_trace(t, c->stream));
         if (lap) {                // l_loss and l_grad join the image part of the trace
@@ -185,6 +190,7 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
             tl.image_n = t.image_n; tl.have_grad = want_grad; tl.image_out = c->trace_dev + t.n_layers * 6;
             HIP_TRY(launch_trace_lap(tl, c->stream));
         }
+        if (anchor) ST_TRY(anchor_trace(c, want_grad, lap, c->trace_dev + t.n_layers * 6));      // a_loss and a_grad, after the Laplacian term's
     }
     c->lt.any = true;
     return ST_OK;
@@ -277,7 +283,7 @@ int st_get_layer_terms(st_ctx* c, int index, float* D, float* raw_S, float* diff
     return ST_OK;
 }
 
-int st_trace_len(st_ctx* c) { return c ? (int)c->active.size() * 6 + 8 + (c->lap.n ? 2 : 0) : 0; }
+int st_trace_len(st_ctx* c) { return c ? (int)c->active.size() * 6 + 8 + (c->lap.n ? 2 : 0) + (c->anchor.on ? 2 : 0) : 0; }
 
 int st_opfunc(st_ctx* c, float* out_loss, float* out_grad, double* trace)
 {
@@ -285,6 +291,7 @@ int st_opfunc(st_ctx* c, float* out_loss, float* out_grad, double* trace)
     if (!c) return fail(ST_ERR_ARG, "ctx is NULL");
     if (!c->x[0]) return fail(ST_ERR_STATE, "no input image");
     ST_TRY(lap_preflight(c));                                 // refused before anything is enqueued
+    ST_TRY(anchor_preflight(c));
     HIP_TRY(hipSetDevice(c->device));
     ST_TRY(eval_objective(c, c->x[c->cur], out_grad != nullptr, c->grad, false, nullptr));
     if (out_grad) HIP_TRY(hipMemcpyAsync(out_grad, c->grad, (size_t)3 * c->H * c->W * sizeof(float), hipMemcpyDeviceToHost, c->stream));

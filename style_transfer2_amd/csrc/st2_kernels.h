@@ -7,11 +7,13 @@
 
 #include "emit_plan.h"
 #include "laplacian_plan.h"
+#include "anchor_plan.h"
 
 namespace st2 {
 
 constexpr int kMaxPartials = 1024;   // grid cap (= partial-sum slots) of every reducing kernel
 static_assert(kLapMaxBlocks == kMaxPartials, "laplacian_plan.h sizes its partial-sum rows like every reducing kernel");
+static_assert(kAnchorMaxBlocks == kMaxPartials, "anchor_plan.h sizes its partial-sum rows like every reducing kernel");
 constexpr int kConvCC = 4;           // K granularity of the packed conv weights (staged chunk = 4 or 8)
 constexpr int kCoutQuantum = 64;     // conv weights are zero-padded to a multiple of this many outputs
 
@@ -365,6 +367,17 @@ struct LapGradArgs { const float* e; float* g; float* part; int H, W, n; int shi
 hipError_t launch_lap_grad(const LapGradArgs& a, int grid, int grid_vec, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
+// The anchor term (anchor.hip; anchor_plan.h has the validation and the grids): planes x, ax, extra and the optional g_lap of (3, H, W),
+// plane = H * W, the optional map m of (H, W).
+// ------------------------------------------------------------------------------------------
+// extra = g_lap + w (2 e) (g_lap == NULL: w (2 e)) with e = m (x / 255 - ax / 255) (m == NULL: no multiplication);
+// part[0][block] = the workgroup's sum of e d, part[1][block] that of (w (2 e))^2 (rows of kAnchorMaxBlocks).  extra == NULL: an
+// evaluation without a gradient -- no plane is written and only row 0.  16-byte loads and stores where W % 4 == 0 and every plane is
+// aligned (grid_vec workgroups), one pixel per thread and trip otherwise (grid); *n_partial: the slots written per row
+struct AnchorArgs { const float* x; const float* ax; const float* m; const float* g_lap; float* extra; float* part; size_t plane; int W; float w; };
+hipError_t launch_anchor(const AnchorArgs& a, int grid, int grid_vec, int* n_partial, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------
 // trace finalisation: one tiny kernel turns the partial sums of an opfunc into the trace scalars
 // ------------------------------------------------------------------------------------------
 constexpr int kMaxTraceLayers = 24;
@@ -397,6 +410,12 @@ hipError_t launch_finalize_trace(const TraceArgs& a, hipStream_t s);
 // image_n)) (0 without a gradient).  part: rows of kLapMaxBlocks partials -- sum E^2 per level (count_e each), then sum g_lap^2 (count_g)
 struct TraceLapArgs { int levels; const float* part; int count_e, count_g; float w[kLapMaxLevels]; double image_n; int have_grad; float* image_out; };
 hipError_t launch_trace_lap(const TraceLapArgs& a, hipStream_t s);
+// The anchor term's part of the trace (anchor.hip), after launch_finalize_trace and, with the Laplacian term on (with_lap), after
+// launch_trace_lap on the same `out`: a_loss = w * float(sum e d) follows the last loss term, a_grad = sqrt(float(sum g_anc^2 /
+// image_n)) (0 without a gradient) the last gradient norm, and loss becomes loss + a_loss: the image part grows from 8 to 10 scalars,
+// or from 10 to 12.  part: two rows of kAnchorMaxBlocks partials -- sum e d (count_l), then sum g_anc^2 (count_g)
+struct TraceAnchorArgs { const float* part; int count_l, count_g; float w; double image_n; int have_grad, with_lap; float* image_out; };
+hipError_t launch_trace_anchor(const TraceAnchorArgs& a, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
 // Fixed-step L-BFGS as a device-resident state machine (lbfgs.hip), optimizers.py:49-125, utils.py:29-46

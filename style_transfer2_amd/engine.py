@@ -517,6 +517,62 @@ class Engine:
         check(self.lib.st_get_laplacian_terms(self._ctx, level, _ptr(target), _ptr(diff), _ptr(grad)))
         return target, diff, grad
 
+    # -- the anchor term (st2.h: st_set_anchor) ------------------------------------------------------------------------------
+    def set_anchor(self, image, mask=None, weight=1.0):
+        """A per-pixel weighted pull toward `image`: every evaluation adds weight * sum mask * (x / 255 - anchor / 255) ** 2 to the loss
+        and its gradient to the image gradient, and the trace has two more scalars (a_loss, a_grad).  image: HxWx3 (uint8 or float,
+        preprocessed on the device like a content image), or already preprocessed planes of shape (3, H, W) or (1, 3, H, W); None turns
+        the term off (the default).  mask: an optional (H, W) map of finite values >= 0 shared by the channels -- float as it is, uint8
+        divided by 255, bool as 0 / 1.  The anchor does not follow the input: after a resize every evaluation is refused until an
+        anchor of the new size is set or the term is turned off.  Refused while a pipelined iteration is in flight and on a
+        tile-configured context."""
+        if image is None:
+            check(self.lib.st_set_anchor(self._ctx, None, 0, 0, 0, None, 1.0))
+            return
+        arr = np.asarray(image)
+        if arr.ndim == 4:
+            if arr.shape[:2] != (1, 3):
+                raise ValueError('planar anchor must be (3, H, W) or (1, 3, H, W), got %s' % (arr.shape,))
+            arr = arr[0]
+        planar = arr.ndim == 3 and arr.shape[0] == 3 and (np.ndim(image) == 4 or arr.shape[2] != 3)
+        if planar:
+            arr = np.ascontiguousarray(arr, F32)
+            h, w = arr.shape[1:]
+        else:
+            arr, u8 = _image_arg(arr)
+            h, w = arr.shape[:2]
+        if mask is not None:
+            mask = np.asarray(mask)
+            if mask.shape != (h, w):
+                raise ValueError('the map must be (%d, %d), got %s' % (h, w, mask.shape))
+            if mask.dtype == np.uint8:
+                mask = mask.astype(F32) / F32(255)
+            mask = np.ascontiguousarray(mask, F32)          # (bool: 0 / 1)
+        if planar:
+            check(self.lib.st_set_anchor_nchw(self._ctx, _ptr(arr), h, w, _ptr(mask), float(weight)))
+        else:
+            check(self.lib.st_set_anchor(self._ctx, _ptr(arr), h, w, u8, _ptr(mask), float(weight)))
+
+    def anchor(self):
+        """The term in force: None while it is off, else a dict with 'size' (H, W), 'has_mask' and 'weight'."""
+        on, h, w, has_mask, weight = c_int(), c_int(), c_int(), c_int(), c_double()
+        check(self.lib.st_get_anchor(self._ctx, byref(on), byref(h), byref(w), byref(has_mask), byref(weight)))
+        if not on.value:
+            return None
+        return {'size': (h.value, w.value), 'has_mask': bool(has_mask.value), 'weight': weight.value}
+
+    def anchor_terms(self, want_extra=True):
+        """Test hook: (anchor, mask, extra) of the last evaluation -- the preprocessed anchor (1, 3, H, W), the map (H, W) or None
+        without one, and the plane the image pass added after the p-norm term (1, 3, H, W): g_lap + g_anc with the Laplacian term
+        on, else g_anc; None when want_extra is False."""
+        info = self.anchor()
+        h, w = info['size'] if info else (1, 1)
+        ax = np.empty((1, 3, h, w), F32)
+        mask = np.empty((h, w), F32) if info and info['has_mask'] else None
+        extra = np.empty((1, 3, h, w), F32) if want_extra else None
+        check(self.lib.st_get_anchor_terms(self._ctx, _ptr(ax), _ptr(mask), _ptr(extra)))
+        return ax, mask, extra
+
     def set_style_nchw(self, x):
         """set_style for an already-preprocessed (1, 3, H, W) image; no colour transform is applied."""
         x = np.ascontiguousarray(x, F32)

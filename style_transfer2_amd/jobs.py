@@ -37,9 +37,20 @@ def load_rgb(path):
     return Image.open(path).convert('RGB')
 
 
+def load_mask(path, hw):
+    """A per-pixel map for the anchor term: an .npy of (H, W) values as they are, or an image read as 8-bit grey (0 .. 255, which
+    Engine.set_anchor divides by 255) and resized to hw = (H, W)."""
+    if str(path).endswith('.npy'):
+        mask = np.load(path)
+        if mask.shape != tuple(hw):
+            raise ValueError('%s: a map of %s for an image of %s' % (path, mask.shape, tuple(hw)))
+        return mask
+    return np.uint8(Image.open(path).convert('L').resize(tuple(hw)[::-1], Image.BILINEAR))
+
+
 def run_job(transfer, content, style, iterations, size=None, style_size=None, optimizer='adam', step_size=None,
             weights=None, params=None, init=None, seed=0, callback=None, iterate_average=None, original_colors=None,
-            match_style_colors=None, laplacian=None):
+            match_style_colors=None, laplacian=None, anchor=None, init_nchw=None):
     """One whole stylisation: content/style are PIL images or HxWx3 arrays.  Returns the final HxWx3 float32
     image.  Mirrors app.init_arrays + 'start': SetImages(reset) -> SetWeights -> SetOptimizer -> iterate.
     iterate_average: a decay in (0, 1) makes every image handed out (the callback's, the result) the bias-corrected running mean of
@@ -49,19 +60,28 @@ def run_job(transfer, content, style, iterations, size=None, style_size=None, op
     the style targets are taken (Engine.set_style_color_match).  False turns either off; None leaves the engine as it is.
     laplacian: a list of (pool, weight) pairs turns the Laplacian-steered content term on (Engine.set_laplacian: the edges and fine
     structure of the content image are held through the Laplacians of the pooled images); an empty list turns it off; None leaves
-    the engine as it is."""
+    the engine as it is.
+    anchor: an (image, mask, weight) tuple turns the anchor term on (StyleTransfer.set_anchor: a per-pixel weighted pull toward the
+    image, which has the content's size; HxWx3, or preprocessed planes (3, H, W)); False turns it off; None leaves the engine as it is.
+    init_nchw: preprocessed planes (3, H, W) or (1, 3, H, W) to start from in place of `init` (an iterate read with
+    Engine.get_input_nchw, for one)."""
     from .device_optimizers import AdamOptimizer, LBFGSOptimizer
     if isinstance(content, Image.Image):
         content = np.uint8(resize_to_fit(content, size or max(content.size)))
     if isinstance(style, Image.Image):
         style = np.uint8(resize_to_fit(style, style_size or size or max(style.size)))
-    if init is None:
+    if init_nchw is not None:
+        init_nchw = np.ascontiguousarray(init_nchw, np.float32).reshape((1, 3) + tuple(content.shape[:2]))
+        init = np.zeros(content.shape[:2] + (3,), np.uint8)    # (sizes the engine's buffers; the planes follow)
+    elif init is None:
         init = noise_image(content.shape[:2], seed)
     if original_colors is not None:
         transfer.engine.set_original_colors(original_colors)
     if match_style_colors is not None:
         transfer.engine.set_style_color_match(match_style_colors)
     transfer.set_input(init)
+    if init_nchw is not None:
+        transfer.engine.set_input_nchw(init_nchw)
     transfer.set_content(content)
     transfer.set_style(style)
     transfer.reset()
@@ -73,6 +93,12 @@ def run_job(transfer, content, style, iterations, size=None, style_size=None, op
         transfer.engine.set_iterate_average(iterate_average)
     if laplacian is not None:
         transfer.set_laplacian(laplacian)
+    if anchor is not None:
+        if anchor is False:
+            transfer.set_anchor(None)
+        else:
+            image, mask, weight = anchor
+            transfer.set_anchor(image, mask, weight)
     if not transfer.start():
         raise RuntimeError('job could not start: inconsistent images')
     image = None
@@ -89,7 +115,7 @@ def run_job(transfer, content, style, iterations, size=None, style_size=None, op
 
 def run_tiled_job(net_params, content, style, iterations, grid, size=None, style_size=None, weights=None, params=None, init=None,
                   seed=0, device=0, precision='fp32', topology=None, callback=None, optimizer='adam', step_size=None, shard_style=False,
-                  iterate_average=None, original_colors=None, match_style_colors=None, laplacian=None):
+                  iterate_average=None, original_colors=None, match_style_colors=None, laplacian=None, anchor=None):
     """The same job for an image no single engine holds (an 8192 x 8192 image has conv1 blobs of 17 GB each): the image is cut into
     grid = (rows, cols) tiles, every tile + apron is an engine context of THIS process on the one GPU (tiled.InProcessFabric: one
     thread per rank, the all-reduces and strip exchanges are device-to-device copies); one st_tile_step per rank and iteration, Adam or
@@ -104,7 +130,10 @@ def run_tiled_job(net_params, content, style, iterations, grid, size=None, style
     and the transform derived from them goes to every rank (Engine.set_style_transform) before the style is set, plain or shard_style.
     laplacian: the Laplacian term does not run tile-sharded (st_set_laplacian refuses a tile-configured context): any levels, here or
     in params['laplacian'], are a ValueError before anything is built.
+    anchor: the anchor term does not run tile-sharded either (st_set_anchor refuses a tile-configured context): a ValueError as well.
     Returns the stitched HxWx3 float32 image; callback(i, trace values) after every iteration."""
+    if anchor:
+        raise ValueError('the anchor term does not run tile-sharded: use run_job, or drop the anchor')
     if laplacian or (params and params.get('laplacian')):
         raise ValueError('the Laplacian term does not run tile-sharded: use run_job, or drop the levels')
     from . import tiled, tiling
@@ -157,3 +186,49 @@ def run_tiled_job(net_params, content, style, iterations, grid, size=None, style
         for b in backends:
             b.engine.close()
     return image
+
+
+def warp_planar(x_chw, flow_hw2):
+    """Backward bilinear warp of planes (C, H, W) by a flow field (H, W, 2) of (dx, dy) in pixels:
+    out[:, y, x] = bilinear(x_chw, y + flow[y, x, 1], x + flow[y, x, 0]), sample coordinates clamped to the image.  Computed in float64,
+    returned as float32.  Frame sequences warp the previous stylised frame onto the next one with it (run_frames)."""
+    x = np.asarray(x_chw, np.float64)
+    flow = np.asarray(flow_hw2, np.float64)
+    if x.ndim != 3 or flow.shape != x.shape[1:] + (2,):
+        raise ValueError('planes (C, H, W) and a flow (H, W, 2) of the same size, got %s and %s' % (x.shape, flow.shape))
+    h, w = x.shape[1:]
+    yy, xx = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing='ij')
+    sy = np.clip(yy + flow[..., 1], 0, h - 1)
+    sx = np.clip(xx + flow[..., 0], 0, w - 1)
+    y0, x0 = np.floor(sy).astype(np.int64), np.floor(sx).astype(np.int64)
+    y1, x1 = np.minimum(y0 + 1, h - 1), np.minimum(x0 + 1, w - 1)
+    fy, fx = sy - y0, sx - x0
+    top = x[:, y0, x0] * (1 - fx) + x[:, y0, x1] * fx
+    bottom = x[:, y1, x0] * (1 - fx) + x[:, y1, x1] * fx
+    return (top * (1 - fy) + bottom * fy).astype(np.float32)
+
+
+def run_frames(transfer, frames, style, iterations, anchor_weight, flows=None, masks=None, first_iterations=None, **job_kwargs):
+    """A frame sequence with temporal consistency (Ruder et al.): frame 0 is a plain run_job (first_iterations of them where given);
+    frame t > 0 starts from the raw iterate of frame t - 1 (Engine.get_input_nchw: never the averaged or recoloured image handed
+    out), warped by flows[t] (warp_planar; (H, W, 2), from frame t back to frame t - 1) where one is given, and is pulled toward that
+    same image by the anchor term with the map masks[t] (the flow's reliability; None: 1 everywhere) and anchor_weight.
+    frames: HxWx3 arrays of one size; flows, masks: sequences as long as frames (entry 0 is not read) or None.
+    job_kwargs go to every run_job.  Returns the list of results."""
+    frames = [np.asarray(f) for f in frames]
+    if len({f.shape for f in frames}) > 1:
+        raise ValueError('the frames differ in size: %s' % sorted({f.shape[:2] for f in frames}))
+    for name, seq in (('flows', flows), ('masks', masks)):
+        if seq is not None and len(seq) != len(frames):
+            raise ValueError('%s: one entry per frame (entry 0 is not read), got %d for %d frames' % (name, len(seq), len(frames)))
+    results = []
+    for t, frame in enumerate(frames):
+        if t == 0:
+            results.append(run_job(transfer, frame, style, first_iterations or iterations, anchor=False, **job_kwargs))
+            continue
+        prev = transfer.engine.get_input_nchw()[0]
+        if flows is not None and flows[t] is not None:
+            prev = warp_planar(prev, flows[t])
+        mask = masks[t] if masks is not None else None
+        results.append(run_job(transfer, frame, style, iterations, anchor=(prev[None], mask, anchor_weight), init_nchw=prev, **job_kwargs))
+    return results

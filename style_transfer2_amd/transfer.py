@@ -75,6 +75,7 @@ class StyleTransfer:
         self.step_size = 1                                      # SetOptimizer.step_sizes['lbfgs']
         self.traces = []
         self._inflight = []
+        self._anchor_on = False                                 # set_anchor: _make_trace cannot tell a 10-long image part apart by length
 
     # ------------------------------------------------------------------ views of device state
     @property
@@ -189,6 +190,12 @@ class StyleTransfer:
         self.engine.set_laplacian(levels)
         self.objective_changed()
 
+    def set_anchor(self, image, mask=None, weight=1.0):
+        """The anchor term (Engine.set_anchor): a per-pixel weighted pull toward `image`; None turns it off."""
+        self.engine.set_anchor(image, mask, weight)
+        self._anchor_on = image is not None
+        self.objective_changed()
+
     def _push_weights(self):
         cols = [[self.cells[k][r] for r in self.rows] for k in LOSS_NAMES]
         self.engine.set_weights(self.rows, cols[0], cols[1], cols[2],
@@ -211,23 +218,21 @@ class StyleTransfer:
                     t('%s_%s_loss' % (layer, tag), v[off])
                     t('%s_%s_grad' % (layer, tag), v[off + 1])
         g = list(values[6 * len(active):])
-        lap = len(g) == 10                                  # the Laplacian term is on: l_loss follows p_loss, l_grad follows p_grad
-        l_loss, l_grad = (g.pop(3), g.pop(6)) if lap else (None, None)
-        t('scd_loss', g[0])
-        t('t_loss', g[1])
-        t('p_loss', g[2])
-        if lap:
-            t('l_loss', l_loss)
+        # the image part is 8 long, plus 2 with the Laplacian term on, plus 2 with the anchor term: a 10-long one is the anchor's only
+        # when this object turned that term on (set_anchor)
+        anchor = len(g) == 12 or (len(g) == 10 and self._anchor_on)
+        lap = len(g) - (2 if anchor else 0) == 10           # the Laplacian term is on: l_loss follows p_loss, l_grad follows p_grad
+        extra = [name for name, on in (('l', lap), ('a', anchor)) if on]
+        n = 3 + len(extra)                                  # losses, then as many gradient norms, then loss and grad
+        for name, v in zip(['scd', 't', 'p'] + extra, g[:n]):
+            t(name + '_loss', v)
         if with_grad:
-            t('scd_grad', g[3])
-            t('t_grad', g[4])
-            t('p_grad', g[5])
-            if lap:
-                t('l_grad', l_grad)
+            for name, v in zip(['scd', 't', 'p'] + extra, g[n:2 * n]):
+                t(name + '_grad', v)
             t('time', time.perf_counter())
-        t('loss', g[6])
+        t('loss', g[2 * n])
         if with_grad:
-            t('grad', g[7])
+            t('grad', g[2 * n + 1])
         return t
 
     def opfunc(self, x=None, return_grad=True):

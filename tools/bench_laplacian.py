@@ -30,8 +30,8 @@ from bench_average import block, make_job, pipelined, resident       # noqa: E40
 CLASSES = ('laplacian_pool', 'laplacian_stencil', 'laplacian_grad', 'image_pass', 'finalize', 'misc')
 
 
-def per_launch(eng, loop, steps, size):
-    """Per class of CLASSES: launches per step, mean microseconds, and GB/s of the bytes the launch books (emit_k: 2 streams)."""
+def per_launch(eng, loop, steps, size, classes=CLASSES):
+    """Per class of `classes`: launches per step, mean microseconds, and GB/s of the bytes the launch books (emit_k: 2 streams)."""
     eng.profile_enable(True)
     eng.profile_read()
     loop(eng, steps)
@@ -39,7 +39,7 @@ def per_launch(eng, loop, steps, size):
     prof = eng.profile_read()
     eng.profile_enable(False)
     out = {}
-    for name in CLASSES:
+    for name in classes:
         p = prof.get(name)
         if not p:
             continue

@@ -44,6 +44,9 @@ def parser():
                     help='st_set_style_color_match (with --grid: st_set_style_transform on every rank): linear colour transfer of the content\'s colours onto the style image')
     ap.add_argument('--laplacian', default='', metavar='P:W,...',
                     help='st_set_laplacian: the Laplacian-steered content term, levels as POOL:WEIGHT such as 4:100,16:100 (at most three; pool sizes 1, 2, 4, 8, 16, 32); not with --grid')
+    ap.add_argument('--anchor', default='', metavar='IMG', help='st_set_anchor: pull the result toward this image (resized to the content\'s size); not with --grid')
+    ap.add_argument('--anchor-mask', default='', metavar='M', help='with --anchor: a per-pixel map of the pull, an image (0 .. 255 -> 0 .. 1) or an .npy of (H, W) values >= 0')
+    ap.add_argument('--anchor-weight', type=float, default=1.0, metavar='W', help='with --anchor: the weight of the term (default 1)')
     return ap
 
 
@@ -52,6 +55,10 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.laplacian and args.grid:
         ap.error('--laplacian with --grid: tile-sharded mode does not run the Laplacian term')
+    if args.anchor and args.grid:
+        ap.error('--anchor with --grid: tile-sharded mode does not run the anchor term')
+    if args.anchor_mask and not args.anchor:
+        ap.error('--anchor-mask without --anchor')
     if args.ave_pools and args.grid:
         ap.error('--ave-pools with --grid: tile-sharded mode does not run average pools')
 
@@ -83,10 +90,17 @@ def main(argv=None):
     else:
         job = st2.StyleTransfer(st2.HipModel(params, topology=None if topology is st2.VGG19_TOPOLOGY else topology, device=args.gpu, precision=args.precision,
                                              conv_algo=args.conv_algo, gram_algo=args.gram_algo, pool_algo=args.pool_algo))
-        image = jobs.run_job(job, jobs.load_rgb(args.content), jobs.load_rgb(args.style), args.iters, size=args.size,
+        content = jobs.load_rgb(args.content)
+        anchor = None
+        if args.anchor:                                     # the anchor and its map take the size the content image will have
+            content = np.uint8(jobs.resize_to_fit(content, args.size or max(content.size)))
+            hw = content.shape[:2]
+            anchor = (np.uint8(jobs.load_rgb(args.anchor).resize(hw[::-1], Image.LANCZOS)),
+                      jobs.load_mask(args.anchor_mask, hw) if args.anchor_mask else None, args.anchor_weight)
+        image = jobs.run_job(job, content, jobs.load_rgb(args.style), args.iters, size=args.size,
                              style_size=args.style_size or None, optimizer=args.optimizer, iterate_average=args.avg_decay,
                              original_colors=args.original_colors or None, match_style_colors=args.match_style_colors or None,
-                             laplacian=levels)
+                             laplacian=levels, anchor=anchor)
     Image.fromarray(np.uint8(np.clip(image, 0, 255))).save(args.out)
     print('wrote', args.out, image.shape)
 
