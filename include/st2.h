@@ -319,6 +319,56 @@ int st_get_anchor(st_ctx* ctx, int* on, int* H, int* W, int* has_mask, double* w
  * Any pointer may be NULL.  ST_ERR_STATE, the message saying why: with the term off, before an evaluation with the term on, after the
  * input was resized, for mask_hw without a map, and for extra_nchw after an evaluation without a gradient. */
 int st_get_anchor_terms(st_ctx* ctx, float* anchor_nchw, float* mask_hw, float* extra_nchw);
+/* ---- frame sequences: earlier iterates kept on the device, warped into the iterate and into the anchor -----------------------------
+ * What the seam between two frames of a stylised sequence needs (Ruder, Dosovitskiy, Brox: "Artistic Style Transfer for Videos", GCPR
+ * 2016): the next frame starts from the previous stylised frame warped by the optical flow and is pulled toward it by the anchor term
+ * above, weighted by the flow's reliability; regions that were covered for a few frames are pulled toward an older frame (the
+ * long-term loss, which for 0 / 1 maps is ONE anchor term whose image and map are composed per pixel from several frames).  No
+ * reference counterpart, this text is the definition; jobs.warp_planar and tests/frames_oracle.py restate it in NumPy.
+ *
+ * The store.  st_frames_keep: depth 0 (default) .. 8 earlier iterates are kept; a smaller depth drops the oldest beyond it, 0 frees every
+ * buffer of the block; anything else is ST_ERR_ARG.  st_frame_push: the current RAW iterate x (the preprocessed planes of
+ * st_get_input_nchw, never the averaged or recoloured image handed out) becomes frame 1, frames 1.. become 2.., the oldest beyond the
+ * depth is dropped; ST_ERR_STATE with depth 0 or without an input; a push at another size than the kept frames' drops those first.
+ * st_get_frames: the depth, the number of frames held and their size (0 x 0 while none is); any pointer may be NULL; it reads only.
+ *
+ * Flows are H * W * 2 host floats (dx, dy) in pixels, of the input's size: `bwd` from the frame being stylised back to frame j, `fwd`
+ * from frame j to the frame being stylised.  They are scanned on the host, as the anchor's map is: a non-finite entry is ST_ERR_ARG.
+ * Frame index: j < 1 or j > depth is ST_ERR_ARG; an empty slot, or kept frames of another size than the input's (or no input), is
+ * ST_ERR_STATE naming both sizes.
+ *
+ * Warp  W(P, f)  of planes P (H, W) by a flow f, every operation in double and rounded once, no contraction, in this order:
+ *   sx = min(max(x + dx, 0), W - 1), sy likewise;  x0 = floor(sx), x1 = min(x0 + 1, W - 1), fx = sx - x0, y0, y1, fy likewise
+ *   top = P[y0, x0] * (1 - fx) + P[y0, x1] * fx;  bottom = P[y1, x0] * (1 - fx) + P[y1, x1] * fx;  out = float(top * (1 - fy) + bottom * fy)
+ * -- jobs.warp_planar, bit for bit.
+ * Reliability  c(bwd, fwd),  in double from the float inputs.  At (y, x): (u, v) = bwd[y, x]; (wx, wy) = W(fwd's two planes, bwd)[y, x],
+ * rounded to float as the warp is.  c = 0 where any of
+ *   outside      x + u < 0, x + u > W - 1, y + v < 0 or y + v > H - 1      (the unclamped sample point leaves the image)
+ *   disoccluded  (wx + u)^2 + (wy + v)^2 > 0.01 * ((wx^2 + wy^2) + (u^2 + v^2)) + 0.5
+ *   boundary     (ux^2 + uy^2) + (vx^2 + vy^2) > 0.01 * (u^2 + v^2) + 0.002,  forward differences clamped to the image:
+ *                ux = bwd[y, min(x + 1, W - 1)].u - u,  uy = bwd[min(y + 1, H - 1), x].u - u,  vx, vy likewise
+ * holds, else 1 (Ruder et al.'s inequalities; the difference scheme and the "outside" rule are this text's).  fwd == NULL: c = 1
+ * everywhere.  With mask_hw (the anchor map's rules: finite, >= 0, scanned on the host) c becomes float(c * mask).  bwd == NULL is no
+ * warp: W(P, NULL) = P, and (u, v) = 0 in the tests above.
+ *
+ * st_set_input_from_frame: x = W(frame j, bwd); everything else of the state is what st_set_input_nchw of those planes leaves (the
+ * iterate average is cleared, captured graphs are stale, nothing is re-made at the equal size).
+ * st_anchor_from_frame, accumulate == 0: the anchor planes are W(frame j, bwd), the map is c when fwd or mask_hw is given and absent
+ * otherwise, the term is on with `weight` (st_set_anchor's rules) -- afterwards every observer (st_get_anchor, st_get_anchor_terms,
+ * st_trace_len, every evaluation) answers as after st_set_anchor_nchw of those planes and that map.  The buffers are made and filled
+ * first: when that fails nothing has changed.  accumulate == 1 (the long-term term) needs the term on at the input's size with a map
+ * (else ST_ERR_STATE) and `weight` equal to the weight in force (else ST_ERR_ARG), and composes per pixel, in float:
+ *   m = max(c - M, 0);   ax = m > 0 ? W(frame j, bwd) : ax  (the three channels);   M = M + m
+ * so that calls in the order j = 1, 2, 4, .. give every pixel the newest frame that reliably shows it.  Warp, reliability, map product
+ * and composition are ONE launch per call.
+ * Every call of the block but st_get_frames bumps the epoch and is refused (ST_ERR_STATE) while a pipelined iteration is in flight and
+ * on a tile-configured context (where st_frames_keep(ctx, 0) stays allowed). */
+int st_frames_keep(st_ctx* ctx, int depth);
+int st_frame_push(st_ctx* ctx);
+int st_get_frames(st_ctx* ctx, int* depth, int* count, int* H, int* W);
+int st_set_input_from_frame(st_ctx* ctx, int j, const float* bwd_flow_hw2);
+int st_anchor_from_frame(st_ctx* ctx, int j, const float* bwd_flow_hw2, const float* fwd_flow_hw2, const float* mask_hw, double weight,
+                         int accumulate);
 /* Steps so far that ran as a hipGraph replay.  Opt-in (environment ST2_GRAPH=1; ST2_GRAPH_MAX_PX=<edge>, default 768):
  * steady-state Adam steps are captured once per ping-pong parity and replayed, bit-identical to plain launches.  Measured
  * on MI355X it is no faster (the step is bound by the dependent kernels' execution latency), hence off by default. */

@@ -99,6 +99,11 @@ PROTOTYPES = {
     'st_set_anchor_nchw': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_double]),
     'st_get_anchor': (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_double)]),
     'st_get_anchor_terms': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    'st_frames_keep': (c_int, [c_void_p, c_int]),
+    'st_frame_push': (c_int, [c_void_p]),
+    'st_get_frames': (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    'st_set_input_from_frame': (c_int, [c_void_p, c_int, c_void_p]),
+    'st_anchor_from_frame': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_double, c_int]),
     'st_graph_replays':(c_int, [c_void_p, POINTER(c_longlong)]),
     'st_live_bytes': (c_int, [POINTER(c_longlong), POINTER(c_longlong)]),
     'st_lbfgs_inv_hv': (c_int, [c_void_p, c_int, POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_void_p]),

@@ -41,6 +41,7 @@ enum ProfClass { P_CONV_FWD, P_CONV_DGRAD, P_POOL_FWD, P_POOL_BWD, P_GRAM, P_GRA
                  P_AVEPOOL_FWD, P_AVEPOOL_BWD, P_GRAM_SPLIT, P_STYLE_GRAD_SPLIT, P_AVEPOOL_BWD_MAP16,
                  P_LAP_POOL, P_LAP_STENCIL, P_LAP_GRAD,      // the launches of the Laplacian term (laplacian.hip), the targets' included
                  P_ANCHOR,                                   // anchor_k, the one launch of the anchor term (anchor.hip)
+                 P_FRAMES,                                   // frames_k, the one launch of st_set_input_from_frame / st_anchor_from_frame (frames.hip)
                  P_COUNT };
 extern const char* const kProfNames[P_COUNT];
 struct ProfRec { int cls; hipEvent_t a, b; double flops, bytes; };
@@ -316,6 +317,14 @@ struct st_ctx {
         bool evaluated = false, have_grad = false; // extra holds the last evaluation's
         bool resized = false;                      // ... it did, until the input was resized
     } anchor;
+    // frame sequences (st_frames_keep .. st_anchor_from_frame; engine_frames.cpp, frames_plan.h)
+    struct Frames {
+        int depth = 0;                             // 0: nothing is kept and every buffer below is empty
+        int count = 0;                             // frames held: slot[0 .. count) are frames 1 .. count, the newest first
+        int H = 0, W = 0;                          // their size (count > 0)
+        DevBuf<float> slot[kFramesMaxDepth];       // raw iterates (3, H, W); allocated by the pushes
+        DevBuf<float> stage;                       // the caller's flows and map on their way to frames_k: [bwd | fwd | mask], grown on demand
+    } frames;
     // tile-sharded mode (BASELINE config 5): this context holds ONE window of a larger image
     struct Tile : TileGeom {
         bool on = false;

@@ -8,6 +8,7 @@
 #include "emit_plan.h"
 #include "laplacian_plan.h"
 #include "anchor_plan.h"
+#include "frames_plan.h"
 
 namespace st2 {
 
@@ -376,6 +377,17 @@ hipError_t launch_lap_grad(const LapGradArgs& a, int grid, int grid_vec, hipStre
 // aligned (grid_vec workgroups), one pixel per thread and trip otherwise (grid); *n_partial: the slots written per row
 struct AnchorArgs { const float* x; const float* ax; const float* m; const float* g_lap; float* extra; float* part; size_t plane; int W; float w; };
 hipError_t launch_anchor(const AnchorArgs& a, int grid, int grid_vec, int* n_partial, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------
+// Frame sequences (frames.hip; frames_plan.h has the validation and the grids): src a kept frame (3, H, W), dst planes of (3, H, W),
+// plane = H * W; bwd, fwd flows of (H, W, 2) as (dx, dy), mask and map of (H, W).
+// ------------------------------------------------------------------------------------------
+// dst = W(src, bwd) (bwd == NULL: src itself); with fwd or mask, map = float(c(bwd, fwd) * mask) (c = 1 without fwd, no product without
+// mask) -- the definitions of include/st2.h, in double.  accumulate: per pixel m = max(c - map, 0), dst takes the new sample where
+// m > 0 and keeps its value elsewhere, map += m (map is then required and read).  16-byte stores where W % 4 == 0 and dst and map are
+// aligned (grid_vec workgroups), one pixel per thread and trip otherwise (grid)
+struct FramesArgs { const float* src; const float* bwd; const float* fwd; const float* mask; float* dst; float* map; int H, W; size_t plane; };
+hipError_t launch_frames(const FramesArgs& a, int accumulate, int grid, int grid_vec, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
 // trace finalisation: one tiny kernel turns the partial sums of an opfunc into the trace scalars

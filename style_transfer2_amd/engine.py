@@ -39,6 +39,28 @@ def _image_arg(image):
     return np.ascontiguousarray(arr, F32), 0
 
 
+def _map_arg(mask, h, w):
+    """A per-pixel map of the anchor term -> contiguous float32 (h, w): float as it is, uint8 divided by 255, bool as 0 / 1; None stays."""
+    if mask is None:
+        return None
+    mask = np.asarray(mask)
+    if mask.shape != (h, w):
+        raise ValueError('the map must be (%d, %d), got %s' % (h, w, mask.shape))
+    if mask.dtype == np.uint8:
+        mask = mask.astype(F32) / F32(255)
+    return np.ascontiguousarray(mask, F32)                  # (bool: 0 / 1)
+
+
+def _flow_arg(flow, h, w, name='flow'):
+    """An optical flow (h, w, 2) of (dx, dy) in pixels -> contiguous float32; None stays."""
+    if flow is None:
+        return None
+    flow = np.asarray(flow)
+    if flow.shape != (h, w, 2):
+        raise ValueError('the %s must be (%d, %d, 2), got %s' % (name, h, w, flow.shape))
+    return np.ascontiguousarray(flow, F32)
+
+
 def cov_full(upper):
     """The six values RR, RG, RB, GG, GB, BB of the C ABI -> symmetric (3, 3) float64."""
     rr, rg, rb, gg, gb, bb = (float(v) for v in upper)
@@ -541,13 +563,7 @@ class Engine:
         else:
             arr, u8 = _image_arg(arr)
             h, w = arr.shape[:2]
-        if mask is not None:
-            mask = np.asarray(mask)
-            if mask.shape != (h, w):
-                raise ValueError('the map must be (%d, %d), got %s' % (h, w, mask.shape))
-            if mask.dtype == np.uint8:
-                mask = mask.astype(F32) / F32(255)
-            mask = np.ascontiguousarray(mask, F32)          # (bool: 0 / 1)
+        mask = _map_arg(mask, h, w)
         if planar:
             check(self.lib.st_set_anchor_nchw(self._ctx, _ptr(arr), h, w, _ptr(mask), float(weight)))
         else:
@@ -572,6 +588,38 @@ class Engine:
         extra = np.empty((1, 3, h, w), F32) if want_extra else None
         check(self.lib.st_get_anchor_terms(self._ctx, _ptr(ax), _ptr(mask), _ptr(extra)))
         return ax, mask, extra
+
+    # -- frame sequences (st2.h: st_frames_keep .. st_anchor_from_frame) ------------------------------------------------------------
+    def frames_keep(self, depth):
+        """Keep up to `depth` (0 .. 8) earlier iterates on the device; a smaller depth drops the oldest beyond it, 0 frees them."""
+        check(self.lib.st_frames_keep(self._ctx, int(depth)))
+
+    def frame_push(self):
+        """The current raw iterate (get_input_nchw: never the averaged or recoloured image) becomes frame 1, frames 1.. become 2..,
+        the oldest beyond the depth is dropped.  A push at another size than the kept frames' drops those first."""
+        check(self.lib.st_frame_push(self._ctx))
+
+    def frames(self):
+        """A dict with 'depth', 'count' (frames held) and 'size' (H, W) of the kept frames, (0, 0) while none is held."""
+        depth, count, h, w = c_int(), c_int(), c_int(), c_int()
+        check(self.lib.st_get_frames(self._ctx, byref(depth), byref(count), byref(h), byref(w)))
+        return {'depth': depth.value, 'count': count.value, 'size': (h.value, w.value)}
+
+    def set_input_from_frame(self, j, flow=None):
+        """The iterate becomes kept frame j, warped on the device by `flow` ((H, W, 2) of (dx, dy), from the frame being stylised back to
+        frame j; the arithmetic of jobs.warp_planar, bit for bit); None: a copy.  The rest of the state as after set_input_nchw."""
+        h, w = self.input_shape()
+        check(self.lib.st_set_input_from_frame(self._ctx, int(j), _ptr(_flow_arg(flow, h, w))))
+
+    def anchor_from_frame(self, j, flow=None, forward_flow=None, mask=None, weight=1.0, accumulate=False):
+        """The anchor term from kept frame j, in one launch on the device: the anchor is the frame warped by `flow` (None: as it is); with
+        forward_flow (from frame j to the frame being stylised) the map is the flow's reliability (st2.h: 0 where the sample leaves the
+        image, at disocclusions and at motion boundaries, else 1), times `mask` where one is given (set_anchor's conversions); without
+        either there is no map.  accumulate=True composes into the anchor that is there (it needs one with a map, of the same weight):
+        pixels its map leaves free take this frame's sample and reliability -- the long-term term, called for j = 1, 2, 4, .. in turn."""
+        h, w = self.input_shape()
+        check(self.lib.st_anchor_from_frame(self._ctx, int(j), _ptr(_flow_arg(flow, h, w)), _ptr(_flow_arg(forward_flow, h, w, 'forward flow')),
+                                            _ptr(_map_arg(mask, h, w)), float(weight), 1 if accumulate else 0))
 
     def set_style_nchw(self, x):
         """set_style for an already-preprocessed (1, 3, H, W) image; no colour transform is applied."""

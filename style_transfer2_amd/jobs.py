@@ -50,7 +50,7 @@ def load_mask(path, hw):
 
 def run_job(transfer, content, style, iterations, size=None, style_size=None, optimizer='adam', step_size=None,
             weights=None, params=None, init=None, seed=0, callback=None, iterate_average=None, original_colors=None,
-            match_style_colors=None, laplacian=None, anchor=None, init_nchw=None):
+            match_style_colors=None, laplacian=None, anchor=None, init_nchw=None, init_frame=None, anchor_frames=None):
     """One whole stylisation: content/style are PIL images or HxWx3 arrays.  Returns the final HxWx3 float32
     image.  Mirrors app.init_arrays + 'start': SetImages(reset) -> SetWeights -> SetOptimizer -> iterate.
     iterate_average: a decay in (0, 1) makes every image handed out (the callback's, the result) the bias-corrected running mean of
@@ -64,8 +64,18 @@ def run_job(transfer, content, style, iterations, size=None, style_size=None, op
     anchor: an (image, mask, weight) tuple turns the anchor term on (StyleTransfer.set_anchor: a per-pixel weighted pull toward the
     image, which has the content's size; HxWx3, or preprocessed planes (3, H, W)); False turns it off; None leaves the engine as it is.
     init_nchw: preprocessed planes (3, H, W) or (1, 3, H, W) to start from in place of `init` (an iterate read with
-    Engine.get_input_nchw, for one)."""
+    Engine.get_input_nchw, for one).
+    init_frame: (j, flow) starts from kept frame j of the engine (Engine.frame_push), warped on the device by flow (or None) in place
+    of `init` (Engine.set_input_from_frame); not together with init_nchw.
+    anchor_frames: (weight, [(j, flow, forward_flow, mask), ...]) turns the anchor term on from kept frames (StyleTransfer.
+    anchor_from_frame): the first entry sets the anchor, the others accumulate into it; not together with anchor."""
     from .device_optimizers import AdamOptimizer, LBFGSOptimizer
+    if init_frame is not None and init_nchw is not None:
+        raise ValueError('init_frame and init_nchw are two ways to start: give one')
+    if anchor_frames is not None and anchor is not None:
+        raise ValueError('anchor_frames and anchor are two ways to set the anchor term: give one')
+    if anchor_frames is not None and not anchor_frames[1]:
+        raise ValueError('anchor_frames: at least one (j, flow, forward_flow, mask) entry')
     if isinstance(content, Image.Image):
         content = np.uint8(resize_to_fit(content, size or max(content.size)))
     if isinstance(style, Image.Image):
@@ -73,6 +83,8 @@ def run_job(transfer, content, style, iterations, size=None, style_size=None, op
     if init_nchw is not None:
         init_nchw = np.ascontiguousarray(init_nchw, np.float32).reshape((1, 3) + tuple(content.shape[:2]))
         init = np.zeros(content.shape[:2] + (3,), np.uint8)    # (sizes the engine's buffers; the planes follow)
+    elif init_frame is not None:
+        init = np.zeros(content.shape[:2] + (3,), np.uint8)    # (sizes the engine's buffers; the warped frame follows)
     elif init is None:
         init = noise_image(content.shape[:2], seed)
     if original_colors is not None:
@@ -82,6 +94,8 @@ def run_job(transfer, content, style, iterations, size=None, style_size=None, op
     transfer.set_input(init)
     if init_nchw is not None:
         transfer.engine.set_input_nchw(init_nchw)
+    if init_frame is not None:
+        transfer.engine.set_input_from_frame(*init_frame)
     transfer.set_content(content)
     transfer.set_style(style)
     transfer.reset()
@@ -99,6 +113,10 @@ def run_job(transfer, content, style, iterations, size=None, style_size=None, op
         else:
             image, mask, weight = anchor
             transfer.set_anchor(image, mask, weight)
+    if anchor_frames is not None:
+        weight, entries = anchor_frames
+        for k, (j, flow, forward_flow, mask) in enumerate(entries):
+            transfer.anchor_from_frame(j, flow, forward_flow, mask, weight, accumulate=k > 0)
     if not transfer.start():
         raise RuntimeError('job could not start: inconsistent images')
     image = None
@@ -208,27 +226,65 @@ def warp_planar(x_chw, flow_hw2):
     return (top * (1 - fy) + bottom * fy).astype(np.float32)
 
 
-def run_frames(transfer, frames, style, iterations, anchor_weight, flows=None, masks=None, first_iterations=None, **job_kwargs):
+def run_frames(transfer, frames, style, iterations, anchor_weight, flows=None, masks=None, first_iterations=None, forward_flows=None,
+               long_term=None, **job_kwargs):
     """A frame sequence with temporal consistency (Ruder et al.): frame 0 is a plain run_job (first_iterations of them where given);
-    frame t > 0 starts from the raw iterate of frame t - 1 (Engine.get_input_nchw: never the averaged or recoloured image handed
-    out), warped by flows[t] (warp_planar; (H, W, 2), from frame t back to frame t - 1) where one is given, and is pulled toward that
-    same image by the anchor term with the map masks[t] (the flow's reliability; None: 1 everywhere) and anchor_weight.
-    frames: HxWx3 arrays of one size; flows, masks: sequences as long as frames (entry 0 is not read) or None.
+    frame t > 0 starts from the raw iterate of frame t - 1 (kept on the device, Engine.frame_push: never the averaged or recoloured
+    image handed out), warped by flows[t] ((H, W, 2), from frame t back to frame t - 1; the arithmetic of warp_planar) where one is
+    given, and is pulled toward that same image by the anchor term with anchor_weight and a map.  The seam between two frames runs on
+    the device (Engine.set_input_from_frame, Engine.anchor_from_frame): no iterate crosses to the host.
+    masks[t]: the caller's map (the flow's reliability; None: 1 everywhere).  forward_flows[t] ((H, W, 2), from frame t - 1 to frame t)
+    turns the derived reliability on (st2.h: forward / backward consistency, motion boundaries, samples outside the image), which
+    masks[t] multiplies where given; it needs flows[t].
+    long_term: {j: (flows_j, forward_flows_j or None)} with integer 2 <= j <= 8: flows_j[t] goes from frame t back to frame t - j and is
+    read for t >= j (a None entry skips that pair).  Pixels the map of frame t - 1 leaves free are then anchored to the newest of those
+    older stylised frames that reliably shows them (the j in ascending order): Ruder's long-term consistency as one anchor term.  It
+    needs a map from forward_flows or masks at every frame it applies to.
+    frames: HxWx3 arrays of one size; flows, masks, forward_flows, flows_j: sequences as long as frames (entry 0 is not read) or None.
     job_kwargs go to every run_job.  Returns the list of results."""
     frames = [np.asarray(f) for f in frames]
     if len({f.shape for f in frames}) > 1:
         raise ValueError('the frames differ in size: %s' % sorted({f.shape[:2] for f in frames}))
-    for name, seq in (('flows', flows), ('masks', masks)):
-        if seq is not None and len(seq) != len(frames):
+    hw = frames[0].shape[:2] if frames else (0, 0)
+    older = []                                             # (j, flows_j, forward_flows_j), ascending
+    for j, pair in (long_term or {}).items():
+        if isinstance(j, bool) or not isinstance(j, (int, np.integer)) or not 2 <= j <= 8:
+            raise ValueError('long_term: the keys are integers from 2 to 8, got %r' % (j,))
+        if not isinstance(pair, (tuple, list)) or len(pair) != 2 or pair[0] is None:
+            raise ValueError('long_term[%d]: a (flows, forward_flows or None) pair' % j)
+        older.append((int(j), pair[0], pair[1]))
+    older.sort(key=lambda e: e[0])
+    named = [('flows', flows, 1, 2), ('masks', masks, 1, 0), ('forward_flows', forward_flows, 1, 2)]
+    for j, fl, ff in older:
+        named += [('long_term[%d] flows' % j, fl, j, 2), ('long_term[%d] forward_flows' % j, ff, j, 2)]
+    for name, seq, first, last_axis in named:
+        if seq is None:
+            continue
+        if len(seq) != len(frames):
             raise ValueError('%s: one entry per frame (entry 0 is not read), got %d for %d frames' % (name, len(seq), len(frames)))
+        want = tuple(hw) + ((last_axis,) if last_axis else ())
+        for t in range(first, len(frames)):
+            if seq[t] is not None and np.shape(seq[t]) != want:
+                raise ValueError('%s[%d]: %s for frames of %s, expected %s' % (name, t, np.shape(seq[t]), tuple(hw), want))
+    for t in range(1, len(frames)):
+        if forward_flows is not None and forward_flows[t] is not None and (flows is None or flows[t] is None):
+            raise ValueError('forward_flows[%d] without flows[%d]: the reliability needs both directions' % (t, t))
+        for j, fl, ff in older:
+            if t < j or fl[t] is None:
+                if t >= j and ff is not None and ff[t] is not None:
+                    raise ValueError('long_term[%d] forward_flows[%d] without its flows[%d]' % (j, t, t))
+                continue
+            if (forward_flows is None or forward_flows[t] is None) and (masks is None or masks[t] is None):
+                raise ValueError('long_term at frame %d needs a map of frame %d: give forward_flows[%d] or masks[%d]' % (t, t - 1, t, t))
+    transfer.engine.frames_keep(max([1] + [j for j, _, _ in older]))
     results = []
     for t, frame in enumerate(frames):
         if t == 0:
             results.append(run_job(transfer, frame, style, first_iterations or iterations, anchor=False, **job_kwargs))
-            continue
-        prev = transfer.engine.get_input_nchw()[0]
-        if flows is not None and flows[t] is not None:
-            prev = warp_planar(prev, flows[t])
-        mask = masks[t] if masks is not None else None
-        results.append(run_job(transfer, frame, style, iterations, anchor=(prev[None], mask, anchor_weight), init_nchw=prev, **job_kwargs))
+        else:
+            flow = flows[t] if flows is not None else None
+            entries = [(1, flow, forward_flows[t] if forward_flows is not None else None, masks[t] if masks is not None else None)]
+            entries += [(j, fl[t], ff[t] if ff is not None else None, None) for j, fl, ff in older if t >= j and fl[t] is not None]
+            results.append(run_job(transfer, frame, style, iterations, init_frame=(1, flow), anchor_frames=(anchor_weight, entries), **job_kwargs))
+        transfer.engine.frame_push()
     return results

@@ -196,6 +196,12 @@ class StyleTransfer:
         self._anchor_on = image is not None
         self.objective_changed()
 
+    def anchor_from_frame(self, j, flow=None, forward_flow=None, mask=None, weight=1.0, accumulate=False):
+        """The anchor term from a kept frame, warped and weighted on the device (Engine.anchor_from_frame)."""
+        self.engine.anchor_from_frame(j, flow, forward_flow, mask, weight, accumulate)
+        self._anchor_on = True
+        self.objective_changed()
+
     def _push_weights(self):
         cols = [[self.cells[k][r] for r in self.rows] for k in LOSS_NAMES]
         self.engine.set_weights(self.rows, cols[0], cols[1], cols[2],

@@ -1,10 +1,17 @@
 #!/usr/bin/env python3
 """Headless stylisation of a frame sequence on one MI355X, with temporal consistency:
-    stylize_frames.py f000.png f001.png ... --style s.jpg --out-dir out [--flows DIR] [--masks DIR] [--anchor-weight W]
+    stylize_frames.py f000.png f001.png ... --style s.jpg --out-dir out [--flows DIR] [--forward-flows DIR] [--masks DIR]
+                      [--long-term 2,4] [--anchor-weight W]
 Frame 0 is a plain job.  Every later frame starts from the previous frame's iterate, warped by the optical flow where one is given, and
-is pulled toward it by the anchor term (st_set_anchor; jobs.run_frames) with the weight W and the frame's map.
+is pulled toward it by the anchor term (st_set_anchor; jobs.run_frames) with the weight W and the frame's map.  The seam between two
+frames runs on the device (st_set_input_from_frame, st_anchor_from_frame).
 --flows DIR: <stem>.npy per frame after the first, (H, W, 2) float (dx, dy) from that frame back to the one before, at the size the
-frames are stylised at.  --masks DIR: <stem>.npy ((H, W) values >= 0) or <stem>.png (0 .. 255 -> 0 .. 1): the flow's reliability.
+frames are stylised at.  --masks DIR: <stem>.npy ((H, W) values >= 0) or <stem>.png (0 .. 255 -> 0 .. 1): the flow's reliability, given.
+--forward-flows DIR: <stem>.npy per frame after the first, the flow from the frame before to that frame: the reliability is then derived
+on the device (forward / backward consistency, motion boundaries, samples outside the image: st2.h) and multiplied by the frame's map
+where --masks has one.  --long-term 2,4: pixels the map leaves free are anchored to the stylised frame 2, then 4 frames back, through
+<stem>.b<j>.npy under --flows (from the frame back to the one j before; frames from the j-th on; a missing file skips that pair) and,
+where it exists, <stem>.f<j>.npy under --forward-flows (the flow from the frame j before to the frame).
 Flows and maps are the caller's: nothing here estimates them.  The results go to <out-dir>/<stem>.png."""
 import argparse
 import os
@@ -21,6 +28,8 @@ def parser():
     ap.add_argument('--out-dir', required=True)
     ap.add_argument('--flows', default='', metavar='DIR')
     ap.add_argument('--masks', default='', metavar='DIR')
+    ap.add_argument('--forward-flows', default='', metavar='DIR', help='<stem>.npy: the flow from the frame before; derives the reliability on the device')
+    ap.add_argument('--long-term', type=long_term_arg, default=[], metavar='J,J', help='earlier frames to anchor uncovered pixels to, e.g. 2,4 (each 2 .. 8)')
     ap.add_argument('--anchor-weight', type=float, default=1.0, metavar='W')
     ap.add_argument('--iters', type=int, default=200, help='iterations of every frame after the first')
     ap.add_argument('--first-iters', type=int, default=0, metavar='N', help='iterations of the first frame (default: --iters)')
@@ -36,6 +45,31 @@ def parser():
     return ap
 
 
+def long_term_arg(text):
+    """'2,4' -> [2, 4]: distinct integers from 2 to 8, ascending."""
+    try:
+        js = sorted(int(part) for part in text.split(',') if part.strip())
+    except ValueError:
+        raise argparse.ArgumentTypeError('--long-term: integers separated by commas, got %r' % text)
+    if not js or len(set(js)) != len(js) or js[0] < 2 or js[-1] > 8:
+        raise argparse.ArgumentTypeError('--long-term: distinct integers from 2 to 8, got %r' % text)
+    return js
+
+
+def long_term_files(flows_dir, forward_dir, stems, js):
+    """{j: ([backward flow file or None per frame], [forward flow file or None per frame] or None)}: <stem>.b<j>.npy under flows_dir for
+    the frames from the j-th on, <stem>.f<j>.npy under forward_dir; a file that does not exist is None."""
+    def existing(directory, name):
+        path = os.path.join(directory, name)
+        return path if os.path.exists(path) else None
+    out = {}
+    for j in js:
+        back = [existing(flows_dir, '%s.b%d.npy' % (stem, j)) if t >= j else None for t, stem in enumerate(stems)]
+        fwd = [existing(forward_dir, '%s.f%d.npy' % (stem, j)) if t >= j and back[t] else None for t, stem in enumerate(stems)] if forward_dir else None
+        out[j] = (back, fwd)
+    return out
+
+
 def side_file(directory, stem, endings):
     for ending in endings:
         path = os.path.join(directory, stem + ending)
@@ -47,6 +81,10 @@ def side_file(directory, stem, endings):
 def main(argv=None):
     ap = parser()
     args = ap.parse_args(argv)
+    if args.forward_flows and not args.flows:
+        ap.error('--forward-flows needs --flows: the reliability takes both directions')
+    if args.long_term and (not args.flows or not (args.forward_flows or args.masks)):
+        ap.error('--long-term needs --flows (the <stem>.b<j>.npy files) and a map from --forward-flows or --masks')
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import style_transfer2_amd as st2
     from style_transfer2_amd import jobs, weights as st2_weights
@@ -59,6 +97,13 @@ def main(argv=None):
         flows = [None] + [np.load(side_file(args.flows, stem, ('.npy',))) for stem in stems[1:]]
     if args.masks:
         masks = [None] + [jobs.load_mask(side_file(args.masks, stem, ('.npy', '.png')), hw) for stem in stems[1:]]
+    forward_flows = long_term = None
+    if args.forward_flows:
+        forward_flows = [None] + [np.load(side_file(args.forward_flows, stem, ('.npy',))) for stem in stems[1:]]
+    if args.long_term:
+        load = lambda paths: [np.load(path) if path else None for path in paths]      # noqa: E731
+        long_term = {j: (load(back), load(fwd) if fwd else None)
+                     for j, (back, fwd) in long_term_files(args.flows, args.forward_flows, stems, args.long_term).items()}
     style = jobs.load_rgb(args.style)
     style = np.uint8(jobs.resize_to_fit(style, args.style_size or args.size))
 
@@ -71,7 +116,7 @@ def main(argv=None):
         params = st2_weights.he_normal(st2.VGG19_TOPOLOGY, seed=0)
     job = st2.StyleTransfer(st2.HipModel(params, device=args.gpu, precision=args.precision, conv_algo=args.conv_algo, gram_algo=args.gram_algo,
                                          pool_algo=args.pool_algo))
-    results = jobs.run_frames(job, frames, style, args.iters, args.anchor_weight, flows=flows, masks=masks,
+    results = jobs.run_frames(job, frames, style, args.iters, args.anchor_weight, flows=flows, masks=masks, forward_flows=forward_flows, long_term=long_term,
                               first_iterations=args.first_iters or None, optimizer=args.optimizer)
     os.makedirs(args.out_dir, exist_ok=True)
     for stem, image in zip(stems, results):
