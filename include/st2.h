@@ -124,6 +124,18 @@ int st_gram(st_ctx* ctx, int index, float* out);
  * after an evaluation that knew the style norm; diff where the style term rode on the data-gradient conv above the blob (bf16 flow with
  * a gradient wanted, ST2_STYLE_FUSE: nothing was written) or after st_backward overwrote it. */
 int st_get_layer_terms(st_ctx* ctx, int index, float* D, float* raw_S, float* diff, float norms[3]);
+/* Test hook: tap the RUNNING diff of blob `index` (-1: off).  The diffs of a backward live in ping-pong buffers that the next launch
+ * overwrites, and the bf16 flow often writes them in bf16 only; while a tap is set, every st_opfunc evaluation with out_grad enqueues --
+ * right after the launch whose output is the diff of that blob -- device-to-device copies of exactly what that launch wrote (the fp32
+ * diff, the channel-blocked bf16 diff [C/8][hw][8], or both) into two buffers the context owns, sized on demand.  No kernel, route or
+ * plan changes: with the tap off an evaluation launches what it launched before, with it on the same launches plus the copies.  Only
+ * st_opfunc honours the tap: st_step / st_step_begin are refused (ST_ERR_STATE, before anything is enqueued) while one is set, and so
+ * are st_tap_diff on a tile-configured context and st_tile_configure under a tap.  st_get_tapped_diff waits for the stream and copies
+ * (no epoch bump, no allocation): out32 receives C*h*w floats when *have32, out16 the ceil(C/8)*8*h*w bf16 bit patterns when *have16
+ * (any pointer may be NULL).  It refuses (ST_ERR_STATE, the message names the blob) until an evaluation with a gradient whose backward
+ * produced that diff has completed since the tap was set, and after the iterate was resized. */
+int st_tap_diff(st_ctx* ctx, int index);
+int st_get_tapped_diff(st_ctx* ctx, float* out32, uint16_t* out16, int* have32, int* have16);
 
 /* ---- image slots: StyleTransfer.set_input / set_content / set_style (worker.py:191-218) ------- */
 /* preprocess (worker.py:63-66) + upload.  is_u8: 1 = uint8 HWC, 0 = float32 HWC. */

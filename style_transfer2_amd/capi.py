@@ -58,6 +58,8 @@ PROTOTYPES = {
     'st_backward': (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_void_p), c_void_p]),
     'st_gram': (c_int, [c_void_p, c_int, c_void_p]),
     'st_get_layer_terms': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, POINTER(c_float)]),
+    'st_tap_diff': (c_int, [c_void_p, c_int]),
+    'st_get_tapped_diff': (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int), POINTER(c_int)]),
     'st_set_input': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int]),
     'st_set_content': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int]),
     'st_set_style': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int]),

@@ -323,6 +323,20 @@ int backward_chain(st_ctx* c, int top, const float* top_diff, const std::vector<
         case B_NONE:
             return fail(ST_ERR_STATE, "internal: no route for the backward of layer %s", L.name.c_str());
         }
+        if (c->tap.armed && c->tap.blob == below) {        // test hook st_tap_diff: exactly what this launch wrote, before the next one overwrites it
+            DiffTap& t = c->tap;
+            const size_t hwb = (size_t)Hb * Wb;
+            if (r.out32) {
+                ST_TRY(t.d32.reserve((size_t)Cb * hwb));
+                HIP_TRY(hipMemcpyAsync(t.d32, dst, (size_t)Cb * hwb * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+            }
+            if (r.out16) {
+                ST_TRY(t.d16.reserve(act16_elems(Cb, hwb)));
+                HIP_TRY(hipMemcpyAsync(t.d16, dst16, act16_elems(Cb, hwb) * sizeof(unsigned short), hipMemcpyDeviceToDevice, c->stream));
+            }
+            t.have32 = r.out32; t.have16 = r.out16; t.C = Cb; t.h = Hb; t.w = Wb;
+            t.captured = true;
+        }
         cur = r.out32 ? dst : nullptr;
         cur16 = r.out16 ? dst16 : nullptr;
     }
@@ -338,6 +352,7 @@ int ensure_input_buffers(st_ctx* c, int H, int W)
     // work buffers by the new one): the hooks refuse until the next forward
     c->act.valid_to = -1;
     if (c->lt.any) { c->lt.any = false; c->lt.resized = true; }      // (st_get_layer_terms: the inject buffers and stmp go below)
+    if (c->tap.have) { c->tap.have = false; c->tap.resized = true; }  // (st_get_tapped_diff: the copy is that of the old geometry)
     lap_input_resized(c);
     anchor_input_resized(c);
     const size_t n3 = (size_t)3 * H * W;

@@ -167,6 +167,21 @@ struct LayerTerms {
     std::vector<char> norm_ok;                     // per blob * 3: the norm was known when the evaluation ended
     void begin(int nb) { any = resized = false; style_blob = raw_blob = -1; n.assign(nb, 0); C.assign(nb, 0); diff.assign(nb, LT_NONE); norm_ok.assign((size_t)nb * 3, 0); }
 };
+
+// ------------------------------------------------------------------------------------- the tapped diff (test hook)
+// st_tap_diff: the running diff of ONE blob, copied out of the backward's ping-pong buffers right after the launch that wrote it
+// (backward_chain), in the forms that launch wrote.  Off (blob < 0) nothing is enqueued and nothing is allocated.
+struct DiffTap {
+    int blob = -1;                                 // the tapped blob; -1: off
+    bool armed = false;                            // inside an st_opfunc evaluation with a gradient: backward_chain copies
+    bool captured = false;                         // ... and did, in this evaluation
+    bool have = false;                             // an evaluation with a gradient has completed since the tap was set, and copied
+    bool resized = false;                          // ... it had, until the iterate was resized
+    bool have32 = false, have16 = false;           // the forms the launch wrote (BwdRoute::out32 / out16)
+    int C = 0, h = 0, w = 0;                       // the blob's shape in that evaluation
+    DevBuf<float> d32;                             // [C][hw]
+    DevBuf<unsigned short> d16;                    // channel-blocked [C/8][hw][8]
+};
 }  // namespace st2e
 
 using namespace st2e;
@@ -219,6 +234,7 @@ struct st_ctx {
     std::vector<DevBuf<unsigned short>> sfuse_w;
     std::vector<const unsigned short*> sf_in, sf_w;
     LayerTerms lt;                                 // test hook st_get_layer_terms: whose data dbuf, stmp and the inject buffers hold
+    DiffTap tap;                                   // test hook st_tap_diff / st_get_tapped_diff
     DevBuf<float> conv_scratch;                    // split-K partial sums of Winograd launches
     // hipGraph replay of the steady-state Adam step (launch-bound regime: small images)
     unsigned long long epoch = 0;                  // bumped by every API call that can change what a step launches

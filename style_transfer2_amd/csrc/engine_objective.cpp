@@ -283,6 +283,42 @@ int st_get_layer_terms(st_ctx* c, int index, float* D, float* raw_S, float* diff
     return ST_OK;
 }
 
+// test hook: tap the running diff of one blob (backward_chain copies what the launch that produces it wrote); -1 turns it off
+int st_tap_diff(st_ctx* c, int index)
+{
+    if (c) c->epoch++;       // anything but st_step may change what a step launches: captured step graphs are stale
+    if (!c || index < -1 || index >= c->nb) return fail(ST_ERR_ARG, "bad argument");
+    if (index >= 0 && c->tile.on) return fail(ST_ERR_STATE, "the diff tap does not run on a tile-configured context");
+    if (c->pipe.count) return fail(ST_ERR_STATE, "%d pipelined iteration(s) in flight: st_step_end first", c->pipe.count);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));              // (a copy of the last tapped evaluation may still be in flight)
+    c->tap = DiffTap{};
+    c->tap.blob = index;
+    return ST_OK;
+}
+
+// test hook: the copy the last tapped evaluation made.  Reads only: no epoch bump, no allocation.
+int st_get_tapped_diff(st_ctx* c, float* out32, uint16_t* out16, int* have32, int* have16)
+{
+    if (!c) return fail(ST_ERR_ARG, "ctx is NULL");
+    const DiffTap& t = c->tap;
+    if (t.blob < 0) return fail(ST_ERR_STATE, "no diff is tapped: st_tap_diff first");
+    const char* name = c->blob_names[t.blob].c_str();
+    if (!t.have)
+        return fail(ST_ERR_STATE, t.resized ? "the iterate was resized after the last tapped evaluation of blob %d (%s): its copy is that of the old size; evaluate again"
+                                            : "no evaluation with a gradient (st_opfunc with out_grad) whose backward produced the diff of blob %d (%s) has completed since the tap was set",
+                    t.blob, name);
+    if ((t.have32 && !t.d32) || (t.have16 && !t.d16)) return fail(ST_ERR_STATE, "internal: the tapped copy of blob %d (%s) is gone", t.blob, name);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const size_t hw = (size_t)t.h * t.w;
+    if (out32 && t.have32) HIP_TRY(hipMemcpy(out32, t.d32, (size_t)t.C * hw * sizeof(float), hipMemcpyDeviceToHost));
+    if (out16 && t.have16) HIP_TRY(hipMemcpy(out16, t.d16, act16_elems(t.C, hw) * sizeof(unsigned short), hipMemcpyDeviceToHost));
+    if (have32) *have32 = t.have32;
+    if (have16) *have16 = t.have16;
+    return ST_OK;
+}
+
 int st_trace_len(st_ctx* c) { return c ? (int)c->active.size() * 6 + 8 + (c->lap.n ? 2 : 0) + (c->anchor.on ? 2 : 0) : 0; }
 
 int st_opfunc(st_ctx* c, float* out_loss, float* out_grad, double* trace)
@@ -293,7 +329,14 @@ int st_opfunc(st_ctx* c, float* out_loss, float* out_grad, double* trace)
     ST_TRY(lap_preflight(c));                                 // refused before anything is enqueued
     ST_TRY(anchor_preflight(c));
     HIP_TRY(hipSetDevice(c->device));
-    ST_TRY(eval_objective(c, c->x[c->cur], out_grad != nullptr, c->grad, false, nullptr));
+    if (c->tap.blob >= 0 && out_grad) {                       // st_tap_diff: this evaluation's backward copies the tapped diff
+        c->tap.armed = true; c->tap.captured = c->tap.have = false;
+        const int rc = eval_objective(c, c->x[c->cur], true, c->grad, false, nullptr);
+        c->tap.armed = false;
+        ST_TRY(rc);
+        c->tap.have = c->tap.captured; c->tap.resized = false;
+    } else
+        ST_TRY(eval_objective(c, c->x[c->cur], out_grad != nullptr, c->grad, false, nullptr));
     if (out_grad) HIP_TRY(hipMemcpyAsync(out_grad, c->grad, (size_t)3 * c->H * c->W * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     return read_trace(c, trace, out_loss);
 }

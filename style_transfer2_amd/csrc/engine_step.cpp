@@ -274,6 +274,7 @@ int st_step(st_ctx* c, float* out_hwc, double* trace, float* out_loss)
     if (!c->x[0]) return fail(ST_ERR_STATE, "no input image");
     if (c->pipe.count) return fail(ST_ERR_STATE, "%d pipelined iteration(s) in flight: st_step_end first", c->pipe.count);
     EmitPlan emit;
+    if (c->tap.blob >= 0) return fail(ST_ERR_STATE, "a diff is tapped (st_tap_diff, blob %d): only st_opfunc evaluations honour the tap; st_tap_diff(ctx, -1) first", c->tap.blob);
     ST_TRY(emit_preflight(c, EMIT_STEP, out_hwc != nullptr, &emit));       // refused before anything is enqueued
     ST_TRY(lap_preflight(c));
     ST_TRY(anchor_preflight(c));
@@ -298,6 +299,7 @@ int st_step_begin(st_ctx* c)
     st_ctx::Pipe& p = c->pipe;
     if (p.count >= 2) return fail(ST_ERR_STATE, "two iterations are already in flight: st_step_end first");
     EmitPlan emit;
+    if (c->tap.blob >= 0) return fail(ST_ERR_STATE, "a diff is tapped (st_tap_diff, blob %d): only st_opfunc evaluations honour the tap; st_tap_diff(ctx, -1) first", c->tap.blob);
     ST_TRY(emit_preflight(c, EMIT_STEP_BEGIN, true, &emit));
     ST_TRY(lap_preflight(c));
     ST_TRY(anchor_preflight(c));

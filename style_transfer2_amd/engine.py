@@ -244,6 +244,30 @@ class Engine:
             out['norms'] = np.array(norms[:], F32)
         return out
 
+    def tap_diff(self, name):
+        """Test hook (st_tap_diff): from now on every opfunc(return_grad=True) copies the running diff of blob `name` right after the
+        launch that wrote it; None turns the tap off.  step() / step_begin() are refused while a tap is set."""
+        check(self.lib.st_tap_diff(self._ctx, -1 if name is None else self._index[name]))
+        self._tapped = name
+
+    def tapped_diff(self):
+        """Test hook (st_get_tapped_diff): {'f32': (1, C, h, w) or None, 'bf16': (1, C, h, w) float32 holding bf16 values or None} --
+        the forms the tapped launch of the last opfunc(return_grad=True) wrote.  StError before such an evaluation has completed
+        and after the iterate was resized."""
+        name = getattr(self, '_tapped', None)
+        if name is None:
+            check(self.lib.st_get_tapped_diff(self._ctx, None, None, None, None))        # (refuses: no diff is tapped)
+        C, h, w = self.blob_shape(name, *self.input_shape())
+        cb = (C + 7) // 8
+        o32, o16 = np.empty((1, C, h, w), F32), np.empty((cb, h * w, 8), np.uint16)
+        h32, h16 = c_int(), c_int()
+        check(self.lib.st_get_tapped_diff(self._ctx, _ptr(o32), _ptr(o16), byref(h32), byref(h16)))
+        out = {'f32': o32 if h32.value else None, 'bf16': None}
+        if h16.value:           # channel-blocked [C/8][hw][8] -> (C, h, w); a bf16 value is the upper half of a float32
+            bits = o16.transpose(0, 2, 1).reshape(cb * 8, h * w)[:C].astype(np.uint32) << 16
+            out['bf16'] = np.ascontiguousarray(bits).view(F32).reshape(1, C, h, w)
+        return out
+
     # -- image slots -------------------------------------------------------------------------------
     def set_input(self, image):
         arr, u8 = _image_arg(image)

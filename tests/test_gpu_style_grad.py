@@ -3,8 +3,8 @@ and the content / deep-dream diffs of layer_elem_k bit for bit -- through st_get
 evaluation left in the engine's own buffers.  The bars are derived in tests/style_grad_oracle.py (and shown reachable, and sharp
 against seeded defects, on the CPU in tests/test_style_grad_oracle_cpu.py); nothing here is fitted to what a kernel returns.
 
-Not covered here: the style term that rides on the bf16 data-gradient conv (ST2_STYLE_FUSE) never materialises S; it stays with the
-A/B test of tests/test_gpu_bf16.py.  ST2_STYLE_GRAD_REPORT=<file> appends the measured figures of every case to that file (the
+The style term that rides on the bf16 data-gradient conv (ST2_STYLE_FUSE) never materialises S: tests/test_gpu_fused_style.py holds it
+to float64 through the diff tap.  ST2_STYLE_GRAD_REPORT=<file> appends the measured figures of every case to that file (the
 record profiles/style_grad_errors.txt was made this way); they are records, not bars."""
 import os
 from ctypes import byref, c_float, c_int, c_void_p
