@@ -381,6 +381,54 @@ int st_get_frames(st_ctx* ctx, int* depth, int* count, int* H, int* W);
 int st_set_input_from_frame(st_ctx* ctx, int j, const float* bwd_flow_hw2);
 int st_anchor_from_frame(st_ctx* ctx, int j, const float* bwd_flow_hw2, const float* fwd_flow_hw2, const float* mask_hw, double weight,
                          int accumulate);
+/* ---- jitter: the network terms evaluated on a randomly rolled iterate ---------------------------------------------------------
+ * Pool windows, Winograd output tiles and the stride-16 grid of the deep layers sit at the same pixels in every iteration; the regular
+ * grid artefacts of DeepDream and Gram-matrix style transfer come from that.  With the mode on, every evaluation shows the network the
+ * iterate rolled by a small shift s = (dy, dx) and rolls the gradient back.  No reference counterpart; this text is the definition.
+ *   roll(P, (dy, dx))[c, y, x] = P[c, (y - dy) mod H, (x - dx) mod W]      (np.roll(P, (dy, dx), (1, 2)); any integers), unroll = roll by -s
+ *   x_s   = roll(x, s)                    x: the preprocessed planar iterate (3, H, W), never moved itself
+ *   F_c,s = content features of roll(cx, s), cx the kept preprocessed content image -- taken by exactly the launches st_set_content_nchw
+ *           of those planes would use, only when an active row carries a content weight, and kept while the shift stays
+ *   scd_loss_s, the per-layer losses, the norms = worker.py:239-279 at x_s against F_c,s and the (unshifted) style targets
+ *   scd   = unroll(d scd_loss_s / d x_s)  what the image pass receives as the network gradient
+ * TV (periodic) and the p-norm (pointwise) are roll-invariant; they, the Laplacian and the anchor term, Adam / L-BFGS, the iterate
+ * average, emission, frames and resampling read and write the unshifted x, in the order and arithmetic they have without the mode.  The
+ * trace keeps its length and layout; its layer entries and scd_* are those of the shifted evaluation.  With no active row nothing is
+ * rolled.  The two rolls are launches of roll_k (jitter.hip), a pure move: 2 x 25.2 MB at 1024^2.  scd_grad, the RMS of the network
+ * gradient, is summed over the planes before the un-roll in the image pass's own order (roll_sumsq_k), so that every layer entry and
+ * scd_* of the trace have the bits of a mode-off evaluation that is given roll(x, s) and roll(cx, s).
+ * Measured at 1024^2 (VGG19, Adam, fp32; profiles/jitter_1024.txt): roll_k 9.0 us per launch (2.8 TB/s); with style rows only 21 us
+ * per 6.98 ms step (0.30 %); with a content row at conv4_2 and a shift that changes every step, one more forward to conv4_2 per step:
+ * 2.46 ms per 7.00 ms step (35 % more time).  A shift that stays (st_set_jitter_shift) pays that forward once.
+ * The shift of step k, in 64-bit unsigned wrap-around arithmetic (splitmix64, output k + 1 from state `seed`):
+ *   mix(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)
+ *   r_k = mix(seed + (k + 1) * 0x9E3779B97F4A7C15)
+ *   dy_k = (int)((r_k >> 32) % (2R + 1)) - R;      dx_k = (int)((r_k & 0xFFFFFFFF) % (2R + 1)) - R
+ * Pinned: r_0..2 for seed 1234567 = 6457827717110365317, 3203168211198807973, 9817491932198370423 (the published splitmix64 vectors);
+ *   (dy, dx) for seed 7, R 3, k = 0..7 = (-1,-2) (-1,-1) (-2,0) (-2,3) (-3,2) (-3,3) (-3,2) (2,-2); seed 0, R 16, k = 0..5 = (5,0) (16,9)
+ *   (-9,-10) (-6,2) (5,6) (9,-2); seed 2^64 - 1, R 1024, k = 0..3 = (-548,1001) (-1010,873) (-210,611) (-662,-816).
+ * k is host state: the optimizer steps begun since the last st_set_jitter, st_set_jitter_shift or st_optimizer_reset.  st_step and
+ * st_step_begin use shift k for EVERY evaluation of the step (L-BFGS's first step evaluates twice, with one shift), then k += 1;
+ * st_opfunc uses shift k and leaves k alone.
+ * L-BFGS caveat: from its second step on the optimizer forms its curvature pair from gradients of two consecutive shifts,
+ * y = g(x_{k+1}; s_{k+1}) - g(x_k; s_k), as the predecessor CLI did: y then holds the change of the objective as well as that of the
+ * iterate.  Nothing guards against it but the s.y > 1e-10 gate the optimizer has anyway; Adam has no such memory.
+ * While the mode is on: st_get_blob, st_get_layer_terms and st_tap_diff answer in the shifted coordinates of the evaluation they
+ * describe; steps are never replayed as a hipGraph (the shift is a per-step argument).  The engine tracks the shift the kept content
+ * features belong to and takes them again before the next evaluation that needs another -- also back to (0, 0) after the mode goes off.
+ * st_set_jitter: radius 0 turns the mode off (the default) and frees every buffer of it; every path then launches what it launched
+ *   before.  ST_ERR_ARG: radius < 0 or > 4096.  ST_ERR_STATE: a pipelined iteration in flight; a tile-configured context
+ *   (st_tile_configure in turn refuses a context with the mode on).  Buffers are allocated first: when that fails nothing has changed.
+ * st_set_jitter_shift: the mode on with this shift held for every evaluation (any integers); k still counts.  Same refusals.
+ * Both bump the epoch and zero k.
+ * st_get_jitter: any pointer may be NULL.  dy, dx: what the next evaluation will use (0, 0 with the mode off).
+ * st_get_jitter_terms (test hook, reads only): xs_nchw: the planes the last evaluation's forward read; scd_nchw: the un-rolled network
+ *   gradient it handed to the image pass; dy, dx: the shift it used, as drawn or given (not reduced).  ST_ERR_STATE with a reason: the
+ *   mode off; no evaluation yet; after a resize; an evaluation without an active row; scd after one without gradient. */
+int st_set_jitter(st_ctx* ctx, int radius, unsigned long long seed);
+int st_set_jitter_shift(st_ctx* ctx, int dy, int dx);
+int st_get_jitter(st_ctx* ctx, int* radius, unsigned long long* seed, long long* k, int* pinned, int* dy, int* dx);
+int st_get_jitter_terms(st_ctx* ctx, float* xs_nchw, float* scd_nchw, int* dy, int* dx);
 /* Steps so far that ran as a hipGraph replay.  Opt-in (environment ST2_GRAPH=1; ST2_GRAPH_MAX_PX=<edge>, default 768):
  * steady-state Adam steps are captured once per ping-pong parity and replayed, bit-identical to plain launches.  Measured
  * on MI355X it is no faster (the step is bound by the dependent kernels' execution latency), hence off by default. */

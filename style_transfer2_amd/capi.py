@@ -2,7 +2,7 @@
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_longlong, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_longlong, c_size_t, c_ulonglong, c_void_p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -106,6 +106,10 @@ PROTOTYPES = {
     'st_get_frames': (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     'st_set_input_from_frame': (c_int, [c_void_p, c_int, c_void_p]),
     'st_anchor_from_frame': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_double, c_int]),
+    'st_set_jitter': (c_int, [c_void_p, c_int, c_ulonglong]),
+    'st_set_jitter_shift': (c_int, [c_void_p, c_int, c_int]),
+    'st_get_jitter': (c_int, [c_void_p, POINTER(c_int), POINTER(c_ulonglong), POINTER(c_longlong), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    'st_get_jitter_terms': (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int), POINTER(c_int)]),
     'st_graph_replays':(c_int, [c_void_p, POINTER(c_longlong)]),
     'st_live_bytes': (c_int, [POINTER(c_longlong), POINTER(c_longlong)]),
     'st_lbfgs_inv_hv': (c_int, [c_void_p, c_int, POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_void_p]),

@@ -355,6 +355,7 @@ int ensure_input_buffers(st_ctx* c, int H, int W)
     if (c->tap.have) { c->tap.have = false; c->tap.resized = true; }  // (st_get_tapped_diff: the copy is that of the old geometry)
     lap_input_resized(c);
     anchor_input_resized(c);
+    jitter_input_resized(c);
     const size_t n3 = (size_t)3 * H * W;
     for (int i = 0; i < 2; ++i) ST_TRY(c->x[i].alloc(n3));
     ST_TRY(c->grad.alloc(n3));
@@ -438,6 +439,7 @@ int content_from_device(st_ctx* c, const float* xdev, int H, int W)
     }
     c->cH = H; c->cW = W;
     c->have_content = true;
+    c->feat_dy = c->feat_dx = 0;                // (jitter: these are the features of the unshifted image)
     c->lap.targets_ok = false;                  // the Laplacian term's targets follow the content image: taken again before the next evaluation
     HIP_TRY(hipStreamSynchronize(c->stream));
     return ST_OK;

@@ -333,6 +333,21 @@ struct st_ctx {
         bool evaluated = false, have_grad = false; // extra holds the last evaluation's
         bool resized = false;                      // ... it did, until the input was resized
     } anchor;
+    // jitter (st_set_jitter; engine_jitter.cpp, jitter_plan.h): the network terms are evaluated on a rolled copy of the iterate
+    struct Jitter {
+        bool on = false;                           // off: every buffer below is empty
+        int radius = 0;                            // 0 with a pinned shift
+        unsigned long long seed = 0;
+        long long k = 0;                           // optimizer steps begun since the last setter / st_optimizer_reset
+        bool pinned = false; int pin_dy = 0, pin_dx = 0;
+        const float* scd_s = nullptr;              // inside an evaluation: the network gradient before the un-roll (a diff buffer of the backward)
+        DevBuf<float> xs, g, cxs;                  // roll(x, s); unroll of the network gradient; roll(content_x, s) (made when a content row first asks)
+        // what the last evaluation left (st_get_jitter_terms)
+        bool evaluated = false, rolled = false, have_grad = false, resized = false;
+        int last_dy = 0, last_dx = 0, last_H = 0, last_W = 0;
+    } jit;
+    // the shift content_feat belongs to, reduced mod (cH, cW); (0, 0) whenever the mode has never been on
+    int feat_dy = 0, feat_dx = 0;
     // frame sequences (st_frames_keep .. st_anchor_from_frame; engine_frames.cpp, frames_plan.h)
     struct Frames {
         int depth = 0;                             // 0: nothing is kept and every buffer below is empty
@@ -511,6 +526,20 @@ int anchor_preflight(const st_ctx* c);
 int anchor_eval(st_ctx* c, const float* x, bool want_grad, const float* g_lap, const float** extra);
 int anchor_trace(st_ctx* c, bool want_grad, bool with_lap, float* image_out);
 void anchor_input_resized(st_ctx* c);             // the input has a new size: `extra` is that of an evaluation at the old one
+// ---------------------------------------------------------------------------------------- engine_jitter.cpp
+// Jitter inside an evaluation; with the mode off each returns at once and launches nothing.  jitter_preflight: the refusal (a
+// tile-configured context) -- no HIP call, nothing changes.  jitter_content: content_feat made those of the shift this evaluation uses
+// (of (0, 0) with the mode off), after objective_terms has checked the content image; skipped where they already are.  jitter_roll_in:
+// *xf = the planes the forward reads, x itself or the mode's buffer holding roll(x, s).  jitter_roll_out: *scd (non-null) replaced by its
+// un-rolled copy for the image pass.  jitter_scd_sums, after the image pass: the scd row of its partial sums retaken over the planes
+// BEFORE the un-roll, in that kernel's order -- scd_grad has the bits of the shifted evaluation
+int jitter_preflight(const st_ctx* c);
+int jitter_content(st_ctx* c);
+int jitter_roll_in(st_ctx* c, const float* x, bool want_grad, const float** xf);
+int jitter_roll_out(st_ctx* c, const float** scd);
+int jitter_scd_sums(st_ctx* c);
+void jitter_step_begun(st_ctx* c);                // an optimizer step has run its evaluations: the next one draws the next shift
+void jitter_input_resized(st_ctx* c);             // the input has a new size: the mode's buffers are those of the old one
 // ---------------------------------------------------------------------------------------- engine_tile.cpp
 // pack (mode 0) / unpack (1 assign, 2 add) the rectangles (y0, x0, h, w each) of a (C, h, w) tensor; checks them against it; enqueues only
 int strips(st_ctx* c, float* tensor, int C, int h, int w, const std::vector<int>& rects, float* buf, int mode);

@@ -57,6 +57,7 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
     if (!c->x[0]) return fail(ST_ERR_STATE, "no input image");
     ST_TRY(lap_preflight(c));
     ST_TRY(anchor_preflight(c));
+    ST_TRY(jitter_preflight(c));
     ST_TRY(act_ensure(c, c->act, c->H, c->W));
     ActSet& a = c->act;
     ObjTerms terms;
@@ -68,8 +69,11 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
     const bool lean = c->bf16 && c->lean && !c->tile.on;         // the bf16 data flow (forward AND backward)
     bool lean32 = false;                                          // fp32: the forward only (dead pooled-layer blobs)
     if (!c->bf16 && c->in_step && !c->tile.on) lean32 = lean32_enabled();
-    ST_TRY(ensure_content_features(c));
-    ST_TRY(forward_range(c, a, x, last, lean || lean32));
+    // jitter (st_set_jitter): the network terms see roll(x, s) and content features of roll(cx, s); mode off: xf == x, the features as ever
+    ST_TRY(jitter_content(c));
+    const float* xf = x;
+    ST_TRY(jitter_roll_in(c, x, want_grad, &xf));
+    ST_TRY(forward_range(c, a, xf, last, lean || lean32));
 
     std::vector<const float*> inj(c->nb, nullptr);
     std::fill(c->cnt.begin(), c->cnt.end(), 0);
@@ -140,6 +144,7 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
             c->sf_in.assign(c->nb, nullptr); c->sf_w.assign(c->nb, nullptr);      // (the ranged-backward entry points never fuse)
             ST_TRY(rc);
         }
+        ST_TRY(jitter_roll_out(c, &scd));         // jitter: the image pass, which reads the unshifted x, takes the un-rolled network gradient
     }
 
     // the Laplacian term (st_set_laplacian): E per level and its sums; with a gradient, g_lap for the image pass to add after p_w g_p
@@ -160,6 +165,7 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
         ProfScope ps(c, P_IMAGE_PASS, 0, 4.0 * n3 * ((adam ? 7 : 3) + (extra ? 1 : 0)));
         HIP_TRY(launch_image_pass(ip, &c->image_cnt, c->stream, extra));
     }
+    ST_TRY(jitter_scd_sums(c));                   // jitter: scd_grad is that of the shifted evaluation (the sums of squares in ITS order)
 
     {
         TraceArgs t{};
@@ -328,6 +334,7 @@ int st_opfunc(st_ctx* c, float* out_loss, float* out_grad, double* trace)
     if (!c->x[0]) return fail(ST_ERR_STATE, "no input image");
     ST_TRY(lap_preflight(c));                                 // refused before anything is enqueued
     ST_TRY(anchor_preflight(c));
+    ST_TRY(jitter_preflight(c));
     HIP_TRY(hipSetDevice(c->device));
     if (c->tap.blob >= 0 && out_grad) {                       // st_tap_diff: this evaluation's backward copies the tapped diff
         c->tap.armed = true; c->tap.captured = c->tap.have = false;

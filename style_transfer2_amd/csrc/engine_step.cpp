@@ -98,6 +98,7 @@ int lbfgs_step(st_ctx* c)
 bool step_graph_ok(const st_ctx* c)
 {
     if (!c->graphs || c->prof_on || c->tile.on || c->m_zero || c->v_zero || c->active.empty()) return false;
+    if (c->jit.on) return false;               // jitter: the shift is a per-step argument of two launches
     if ((size_t)c->H * c->W > c->graph_max_px) return false;
     if (c->plain_epoch != c->epoch || c->plain_steps < 1) return false;       // one plain step first: lazy allocations, norm capture
     for (const ActiveLayer& al : c->active) {
@@ -133,7 +134,8 @@ int step_graph_capture(st_ctx* c, int par)
 // the optimizer step itself: everything st_step launches before the iterate is read back
 int step_enqueue(st_ctx* c)
 {
-    struct InStep { st_ctx* c; InStep(st_ctx* x) : c(x) { c->in_step = true; } ~InStep() { c->in_step = false; } } in_step(c);
+    // (jitter: every evaluation of the step uses shift k; the step counts as begun however it ends)
+    struct InStep { st_ctx* c; InStep(st_ctx* x) : c(x) { c->in_step = true; } ~InStep() { c->in_step = false; jitter_step_begun(c); } } in_step(c);
     if (c->opt_kind == ST_OPT_ADAM) {
         c->items1 += 1; c->items2 += 1;          // DecayingMean.__call__(item), utils.py:58-61
         bool replayed = false;
@@ -219,6 +221,7 @@ int st_optimizer_reset(st_ctx* c, int kind, double step_size)
     c->lb_clear = true;
     c->have_cur = false;
     c->avg_items = 0;        // a new optimizer: the iterate average starts empty (st_objective_changed keeps it)
+    c->jit.k = 0;            // ... and the jitter sequence starts over
     return ST_OK;
 }
 
@@ -278,6 +281,7 @@ int st_step(st_ctx* c, float* out_hwc, double* trace, float* out_loss)
     ST_TRY(emit_preflight(c, EMIT_STEP, out_hwc != nullptr, &emit));       // refused before anything is enqueued
     ST_TRY(lap_preflight(c));
     ST_TRY(anchor_preflight(c));
+    ST_TRY(jitter_preflight(c));
     HIP_TRY(hipSetDevice(c->device));
     ST_TRY(step_enqueue(c));
     // iterate averaging: the update rides on the image pass when an image is wanted, and is a launch of its own otherwise
@@ -303,6 +307,7 @@ int st_step_begin(st_ctx* c)
     ST_TRY(emit_preflight(c, EMIT_STEP_BEGIN, true, &emit));
     ST_TRY(lap_preflight(c));
     ST_TRY(anchor_preflight(c));
+    ST_TRY(jitter_preflight(c));
     HIP_TRY(hipSetDevice(c->device));
     const size_t n3 = (size_t)3 * c->H * c->W;
     if (!p.copy) {

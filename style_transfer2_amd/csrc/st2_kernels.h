@@ -9,6 +9,7 @@
 #include "laplacian_plan.h"
 #include "anchor_plan.h"
 #include "frames_plan.h"
+#include "jitter_plan.h"
 
 namespace st2 {
 
@@ -377,6 +378,17 @@ hipError_t launch_lap_grad(const LapGradArgs& a, int grid, int grid_vec, hipStre
 // aligned (grid_vec workgroups), one pixel per thread and trip otherwise (grid); *n_partial: the slots written per row
 struct AnchorArgs { const float* x; const float* ax; const float* m; const float* g_lap; float* extra; float* part; size_t plane; int W; float w; };
 hipError_t launch_anchor(const AnchorArgs& a, int grid, int grid_vec, int* n_partial, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------
+// Jitter (jitter.hip; jitter_plan.h has the shift sequence, the source index and the grids): dst = roll(src, (p.dy, p.dx)) over the three
+// planes of (3, H, W), dst[c][y][x] = src[c][(y - dy) mod H][(x - dx) mod W].  A pure move: every element is read once and written once.
+// Aligned 16-byte stores of four destination pixels (their sources are dword loads: a shifted row start is not aligned, a group may
+// wrap at the row end) where W % 4 == 0 and dst is 16-byte aligned, one pixel per lane otherwise.  src and dst must not overlap
+// ------------------------------------------------------------------------------------------
+hipError_t launch_roll(const float* src, float* dst, const JitterPlan& p, hipStream_t s);
+// partial[0 .. grid) = what launch_image_pass writes into the scd row of its partial sums (ImagePassArgs::partial + 2 * kMaxPartials)
+// when `planes` (3, H, W) is its scd and `grid` the workgroups it launched (*n_partial): the same walk, the same fp32 sums of squares
+hipError_t launch_roll_sumsq(const float* planes, int H, int W, int grid, float* partial, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
 // Frame sequences (frames.hip; frames_plan.h has the validation and the grids): src a kept frame (3, H, W), dst planes of (3, H, W),

@@ -2,7 +2,7 @@
 model + objective + optimizer, resident on one MI355X."""
 
 import ctypes
-from ctypes import POINTER, byref, c_double, c_float, c_int, c_longlong, c_void_p
+from ctypes import POINTER, byref, c_double, c_float, c_int, c_longlong, c_ulonglong, c_void_p
 
 import numpy as np
 
@@ -612,6 +612,39 @@ class Engine:
         extra = np.empty((1, 3, h, w), F32) if want_extra else None
         check(self.lib.st_get_anchor_terms(self._ctx, _ptr(ax), _ptr(mask), _ptr(extra)))
         return ax, mask, extra
+
+    # -- jitter (st2.h: st_set_jitter) ------------------------------------------------------------------------------------------------
+    def set_jitter(self, radius, seed=0):
+        """Evaluate the network terms on the iterate rolled by a random shift of up to `radius` pixels per axis (1 .. 4096), one shift per
+        optimizer step drawn from splitmix64 of `seed`; the gradient is rolled back, the iterate itself never moves.  0 or None turns
+        the mode off (the default).  Refused while a pipelined iteration is in flight and on a tile-configured context."""
+        seed = int(seed)
+        if not 0 <= seed < 1 << 64:
+            raise ValueError('the jitter seed must fit 64 unsigned bits, got %d' % seed)
+        check(self.lib.st_set_jitter(self._ctx, int(radius or 0), seed))
+
+    def set_jitter_shift(self, dy, dx):
+        """The mode on with the shift (dy, dx) -- any integers -- held for every evaluation; the step counter still counts."""
+        check(self.lib.st_set_jitter_shift(self._ctx, int(dy), int(dx)))
+
+    def jitter(self):
+        """The mode in force: None while it is off, else a dict with 'radius', 'seed', 'k' (optimizer steps begun since it was set),
+        'pinned' and 'shift', the (dy, dx) the next evaluation will use."""
+        radius, seed, k, pinned, dy, dx = c_int(), c_ulonglong(), c_longlong(), c_int(), c_int(), c_int()
+        check(self.lib.st_get_jitter(self._ctx, byref(radius), byref(seed), byref(k), byref(pinned), byref(dy), byref(dx)))
+        if not radius.value and not pinned.value:
+            return None
+        return {'radius': radius.value, 'seed': seed.value, 'k': k.value, 'pinned': bool(pinned.value), 'shift': (dy.value, dx.value)}
+
+    def jitter_terms(self, want_scd=True):
+        """Test hook: (xs, scd, (dy, dx)) of the last evaluation -- the planes its forward read (1, 3, H, W), the un-rolled network
+        gradient it handed to the image pass (None when want_scd is False), and the shift it used."""
+        h, w = self.input_shape()
+        xs = np.empty((1, 3, max(h, 1), max(w, 1)), F32)
+        scd = np.empty_like(xs) if want_scd else None
+        dy, dx = c_int(), c_int()
+        check(self.lib.st_get_jitter_terms(self._ctx, _ptr(xs), _ptr(scd), byref(dy), byref(dx)))
+        return xs, scd, (dy.value, dx.value)
 
     # -- frame sequences (st2.h: st_frames_keep .. st_anchor_from_frame) ------------------------------------------------------------
     def frames_keep(self, depth):

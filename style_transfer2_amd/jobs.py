@@ -50,7 +50,8 @@ def load_mask(path, hw):
 
 def run_job(transfer, content, style, iterations, size=None, style_size=None, optimizer='adam', step_size=None,
             weights=None, params=None, init=None, seed=0, callback=None, iterate_average=None, original_colors=None,
-            match_style_colors=None, laplacian=None, anchor=None, init_nchw=None, init_frame=None, anchor_frames=None):
+            match_style_colors=None, laplacian=None, anchor=None, init_nchw=None, init_frame=None, anchor_frames=None, jitter=None,
+            jitter_seed=0):
     """One whole stylisation: content/style are PIL images or HxWx3 arrays.  Returns the final HxWx3 float32
     image.  Mirrors app.init_arrays + 'start': SetImages(reset) -> SetWeights -> SetOptimizer -> iterate.
     iterate_average: a decay in (0, 1) makes every image handed out (the callback's, the result) the bias-corrected running mean of
@@ -68,7 +69,10 @@ def run_job(transfer, content, style, iterations, size=None, style_size=None, op
     init_frame: (j, flow) starts from kept frame j of the engine (Engine.frame_push), warped on the device by flow (or None) in place
     of `init` (Engine.set_input_from_frame); not together with init_nchw.
     anchor_frames: (weight, [(j, flow, forward_flow, mask), ...]) turns the anchor term on from kept frames (StyleTransfer.
-    anchor_from_frame): the first entry sets the anchor, the others accumulate into it; not together with anchor."""
+    anchor_from_frame): the first entry sets the anchor, the others accumulate into it; not together with anchor.
+    jitter: a radius R in 1 .. 4096 makes every iteration show the network the iterate rolled by a random shift of up to R pixels per
+    axis, drawn from jitter_seed (Engine.set_jitter: the grid artefacts of pools and strides go; the iterate itself never moves); 0
+    turns it off; None leaves the engine as it is."""
     from .device_optimizers import AdamOptimizer, LBFGSOptimizer
     if init_frame is not None and init_nchw is not None:
         raise ValueError('init_frame and init_nchw are two ways to start: give one')
@@ -113,6 +117,8 @@ def run_job(transfer, content, style, iterations, size=None, style_size=None, op
         else:
             image, mask, weight = anchor
             transfer.set_anchor(image, mask, weight)
+    if jitter is not None:
+        transfer.engine.set_jitter(jitter, jitter_seed)     # (after the resets: the shift sequence starts at step 0 of this job)
     if anchor_frames is not None:
         weight, entries = anchor_frames
         for k, (j, flow, forward_flow, mask) in enumerate(entries):
@@ -227,7 +233,7 @@ def warp_planar(x_chw, flow_hw2):
 
 
 def run_frames(transfer, frames, style, iterations, anchor_weight, flows=None, masks=None, first_iterations=None, forward_flows=None,
-               long_term=None, **job_kwargs):
+               long_term=None, jitter=None, jitter_seed=0, **job_kwargs):
     """A frame sequence with temporal consistency (Ruder et al.): frame 0 is a plain run_job (first_iterations of them where given);
     frame t > 0 starts from the raw iterate of frame t - 1 (kept on the device, Engine.frame_push: never the averaged or recoloured
     image handed out), warped by flows[t] ((H, W, 2), from frame t back to frame t - 1; the arithmetic of warp_planar) where one is
@@ -241,6 +247,7 @@ def run_frames(transfer, frames, style, iterations, anchor_weight, flows=None, m
     older stylised frames that reliably shows them (the j in ascending order): Ruder's long-term consistency as one anchor term.  It
     needs a map from forward_flows or masks at every frame it applies to.
     frames: HxWx3 arrays of one size; flows, masks, forward_flows, flows_j: sequences as long as frames (entry 0 is not read) or None.
+    jitter, jitter_seed: run_job's, for every frame: each frame's job draws the same shift sequence from step 0.
     job_kwargs go to every run_job.  Returns the list of results."""
     frames = [np.asarray(f) for f in frames]
     if len({f.shape for f in frames}) > 1:
@@ -280,11 +287,12 @@ def run_frames(transfer, frames, style, iterations, anchor_weight, flows=None, m
     results = []
     for t, frame in enumerate(frames):
         if t == 0:
-            results.append(run_job(transfer, frame, style, first_iterations or iterations, anchor=False, **job_kwargs))
+            results.append(run_job(transfer, frame, style, first_iterations or iterations, anchor=False, jitter=jitter, jitter_seed=jitter_seed, **job_kwargs))
         else:
             flow = flows[t] if flows is not None else None
             entries = [(1, flow, forward_flows[t] if forward_flows is not None else None, masks[t] if masks is not None else None)]
             entries += [(j, fl[t], ff[t] if ff is not None else None, None) for j, fl, ff in older if t >= j and fl[t] is not None]
-            results.append(run_job(transfer, frame, style, iterations, init_frame=(1, flow), anchor_frames=(anchor_weight, entries), **job_kwargs))
+            results.append(run_job(transfer, frame, style, iterations, init_frame=(1, flow), anchor_frames=(anchor_weight, entries), jitter=jitter,
+                                   jitter_seed=jitter_seed, **job_kwargs))
         transfer.engine.frame_push()
     return results

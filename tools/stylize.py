@@ -5,7 +5,9 @@
 --avg-decay D: the image written is the bias-corrected exponentially weighted mean of the iterates (st_set_iterate_average), not
 the last iterate.
 --original-colors: the image written keeps the content image's colours (the iterate's luminance, the content's chroma).
---match-style-colors: the style image is given the content image's colour mean and covariance before the style targets are taken."""
+--match-style-colors: the style image is given the content image's colour mean and covariance before the style targets are taken.
+--jitter R [--jitter-seed S]: every iteration shows the network the iterate rolled by a random shift of up to R pixels per axis
+(st_set_jitter), which removes the regular grid artefacts of pools and strides; not with --grid."""
 import argparse
 import os
 import sys
@@ -47,6 +49,9 @@ def parser():
     ap.add_argument('--anchor', default='', metavar='IMG', help='st_set_anchor: pull the result toward this image (resized to the content\'s size); not with --grid')
     ap.add_argument('--anchor-mask', default='', metavar='M', help='with --anchor: a per-pixel map of the pull, an image (0 .. 255 -> 0 .. 1) or an .npy of (H, W) values >= 0')
     ap.add_argument('--anchor-weight', type=float, default=1.0, metavar='W', help='with --anchor: the weight of the term (default 1)')
+    ap.add_argument('--jitter', type=int, default=None, metavar='R',
+                    help='st_set_jitter: evaluate the network on the iterate rolled by a random shift of up to R pixels per axis in every iteration (1 .. 4096; removes the grid artefacts of pools and strides); not with --grid')
+    ap.add_argument('--jitter-seed', type=int, default=None, metavar='S', help='with --jitter: the seed of the shift sequence, 0 .. 2**64 - 1 (default 0)')
     return ap
 
 
@@ -57,6 +62,10 @@ def main(argv=None):
         ap.error('--laplacian with --grid: tile-sharded mode does not run the Laplacian term')
     if args.anchor and args.grid:
         ap.error('--anchor with --grid: tile-sharded mode does not run the anchor term')
+    if args.jitter and args.grid:
+        ap.error('--jitter with --grid: tile-sharded mode does not run jitter')
+    if args.jitter_seed is not None and args.jitter is None:
+        ap.error('--jitter-seed without --jitter')
     if args.anchor_mask and not args.anchor:
         ap.error('--anchor-mask without --anchor')
     if args.ave_pools and args.grid:
@@ -64,7 +73,11 @@ def main(argv=None):
 
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import style_transfer2_amd as st2
-    from style_transfer2_amd import jobs, laplacian, weights as st2_weights
+    from style_transfer2_amd import jitter as st2_jitter, jobs, laplacian, weights as st2_weights
+    try:
+        jit = st2_jitter.check_jitter(args.jitter, args.jitter_seed or 0) if args.jitter is not None else None
+    except ValueError as err:
+        ap.error('--jitter %s: %s' % (args.jitter, err))
     try:
         levels = laplacian.parse_levels(args.laplacian) if args.laplacian else None
     except ValueError as err:
@@ -100,7 +113,7 @@ def main(argv=None):
         image = jobs.run_job(job, content, jobs.load_rgb(args.style), args.iters, size=args.size,
                              style_size=args.style_size or None, optimizer=args.optimizer, iterate_average=args.avg_decay,
                              original_colors=args.original_colors or None, match_style_colors=args.match_style_colors or None,
-                             laplacian=levels, anchor=anchor)
+                             laplacian=levels, anchor=anchor, jitter=jit[0] if jit else None, jitter_seed=jit[1] if jit else 0)
     Image.fromarray(np.uint8(np.clip(image, 0, 255))).save(args.out)
     print('wrote', args.out, image.shape)
 

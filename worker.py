@@ -125,6 +125,21 @@ def read_laplacian(config):
         raise ValueError('config key laplacian = %r: %s (expected POOL:WEIGHT,... such as 4:100,16:100)' % (raw, err)) from None
 
 
+def read_jitter(config):
+    """The optional config key ``jitter = R`` or ``jitter = R:SEED``: the network terms are evaluated on the iterate rolled by a random
+    shift of up to R pixels per axis (Engine.set_jitter), R an integer in [0, 4096] (``0`` or ``off`` is off), SEED an integer in
+    [0, 2**64) (default 0).  Returns (R, SEED), or None when the key is absent or empty (no call is made: the engine's default, off,
+    stays); a malformed value is a ValueError that names the key.  Pure: any mapping with ``get`` will do."""
+    raw = config.get('jitter', None)
+    if raw is None or str(raw).strip() == '':
+        return None
+    from style_transfer2_amd.jitter import parse_jitter
+    try:
+        return parse_jitter(raw)
+    except ValueError as err:
+        raise ValueError('config key jitter = %r: %s (expected R or R:SEED such as 8 or 8:1234)' % (raw, err)) from None
+
+
 COLOR_KEYS = ('original_colors', 'style_color_match')
 
 
@@ -360,6 +375,11 @@ class Worker:
             levels = read_laplacian(config)
             if levels is not None:
                 self.transfer.engine.set_laplacian(levels)
+            # jitter (config key jitter): the network sees the iterate rolled by a new random shift in every iteration; the trace keeps
+            # its length, and what goes out on the wire its order
+            jitter = read_jitter(config)
+            if jitter is not None:
+                self.transfer.engine.set_jitter(*jitter)
             async_send = str(config.get('async_iterate', '1')).lower() not in ('0', 'false', 'no')
             if async_send:
                 self.sock_out = AsyncSender(sock_out)
