@@ -381,6 +381,51 @@ int st_get_frames(st_ctx* ctx, int* depth, int* count, int* H, int* W);
 int st_set_input_from_frame(st_ctx* ctx, int j, const float* bwd_flow_hw2);
 int st_anchor_from_frame(st_ctx* ctx, int j, const float* bwd_flow_hw2, const float* fwd_flow_hw2, const float* mask_hw, double weight,
                          int accumulate);
+/* ---- optical flow: the flows of the frames block, estimated on the device -------------------------------------------------------
+ * A dense estimator for callers who have only frames: coarse-to-fine Horn-Schunck with warping and Jacobi inner iterations (Horn,
+ * Schunck: "Determining Optical Flow", 1981; the warping scheme of Brox et al., ECCV 2004, with the quadratic penalties).  Every block
+ * is a stencil, so tests/flow_oracle.py restates it in NumPy bit for bit.  No reference counterpart; this text is the definition.
+ * All arithmetic is float32: one rounding per operation, no contraction, IEEE division, operations in the order written.
+ *
+ * estimate(from, to) = f = (dx, dy) per pixel of `from` with from(p) ~ to(p + f(p)): with from = frame t and to = frame t - j it is the
+ * `bwd` flow of the frames block, with from = frame t - j and to = frame t the `fwd` flow.
+ *   luma      g = ((0.299f R + 0.587f G) + 0.114f B) / 255f             per pixel of an H x W x 3 image, uint8 or float32 on the 0 .. 255 scale
+ *   pyramid   level 0 = g; level l + 1 = the 2 x 2 / stride 2 average of level l in Caffe's ceil mode, ((a + b) + (c + d)) / count with
+ *             pixels outside counting 0 and count the clipped window's size (4, 2 or 1): the P(u) of the Laplacian block at p = 2.
+ *             levels = 0: pool while min(h, w) >= 32 and fewer than 12 levels exist; levels = L (1 .. 12): pool L - 1 times, stopping
+ *             early at a 1 x 1 level.  After the pyramid is built from the unsmoothed planes, every level of both images is smoothed
+ *             once, borders replicated:  t = ((g[x-1] + g[x+1]) + 2f g) 0.25f along x, then the same along y on t
+ *   start     u = v = 0 at the coarsest level; moving to a finer level (h x w): u[y, x] = 2f u_coarse[y >> 1, x >> 1], v likewise
+ *   per level, `warps` times, with A the `from` level and B the `to` level:
+ *     Bw  = bilinear(B, x + u, y + v): sample coordinates (float)x + u clamped to [0, w - 1], x0 = floor, x1 = min(x0 + 1, w - 1),
+ *           fx = sx - x0, gx = 1f - fx (y likewise); top = B00 gx + B01 fx, bottom = B10 gx + B11 fx, Bw = top gy + bottom fy
+ *     Ix  = 0.5f (Bw[x+1] - Bw[x-1]), Iy likewise, indices clamped
+ *     c   = ((Bw - A) - Ix u) - Iy v
+ *     den = (a2 + Ix Ix) + Iy Iy,  a2 = float(alpha) float(alpha)
+ *     then `iters` Jacobi iterations, each reading the previous iterate only:
+ *       ub = ((u[y-1] + u[y+1]) + (u[x-1] + u[x+1])) 0.25f, indices clamped; vb likewise
+ *       r  = ((Ix ub + Iy vb) + c) / den;   u' = ub - Ix r,  v' = vb - Iy r
+ *   result    (u, v) of level 0, interleaved as (H, W, 2)
+ * Defaults (params == NULL): alpha 0.06, warps 3, iters 40, levels 0.  The limit: a pyramid resolves motion of a few pixels at its
+ * coarsest level, so at 96 x 128 (three levels) shifts of up to about 4 pixels are recovered to a few hundredths of a pixel, while a
+ * shift of (12, -9) is beyond it (mean error 3.8 px); larger frames have more levels and reach proportionally further.
+ *
+ * st_flow_estimate uploads the two images, runs on the engine's stream, waits, and copies the flow out.  It reads and writes nothing of
+ * the iterate, the optimizer, the anchor, the kept frames or the activations, and bumps no epoch: hooks and captured graphs stay valid.
+ * It is allowed on a tile-configured context.  Its scratch is sized on demand and kept until st_flow_release, st_destroy or a larger
+ * request; when the allocation fails nothing has changed.  route: a test switch, 0 automatic (levels of up to 4096 pixels run all the
+ * Jacobi iterations of a warp in one launch of one workgroup), 1 one launch per Jacobi iteration at every level; the bits are the same.
+ * ST_ERR_ARG: a NULL image or output; H or W < 1; levels outside 0 .. 12, warps outside 1 .. 16, iters outside 1 .. 1000; alpha
+ * non-finite or outside [1e-6, 1e3]; route outside {0, 1}; a non-finite value in a float32 image (scanned on the host).  ST_ERR_STATE:
+ * a pipelined iteration is in flight.  A refused call enqueues nothing.
+ * st_get_flow_level (test hook, reads only): the size of one level of the last estimate, its smoothed planes (h w floats each) and its
+ * finished flow (h w 2); any pointer may be NULL.  ST_ERR_STATE before an estimate or after a release, ST_ERR_ARG for a level that
+ * does not exist. */
+typedef struct st_flow_params { int levels, warps, iters; double alpha; int route; } st_flow_params;
+int st_flow_estimate(st_ctx* ctx, const void* from_hwc, const void* to_hwc, int H, int W, int is_u8, const st_flow_params* params,
+                     float* out_flow_hw2);
+int st_flow_release(st_ctx* ctx);
+int st_get_flow_level(st_ctx* ctx, int level, int* h, int* w, float* from_l, float* to_l, float* flow_l_hw2);
 /* ---- jitter: the network terms evaluated on a randomly rolled iterate ---------------------------------------------------------
  * Pool windows, Winograd output tiles and the stride-16 grid of the deep layers sit at the same pixels in every iteration; the regular
  * grid artefacts of DeepDream and Gram-matrix style transfer come from that.  With the mode on, every evaluation shows the network the

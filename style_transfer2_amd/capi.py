@@ -34,6 +34,10 @@ class LayerDesc(ctypes.Structure):
     _fields_ = [('kind', c_int), ('name', c_char_p), ('cin', c_int), ('cout', c_int)]
 
 
+class FlowParams(ctypes.Structure):
+    _fields_ = [('levels', c_int), ('warps', c_int), ('iters', c_int), ('alpha', c_double), ('route', c_int)]
+
+
 def lib_path():
     return os.environ.get('ST2_HIP_LIB', os.path.join(HERE, 'lib', 'libst2_hip.so'))
 
@@ -106,6 +110,9 @@ PROTOTYPES = {
     'st_get_frames': (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     'st_set_input_from_frame': (c_int, [c_void_p, c_int, c_void_p]),
     'st_anchor_from_frame': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_double, c_int]),
+    'st_flow_estimate': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, POINTER(FlowParams), c_void_p]),
+    'st_flow_release': (c_int, [c_void_p]),
+    'st_get_flow_level': (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_int), c_void_p, c_void_p, c_void_p]),
     'st_set_jitter': (c_int, [c_void_p, c_int, c_ulonglong]),
     'st_set_jitter_shift': (c_int, [c_void_p, c_int, c_int]),
     'st_get_jitter': (c_int, [c_void_p, POINTER(c_int), POINTER(c_ulonglong), POINTER(c_longlong), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),

@@ -26,7 +26,7 @@ const char* const kProfNames[P_COUNT] = {"conv3x3_fwd_mfma_f32", "conv3x3_dgrad_
                                           "gram_partial_mfma_bf16", "style_grad_mfma_bf16", "conv3x3_fwd_wino_split_bf16x6", "conv3x3_dgrad_wino_split_bf16x6",
                                           "style_grad_fused_in_conv_dgrad_bf16", "avepool_fwd", "avepool_bwd",
                                           "gram_partial_split_bf16x6", "style_grad_split_bf16x6", "avepool_bwd_map16", "laplacian_pool", "laplacian_stencil", "laplacian_grad", "anchor",
-                                          "frames"};
+                                          "frames", "flow_prepare", "flow_linearise", "flow_jacobi", "flow_jacobi_one_workgroup"};
 
 static const struct { int kind; const char* name; int cin, cout; } kVgg19[] = {
     {0, "conv1_1", 3, 64}, {0, "conv1_2", 64, 64}, {1, "pool1", 0, 0},

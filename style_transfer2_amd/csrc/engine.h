@@ -42,6 +42,7 @@ enum ProfClass { P_CONV_FWD, P_CONV_DGRAD, P_POOL_FWD, P_POOL_BWD, P_GRAM, P_GRA
                  P_LAP_POOL, P_LAP_STENCIL, P_LAP_GRAD,      // the launches of the Laplacian term (laplacian.hip), the targets' included
                  P_ANCHOR,                                   // anchor_k, the one launch of the anchor term (anchor.hip)
                  P_FRAMES,                                   // frames_k, the one launch of st_set_input_from_frame / st_anchor_from_frame (frames.hip)
+                 P_FLOW_PREP, P_FLOW_LINEAR, P_FLOW_JACOBI, P_FLOW_JACOBI_WG,   // optical flow (flow.hip): pyramids, start and interleave; a warp's linearisation; one Jacobi iteration; all of a warp's in one workgroup
                  P_COUNT };
 extern const char* const kProfNames[P_COUNT];
 struct ProfRec { int cls; hipEvent_t a, b; double flops, bytes; };
@@ -356,6 +357,12 @@ struct st_ctx {
         DevBuf<float> slot[kFramesMaxDepth];       // raw iterates (3, H, W); allocated by the pushes
         DevBuf<float> stage;                       // the caller's flows and map on their way to frames_k: [bwd | fwd | mask], grown on demand
     } frames;
+    // optical flow (st_flow_estimate .. st_get_flow_level; engine_flow.cpp, flow_plan.h)
+    struct Flow {
+        DevBuf<float> scratch;                     // everything an estimate needs, laid out by flow_plan; grown on demand, kept until st_flow_release
+        FlowPlan plan{};                           // of the last estimate
+        bool have = false;                         // scratch holds the levels of a finished estimate (st_get_flow_level)
+    } flow;
     // tile-sharded mode (BASELINE config 5): this context holds ONE window of a larger image
     struct Tile : TileGeom {
         bool on = false;

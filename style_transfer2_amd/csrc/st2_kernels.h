@@ -10,6 +10,7 @@
 #include "anchor_plan.h"
 #include "frames_plan.h"
 #include "jitter_plan.h"
+#include "flow_plan.h"
 
 namespace st2 {
 
@@ -400,6 +401,26 @@ hipError_t launch_roll_sumsq(const float* planes, int H, int W, int grid, float*
 // aligned (grid_vec workgroups), one pixel per thread and trip otherwise (grid)
 struct FramesArgs { const float* src; const float* bwd; const float* fwd; const float* mask; float* dst; float* map; int H, W; size_t plane; };
 hipError_t launch_frames(const FramesArgs& a, int accumulate, int grid, int grid_vec, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------
+// Optical flow (flow.hip; flow_plan.h has the validation, the level geometry and the grids; include/st2.h the definition).  `base` is
+// the block's scratch buffer, every plane an offset of the plan into it.  All of it in fp32, one rounding per operation.
+// ------------------------------------------------------------------------------------------
+// level 0 of both pyramids from the staged HWC images (uint8 or float32), one launch
+hipError_t launch_flow_luma(const FlowPlan& p, float* base, hipStream_t s);
+// level l + 1 of both pyramids from the unsmoothed level l; the smoothed planes of level l from its unsmoothed ones: one launch each
+hipError_t launch_flow_pool(const FlowPlan& p, float* base, int l, hipStream_t s);
+hipError_t launch_flow_smooth(const FlowPlan& p, float* base, int l, hipStream_t s);
+// the flow a level starts from: 0 at the coarsest, twice the coarser level's at (y >> 1, x >> 1) elsewhere
+hipError_t launch_flow_start(const FlowPlan& p, float* base, int l, hipStream_t s);
+// Ix, Iy, c, den of one warp at level l, from the flow in (u, v)
+hipError_t launch_flow_linear(const FlowPlan& p, float* base, int l, const float* u, const float* v, hipStream_t s);
+// one Jacobi iteration (u, v) -> (un, vn), distinct buffers
+hipError_t launch_flow_jacobi(const FlowPlan& p, float* base, int l, const float* u, const float* v, float* un, float* vn, hipStream_t s);
+// all p.par.iters Jacobi iterations in place, in one workgroup (levels with one_wg)
+hipError_t launch_flow_jacobi_wg(const FlowPlan& p, float* base, int l, float* u, float* v, hipStream_t s);
+// (u, v) planes of h x w -> (h, w, 2)
+hipError_t launch_flow_interleave(const float* u, const float* v, float* out_hw2, size_t n, int grid, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
 // trace finalisation: one tiny kernel turns the partial sums of an opfunc into the trace scalars

@@ -7,6 +7,7 @@ from ctypes import POINTER, byref, c_double, c_float, c_int, c_longlong, c_ulong
 import numpy as np
 
 from . import capi, prototxt
+from . import flow as flow_mod
 from .capi import check
 
 F32 = np.float32
@@ -645,6 +646,39 @@ class Engine:
         dy, dx = c_int(), c_int()
         check(self.lib.st_get_jitter_terms(self._ctx, _ptr(xs), _ptr(scd), byref(dy), byref(dx)))
         return xs, scd, (dy.value, dx.value)
+
+    # -- optical flow (st2.h: st_flow_estimate .. st_get_flow_level) ----------------------------------------------------------------
+    def flow_estimate(self, from_image, to_image, **params):
+        """The dense optical flow (H, W, 2) float32 of (dx, dy) with from_image(p) ~ to_image(p + flow(p)), estimated on the device
+        (st2.h: coarse-to-fine Horn-Schunck; tests/flow_oracle.py restates it bit for bit).  The images are HxWx3 of one size, uint8
+        or float on the 0 .. 255 scale.  params: alpha, warps, iters, levels, route (flow.check_flow; the defaults of flow.DEFAULTS).
+        With from = frame t and to = frame t - 1 this is flows[t] of jobs.run_frames; the other way round, forward_flows[t].  Nothing
+        of the job's state is read or written."""
+        par = flow_mod.check_flow(**params)
+        a, a_u8 = _image_arg(from_image)
+        b, b_u8 = _image_arg(to_image)
+        if a.shape != b.shape:
+            raise ValueError('the two images differ in size: %s and %s' % (a.shape[:2], b.shape[:2]))
+        if a_u8 != b_u8:                                   # one upload format for both
+            a, b, a_u8 = np.ascontiguousarray(a, F32), np.ascontiguousarray(b, F32), 0
+        h, w = a.shape[:2]
+        out = np.empty((h, w, 2), F32)
+        cpar = capi.FlowParams(par['levels'], par['warps'], par['iters'], par['alpha'], par['route'])
+        check(self.lib.st_flow_estimate(self._ctx, _ptr(a), _ptr(b), h, w, a_u8, byref(cpar), _ptr(out)))
+        return out
+
+    def flow_release(self):
+        """Free the scratch buffer the estimates keep on the device (the next estimate makes it again)."""
+        check(self.lib.st_flow_release(self._ctx))
+
+    def flow_level(self, level):
+        """Test hook: (from_l, to_l, flow_l) of one level of the last estimate: the smoothed luma planes (h, w) and the level's
+        finished flow (h, w, 2)."""
+        h, w = c_int(), c_int()
+        check(self.lib.st_get_flow_level(self._ctx, int(level), byref(h), byref(w), None, None, None))
+        a, b, f = np.empty((h.value, w.value), F32), np.empty((h.value, w.value), F32), np.empty((h.value, w.value, 2), F32)
+        check(self.lib.st_get_flow_level(self._ctx, int(level), byref(h), byref(w), _ptr(a), _ptr(b), _ptr(f)))
+        return a, b, f
 
     # -- frame sequences (st2.h: st_frames_keep .. st_anchor_from_frame) ------------------------------------------------------------
     def frames_keep(self, depth):

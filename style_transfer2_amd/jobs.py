@@ -232,8 +232,61 @@ def warp_planar(x_chw, flow_hw2):
     return (top * (1 - fy) + bottom * fy).astype(np.float32)
 
 
+def _long_term_keys(long_term):
+    js = sorted(long_term or ())
+    for j in js:
+        if isinstance(j, bool) or not isinstance(j, (int, np.integer)) or not 2 <= j <= 8:
+            raise ValueError('long_term: the keys are integers from 2 to 8, got %r' % (j,))
+    return [int(j) for j in js]
+
+
+def estimate_flows(engine, frames, long_term=(), **params):
+    """Every optical flow run_frames reads, estimated on the device from the frames themselves (Engine.flow_estimate; st2.h:
+    st_flow_estimate).  frames: HxWx3 arrays of one size, as they are stylised.  long_term: the distances j (2 .. 8) to estimate as well.
+    params: alpha, warps, iters, levels (flow.DEFAULTS).  Returns (flows, forward_flows, long_term) in the shapes run_frames takes:
+    flows[t] = estimate(frames[t], frames[t - 1]), forward_flows[t] = estimate(frames[t - 1], frames[t]), entry 0 None;
+    long_term = {j: (flows_j, forward_flows_j)} likewise against frame t - j, entries below j None."""
+    frames = [np.asarray(f) for f in frames]
+    if len({f.shape for f in frames}) > 1:
+        raise ValueError('the frames differ in size: %s' % sorted({f.shape[:2] for f in frames}))
+
+    def pair(j):
+        back = [None if t < j else engine.flow_estimate(frames[t], frames[t - j], **params) for t in range(len(frames))]
+        forth = [None if t < j else engine.flow_estimate(frames[t - j], frames[t], **params) for t in range(len(frames))]
+        return back, forth
+    flows, forward_flows = pair(1)
+    return flows, forward_flows, {j: pair(j) for j in _long_term_keys(long_term)}
+
+
+def _filled(given, estimated):
+    """Per frame the caller's entry where there is one, else the estimated one."""
+    if given is None:
+        return estimated
+    if len(given) != len(estimated):
+        return given                                       # (run_frames' own checks name the sequence)
+    return [e if g is None else g for g, e in zip(given, estimated)]
+
+
+def fill_flows(engine, frames, flows=None, forward_flows=None, long_term=None, **params):
+    """run_frames' (flows, forward_flows, long_term) with every flow the caller did not give estimated from the frames (estimate_flows
+    with params); what is given wins, entry by entry.  long_term: a dict {j: (flows_j, forward_flows_j or None) or None}, or a plain
+    sequence of distances.  The estimates' scratch on the device is released before returning."""
+    given = long_term if isinstance(long_term, dict) else {j: None for j in (long_term or ())}
+    for j in _long_term_keys(given):
+        pair = given[j]
+        if pair is not None and (not isinstance(pair, (tuple, list)) or len(pair) != 2):
+            raise ValueError('long_term[%d]: a (flows, forward_flows or None) pair, or None to estimate both' % j)
+    est_flows, est_forward, est_long = estimate_flows(engine, frames, long_term=given, **params)
+    engine.flow_release()                                  # (the jobs run with the memory they have without the estimates)
+    out = {}
+    for j, (back, forth) in est_long.items():
+        pair = given[j]
+        out[j] = (_filled(pair[0], back), _filled(pair[1], forth)) if pair is not None else (back, forth)
+    return _filled(flows, est_flows), _filled(forward_flows, est_forward), out
+
+
 def run_frames(transfer, frames, style, iterations, anchor_weight, flows=None, masks=None, first_iterations=None, forward_flows=None,
-               long_term=None, jitter=None, jitter_seed=0, **job_kwargs):
+               long_term=None, jitter=None, jitter_seed=0, estimate=None, **job_kwargs):
     """A frame sequence with temporal consistency (Ruder et al.): frame 0 is a plain run_job (first_iterations of them where given);
     frame t > 0 starts from the raw iterate of frame t - 1 (kept on the device, Engine.frame_push: never the averaged or recoloured
     image handed out), warped by flows[t] ((H, W, 2), from frame t back to frame t - 1; the arithmetic of warp_planar) where one is
@@ -248,11 +301,17 @@ def run_frames(transfer, frames, style, iterations, anchor_weight, flows=None, m
     needs a map from forward_flows or masks at every frame it applies to.
     frames: HxWx3 arrays of one size; flows, masks, forward_flows, flows_j: sequences as long as frames (entry 0 is not read) or None.
     jitter, jitter_seed: run_job's, for every frame: each frame's job draws the same shift sequence from step 0.
+    estimate: None, or a dict of estimate_flows' parameters (possibly empty): every flow the caller did not give -- flows, forward_flows
+    and, for every key of long_term (then also a plain sequence of distances, or a dict with None in place of a pair), both of its
+    sequences -- is estimated on the device from the frames (estimate_flows) before the first job; entries that are given win.  With
+    estimate=None nothing is estimated, and flows=None still means "no warp".
     job_kwargs go to every run_job.  Returns the list of results."""
     frames = [np.asarray(f) for f in frames]
     if len({f.shape for f in frames}) > 1:
         raise ValueError('the frames differ in size: %s' % sorted({f.shape[:2] for f in frames}))
     hw = frames[0].shape[:2] if frames else (0, 0)
+    if estimate is not None:
+        flows, forward_flows, long_term = fill_flows(transfer.engine, frames, flows, forward_flows, long_term, **dict(estimate))
     older = []                                             # (j, flows_j, forward_flows_j), ascending
     for j, pair in (long_term or {}).items():
         if isinstance(j, bool) or not isinstance(j, (int, np.integer)) or not 2 <= j <= 8:

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Headless stylisation of a frame sequence on one MI355X, with temporal consistency:
     stylize_frames.py f000.png f001.png ... --style s.jpg --out-dir out [--flows DIR] [--forward-flows DIR] [--masks DIR]
-                      [--long-term 2,4] [--anchor-weight W]
+                      [--long-term 2,4] [--anchor-weight W] [--estimate-flow [--flow-alpha A] [--flow-iters N] [--flow-warps N]
+                      [--flow-levels N] [--save-flows DIR]]
 Frame 0 is a plain job.  Every later frame starts from the previous frame's iterate, warped by the optical flow where one is given, and
 is pulled toward it by the anchor term (st_set_anchor; jobs.run_frames) with the weight W and the frame's map.  The seam between two
 frames runs on the device (st_set_input_from_frame, st_anchor_from_frame).
@@ -12,7 +13,11 @@ on the device (forward / backward consistency, motion boundaries, samples outsid
 where --masks has one.  --long-term 2,4: pixels the map leaves free are anchored to the stylised frame 2, then 4 frames back, through
 <stem>.b<j>.npy under --flows (from the frame back to the one j before; frames from the j-th on; a missing file skips that pair) and,
 where it exists, <stem>.f<j>.npy under --forward-flows (the flow from the frame j before to the frame).
-Flows and maps are the caller's: nothing here estimates them.  The results go to <out-dir>/<stem>.png."""
+Flows and maps may be the caller's, or --estimate-flow estimates the flows on the device from the frames themselves (st_flow_estimate:
+coarse-to-fine Horn-Schunck; --flow-alpha, --flow-iters, --flow-warps, --flow-levels are its parameters): --flows, --forward-flows and
+the --long-term side files are then optional, and a file that exists still wins over the estimate.  --save-flows DIR writes the flows
+the run used as <stem>.npy, <stem>.fwd.npy, <stem>.b<j>.npy and <stem>.f<j>.npy; given as both --flows and --forward-flows, that
+directory reproduces the run (--forward-flows reads <stem>.fwd.npy where there is one, else <stem>.npy).  The results go to <out-dir>/<stem>.png."""
 import argparse
 import os
 import sys
@@ -31,6 +36,12 @@ def parser():
     ap.add_argument('--forward-flows', default='', metavar='DIR', help='<stem>.npy: the flow from the frame before; derives the reliability on the device')
     ap.add_argument('--long-term', type=long_term_arg, default=[], metavar='J,J', help='earlier frames to anchor uncovered pixels to, e.g. 2,4 (each 2 .. 8)')
     ap.add_argument('--anchor-weight', type=float, default=1.0, metavar='W')
+    ap.add_argument('--estimate-flow', action='store_true', help='estimate on the device every flow no file gives (st_flow_estimate)')
+    ap.add_argument('--flow-alpha', type=float, default=None, metavar='A', help='smoothness weight of the estimator (default 0.06)')
+    ap.add_argument('--flow-iters', type=int, default=None, metavar='N', help='Jacobi iterations per warp (default 40)')
+    ap.add_argument('--flow-warps', type=int, default=None, metavar='N', help='warps per pyramid level (default 3)')
+    ap.add_argument('--flow-levels', type=int, default=None, metavar='N', help='pyramid levels; 0: while the shorter side is at least 32 (default)')
+    ap.add_argument('--save-flows', default='', metavar='DIR', help='with --estimate-flow: write the flows the run used')
     ap.add_argument('--iters', type=int, default=200, help='iterations of every frame after the first')
     ap.add_argument('--first-iters', type=int, default=0, metavar='N', help='iterations of the first frame (default: --iters)')
     ap.add_argument('--size', type=int, default=512)
@@ -78,13 +89,51 @@ def side_file(directory, stem, endings):
     raise FileNotFoundError('%s: no %s' % (directory, ' or '.join(stem + e for e in endings)))
 
 
+def optional_file(directory, name):
+    """The side file where the directory is given and holds it, else None (--estimate-flow fills the gap)."""
+    path = os.path.join(directory, name) if directory else ''
+    return path if path and os.path.exists(path) else None
+
+
+def flow_params(ap, args):
+    """The estimator's parameters from the command line, checked (None without --estimate-flow); refuses what cannot work."""
+    given = {key: getattr(args, 'flow_' + key) for key in ('alpha', 'iters', 'warps', 'levels') if getattr(args, 'flow_' + key) is not None}
+    if not args.estimate_flow:
+        if given or args.save_flows:
+            ap.error('--flow-alpha, --flow-iters, --flow-warps, --flow-levels and --save-flows need --estimate-flow')
+        if args.forward_flows and not args.flows:
+            ap.error('--forward-flows needs --flows: the reliability takes both directions')
+        if args.long_term and (not args.flows or not (args.forward_flows or args.masks)):
+            ap.error('--long-term needs --flows (the <stem>.b<j>.npy files) and a map from --forward-flows or --masks')
+        return None
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from style_transfer2_amd import flow
+    try:
+        flow.check_flow(**given)
+    except ValueError as e:
+        ap.error('--estimate-flow: %s' % e)
+    return given
+
+
+def save_flows(directory, stems, flows, forward_flows, long_term):
+    """<stem>.npy, <stem>.fwd.npy, <stem>.b<j>.npy, <stem>.f<j>.npy of every flow that is there; returns the paths written."""
+    os.makedirs(directory, exist_ok=True)
+    named = [('%s.npy', flows), ('%s.fwd.npy', forward_flows)]
+    for j, (back, forth) in sorted((long_term or {}).items()):
+        named += [('%%s.b%d.npy' % j, back), ('%%s.f%d.npy' % j, forth)]
+    written = []
+    for pattern, seq in named:
+        for stem, f in zip(stems, seq or []):
+            if f is not None:
+                written.append(os.path.join(directory, pattern % stem))
+                np.save(written[-1], np.asarray(f, np.float32))
+    return written
+
+
 def main(argv=None):
     ap = parser()
     args = ap.parse_args(argv)
-    if args.forward_flows and not args.flows:
-        ap.error('--forward-flows needs --flows: the reliability takes both directions')
-    if args.long_term and (not args.flows or not (args.forward_flows or args.masks)):
-        ap.error('--long-term needs --flows (the <stem>.b<j>.npy files) and a map from --forward-flows or --masks')
+    estimate = flow_params(ap, args)
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import style_transfer2_amd as st2
     from style_transfer2_amd import jobs, weights as st2_weights
@@ -93,15 +142,21 @@ def main(argv=None):
     stems = [os.path.splitext(os.path.basename(path))[0] for path in args.frames]
     hw = frames[0].shape[:2]
     flows = masks = None
-    if args.flows:
+    load = lambda paths: [np.load(path) if path else None for path in paths]      # noqa: E731
+    if args.flows and estimate is None:
         flows = [None] + [np.load(side_file(args.flows, stem, ('.npy',))) for stem in stems[1:]]
     if args.masks:
         masks = [None] + [jobs.load_mask(side_file(args.masks, stem, ('.npy', '.png')), hw) for stem in stems[1:]]
     forward_flows = long_term = None
-    if args.forward_flows:
-        forward_flows = [None] + [np.load(side_file(args.forward_flows, stem, ('.npy',))) for stem in stems[1:]]
-    if args.long_term:
-        load = lambda paths: [np.load(path) if path else None for path in paths]      # noqa: E731
+    if args.forward_flows and estimate is None:
+        forward_flows = [None] + [np.load(side_file(args.forward_flows, stem, ('.fwd.npy', '.npy'))) for stem in stems[1:]]
+    if estimate is not None:                                # the files that exist; the estimates fill the gaps below
+        flows = [None] + load(optional_file(args.flows, stem + '.npy') for stem in stems[1:])
+        forward_flows = [None] + load(optional_file(args.forward_flows, stem + '.fwd.npy') or optional_file(args.forward_flows, stem + '.npy')
+                                      for stem in stems[1:])
+    if args.long_term and estimate is not None and not args.flows:
+        long_term = {j: None for j in args.long_term}       # no side files: both directions are estimated
+    elif args.long_term:
         long_term = {j: (load(back), load(fwd) if fwd else None)
                      for j, (back, fwd) in long_term_files(args.flows, args.forward_flows, stems, args.long_term).items()}
     style = jobs.load_rgb(args.style)
@@ -116,6 +171,11 @@ def main(argv=None):
         params = st2_weights.he_normal(st2.VGG19_TOPOLOGY, seed=0)
     job = st2.StyleTransfer(st2.HipModel(params, device=args.gpu, precision=args.precision, conv_algo=args.conv_algo, gram_algo=args.gram_algo,
                                          pool_algo=args.pool_algo))
+    if estimate is not None:
+        flows, forward_flows, long_term = jobs.fill_flows(job.engine, frames, flows, forward_flows, long_term or {}, **estimate)
+        if args.save_flows:
+            for path in save_flows(args.save_flows, stems, flows, forward_flows, long_term):
+                print('wrote', path)
     results = jobs.run_frames(job, frames, style, args.iters, args.anchor_weight, flows=flows, masks=masks, forward_flows=forward_flows, long_term=long_term,
                               first_iterations=args.first_iters or None, optimizer=args.optimizer)
     os.makedirs(args.out_dir, exist_ok=True)
