@@ -157,7 +157,7 @@ int st_input_shape(st_ctx* ctx, int* H, int* W);
 int st_set_weights(st_ctx* ctx, int n_rows, const int* blob_index, const float* content,
                    const float* style, const float* deepdream, const double params[4]);
 int st_clear_norms(st_ctx* ctx);                          /* the `norms` half of reset() */
-/* number of trace scalars an evaluation produces: 6 per active layer + 8 (+ 2 while st_set_laplacian is on, + 2 while st_set_anchor is) */
+/* number of trace scalars an evaluation produces: 6 per active layer + 8 (+ 2 while st_set_laplacian is on, + 2 while st_set_anchor is, + 2 while st_set_matting is) */
 int st_trace_len(st_ctx* ctx);
 /* evaluates opfunc at the current input; out_grad (3,H,W) may be NULL (return_grad=False) */
 int st_opfunc(st_ctx* ctx, float* out_loss, float* out_grad, double* trace);
@@ -331,6 +331,61 @@ int st_get_anchor(st_ctx* ctx, int* on, int* H, int* W, int* has_mask, double* w
  * Any pointer may be NULL.  ST_ERR_STATE, the message saying why: with the term off, before an evaluation with the term on, after the
  * input was resized, for mask_hw without a map, and for extra_nchw after an evaluation without a gradient. */
 int st_get_anchor_terms(st_ctx* ctx, float* anchor_nchw, float* mask_hw, float* extra_nchw);
+/* ---- the photorealism term: the matting-Laplacian regulariser ----------------------------------------------------------------------
+ * An image-space term like TV, the p-norm, the Laplacian and the anchor term; no reference counterpart, this text is the definition.
+ * It is the photorealism regulariser of Luan, Paris, Shechtman, Bala ("Deep Photo Style Transfer", CVPR 2017): w * sum_c u_c' L u_c with
+ * L the matting Laplacian of the content image (Levin, Lischinski, Weiss: "A Closed-Form Solution to Natural Image Matting"), zero
+ * exactly when every 3 x 3 window of the result is an affine function of the content's colours in that window.  L is never formed: the
+ * term is evaluated matrix-free, as Levin's cost at its minimum, window by window.
+ * Symbols: u = x / 255, planar (3, H, W), x the preprocessed iterate; I = cx / 255, cx the preprocessed content image of the input's
+ * size (both divisions fp32 IEEE).  A window k is the 3 x 3 block centred at a pixel with 1 <= ky <= H - 2, 1 <= kx <= W - 2: only windows
+ * wholly inside the image exist, so H, W >= 3, there are (H - 2)(W - 2) of them and each has nine pixels, always visited row-major
+ * (dy = -1 .. 1 outer, dx = -1 .. 1 inner); every sum starts from 0 in that order.  w: finite and non-zero as a double and as a float;
+ * eps in [1e-9, 1].
+ * Per window, taken when the content image or the input's size changes (float64, one rounding per operation, no contraction):
+ *   mu_a = (sum_i I_a,i) / 9;  dI_a,i = I_a,i - mu_a;  s_ab = (sum_i dI_a,i * dI_b,i) / 9 (a <= b);  eps / 9 is added to s_00, s_11, s_22;
+ *   c00 = s11 s22 - s12 s12; c01 = s02 s12 - s01 s22; c02 = s01 s12 - s02 s11; det = (s00 c00 + s01 c01) + s02 c02;
+ *   c11 = s00 s22 - s02 s02; c12 = s01 s02 - s00 s12; c22 = s00 s11 - s01 s01;  M_ab = c_ab / det.
+ *   Stored: mu (3) and M (6), each rounded once to fp32; I as three fp32 planes.
+ * Per evaluation, first pass (per window k and channel c of u; fp32, one rounding per operation, in the order written):
+ *   pb = (sum_i u_i) / 9;  dp_i = u_i - pb;  dI_a,i = I_a,i - mu_a (the stored fp32 mu);  cov_a = (sum_i dI_a,i * dp_i) / 9;
+ *   a_a = (M_a0 cov_0 + M_a1 cov_1) + M_a2 cov_2;  r_i = dp_i - ((a_0 dI_0,i + a_1 dI_1,i) + a_2 dI_2,i);
+ *   J = (sum_i (double)r_i * (double)r_i) + eps * (((double)a_0 * a_0 + (double)a_1 * a_1) + (double)a_2 * a_2), all in double.
+ *   a_0, a_1, a_2, pb are written per window and channel.  A workgroup of 256 threads takes tiles of 64 x 4 windows, thread t the window
+ *   (t / 64, t % 64) of its tile, and walks the tiles (row-major) block, block + grid, ... with grid = min(tiles, 1024); a thread adds its
+ *   J (channel 0, 1, 2 of a window, tile after tile) in double, the workgroup's sum is fp32 (the wave and workgroup trees of the other
+ *   terms), the sum across workgroups double -- exactly as the Laplacian and anchor terms do.
+ * Second pass, only with a gradient (per pixel i and channel c):
+ *   Lu_i = sum of r_ik over the existing windows k that contain i (ky = y - 1 .. y + 1, kx = x - 1 .. x + 1 clipped to the valid
+ *   centres, row-major, from 0), r_ik recomputed by the expression above from the stored a, pb, mu and the pixel's u, I: the same bits.
+ *   g_mat = w * (2 * Lu_i): the factor 2 first, then w as a float; the derivative with respect to u, added to the image gradient as it
+ *   is (no 1 / 255 chain factor, like g_tv, g_p, g_lap, g_anc).
+ *   grad = ((scd + tv_w g_tv) + p_w g_p) + extra,  extra = prev + g_mat (one fp32 addition, prev first) with prev what extra was without
+ *   this term (g_lap, g_anc or g_lap + g_anc); extra = g_mat when neither other term is on.  The sums of g_mat^2 go over tiles of
+ *   64 x 4 pixels the same way (channel 0, 1, 2 of a pixel).
+ * While the term is on the trace gains two scalars; its image part becomes [scd_loss, t_loss, p_loss, (l_loss,) (a_loss,) m_loss,
+ * scd_grad, tv_grad, p_grad, (l_grad,) (a_grad,) m_grad, loss, grad] with m_loss = w * float(sum J), added to loss last, after a_loss,
+ * and m_grad = sqrt(float(sum g_mat^2 / (3 H W))), 0 for an evaluation without a gradient; grad is the rms of the combined gradient.
+ * With the term off every trace is what it was.  Jitter does not touch the term: it reads the unshifted iterate and content image.
+ *
+ * st_set_matting: weight == 0 is off, the default: every buffer of the term is freed and every path launches what it launched before.
+ * ST_ERR_ARG: a NaN, infinite, float-underflowing or float-overflowing weight; eps outside [1e-9, 1].  ST_ERR_STATE: while a pipelined
+ * iteration is in flight; on a tile-configured context (st_tile_configure refuses a context with the term on).  The buffers are
+ * allocated first: when that fails nothing has changed.  The per-window data are taken here when a content image of the input's size
+ * exists, and again before the next evaluation whenever the content image (st_set_content*, st_resample_content) or the input's size
+ * has changed since.  An evaluation (st_opfunc, st_step, st_step_begin) with the term on returns ST_ERR_STATE, the sizes named, before
+ * anything is enqueued: without a content image, with one of another size than the input, and with H < 3 or W < 3. */
+int st_set_matting(st_ctx* ctx, double weight, double eps);
+/* the term in force; any pointer may be NULL */
+int st_get_matting(st_ctx* ctx, int* on, double* weight, double* eps);
+/* Test hook, reads only: mu (3, H - 2, W - 2), M (6, H - 2, W - 2) in the order 00 01 02 11 12 22, a_pb (3, 4, H - 2, W - 2) as the
+ * last evaluation's first pass left it, and `extra` (3, H, W) as its second pass did.  Any pointer may be NULL.  ST_ERR_STATE, the
+ * message saying why: with the term off, before an evaluation with the term on, after the input was resized, and for extra_nchw after
+ * an evaluation without a gradient. */
+int st_get_matting_terms(st_ctx* ctx, float* mu, float* M, float* a_pb, float* extra_nchw);
+/* Which optional image-space terms are on, in the order the trace lists them (1 or 0 each; any pointer may be NULL): what a caller needs
+ * to name the scalars of the image part, whose length alone does not say.  Reads host state only. */
+int st_get_trace_terms(st_ctx* ctx, int* laplacian, int* anchor, int* matting);
 /* ---- frame sequences: earlier iterates kept on the device, warped into the iterate and into the anchor -----------------------------
  * What the seam between two frames of a stylised sequence needs (Ruder, Dosovitskiy, Brox: "Artistic Style Transfer for Videos", GCPR
  * 2016): the next frame starts from the previous stylised frame warped by the optical flow and is pulled toward it by the anchor term

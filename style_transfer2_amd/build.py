@@ -29,6 +29,7 @@ SOURCES = (
     ('emit.hip', ('-ffp-contract=off',)),        # the image handed out (plain, averaged, luminance): NumPy's float32 arithmetic
     ('laplacian.hip', ('-ffp-contract=off',)),   # the Laplacian term: pool, stencil, gradient, one rounding per operation
     ('anchor.hip', ('-ffp-contract=off',)),      # the anchor term: one pass, one rounding per operation
+    ('matting.hip', ('-ffp-contract=off',)),     # the photorealism term: two window passes, one rounding per operation
     ('frames.hip', ('-ffp-contract=off',)),      # frame sequences: warp, reliability, composition in jobs.warp_planar's float64 arithmetic
     ('jitter.hip', ('-ffp-contract=off',)),      # jitter: roll_k, a pure move; roll_sumsq_k rounds like image_pass_k
     ('flow.hip', ('-ffp-contract=off',)),        # optical flow: pyramids, warp, Jacobi in tests/flow_oracle.py's float32 arithmetic
@@ -49,11 +50,12 @@ SOURCES = (
     ('engine_emit.cpp', ('-x', 'hip')),
     ('engine_laplacian.cpp', ('-x', 'hip')),
     ('engine_anchor.cpp', ('-x', 'hip')),
+    ('engine_matting.cpp', ('-x', 'hip')),
     ('engine_frames.cpp', ('-x', 'hip')),
     ('engine_jitter.cpp', ('-x', 'hip')),
     ('engine_flow.cpp', ('-x', 'hip')),
 )
-HEADERS = ('st2_kernels.h', 'env.h', 'wave_reduce.h', 'engine.h', 'devbuf.h', 'color_match.h', 'emit_plan.h', 'laplacian_plan.h', 'anchor_plan.h', 'frames_plan.h', 'jitter_plan.h', 'flow_plan.h', 'image_pass_kernel.inc', 'channel_mean.h', os.path.join('..', '..', 'include', 'st2.h'))
+HEADERS = ('st2_kernels.h', 'env.h', 'wave_reduce.h', 'engine.h', 'devbuf.h', 'color_match.h', 'emit_plan.h', 'laplacian_plan.h', 'anchor_plan.h', 'matting_plan.h', 'frames_plan.h', 'jitter_plan.h', 'flow_plan.h', 'image_pass_kernel.inc', 'channel_mean.h', os.path.join('..', '..', 'include', 'st2.h'))
 
 
 def _hipcc():

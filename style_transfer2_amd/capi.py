@@ -105,6 +105,10 @@ PROTOTYPES = {
     'st_set_anchor_nchw': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_double]),
     'st_get_anchor': (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_double)]),
     'st_get_anchor_terms': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    'st_set_matting': (c_int, [c_void_p, c_double, c_double]),
+    'st_get_matting': (c_int, [c_void_p, POINTER(c_int), POINTER(c_double), POINTER(c_double)]),
+    'st_get_matting_terms': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'st_get_trace_terms': (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     'st_frames_keep': (c_int, [c_void_p, c_int]),
     'st_frame_push': (c_int, [c_void_p]),
     'st_get_frames': (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),

@@ -26,7 +26,8 @@ const char* const kProfNames[P_COUNT] = {"conv3x3_fwd_mfma_f32", "conv3x3_dgrad_
                                           "gram_partial_mfma_bf16", "style_grad_mfma_bf16", "conv3x3_fwd_wino_split_bf16x6", "conv3x3_dgrad_wino_split_bf16x6",
                                           "style_grad_fused_in_conv_dgrad_bf16", "avepool_fwd", "avepool_bwd",
                                           "gram_partial_split_bf16x6", "style_grad_split_bf16x6", "avepool_bwd_map16", "laplacian_pool", "laplacian_stencil", "laplacian_grad", "anchor",
-                                          "frames", "flow_prepare", "flow_linearise", "flow_jacobi", "flow_jacobi_one_workgroup"};
+                                          "frames", "flow_prepare", "flow_linearise", "flow_jacobi", "flow_jacobi_one_workgroup",
+                                          "matting_fit", "matting_apply", "matting_windows"};
 
 static const struct { int kind; const char* name; int cin, cout; } kVgg19[] = {
     {0, "conv1_1", 3, 64}, {0, "conv1_2", 64, 64}, {1, "pool1", 0, 0},
@@ -355,6 +356,7 @@ int ensure_input_buffers(st_ctx* c, int H, int W)
     if (c->tap.have) { c->tap.have = false; c->tap.resized = true; }  // (st_get_tapped_diff: the copy is that of the old geometry)
     lap_input_resized(c);
     anchor_input_resized(c);
+    mat_input_resized(c);
     jitter_input_resized(c);
     const size_t n3 = (size_t)3 * H * W;
     for (int i = 0; i < 2; ++i) ST_TRY(c->x[i].alloc(n3));
@@ -441,6 +443,7 @@ int content_from_device(st_ctx* c, const float* xdev, int H, int W)
     c->have_content = true;
     c->feat_dy = c->feat_dx = 0;                // (jitter: these are the features of the unshifted image)
     c->lap.targets_ok = false;                  // the Laplacian term's targets follow the content image: taken again before the next evaluation
+    c->mat.windows_ok = false;                  // ... and so do the photorealism term's per-window data
     HIP_TRY(hipStreamSynchronize(c->stream));
     return ST_OK;
 }
@@ -524,12 +527,12 @@ int st_create(st_ctx** out, int device_id, const st_layer_desc* layers, int n_la
     c->norm_valid.assign(c->nb * 3, 0);
     ST_TRY(c->norms.alloc(c->nb * 3));
     ST_TRY(c->image_part.alloc(6 * kMaxPartials));
-    ST_TRY(c->trace_dev.alloc(kMaxTraceLayers * 6 + 8 + 4));                  // (+ l_loss, l_grad under st_set_laplacian, a_loss, a_grad under st_set_anchor)
+    ST_TRY(c->trace_dev.alloc(kMaxTraceLayers * 6 + 8 + 6));                  // (+ l_loss, l_grad under st_set_laplacian, a_loss, a_grad under st_set_anchor, m_loss, m_grad under st_set_matting)
     ST_TRY(c->trace_sums.alloc(kMaxTraceLayers * kLayerSlots + kImageSlots));
     ST_TRY(c->lb_dev.alloc(1));
     HIP_TRY(hipMemset(c->lb_dev, 0, sizeof(LbfgsDev)));
     ST_TRY(c->lb_part.alloc(4 * kMaxPartials));
-    ST_TRY(c->trace_host.alloc(kMaxTraceLayers * 6 + 8 + 4));
+    ST_TRY(c->trace_host.alloc(kMaxTraceLayers * 6 + 8 + 6));
     // worker.py:129-133: all-ones weights over every blob until SetWeights arrives
     for (int b = 0; b < c->nb; ++b) c->rows.push_back(ActiveLayer{b, 1.f, 1.f, 1.f, true, true, true});
     c->active = c->rows;

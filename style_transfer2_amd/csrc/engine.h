@@ -43,6 +43,7 @@ enum ProfClass { P_CONV_FWD, P_CONV_DGRAD, P_POOL_FWD, P_POOL_BWD, P_GRAM, P_GRA
                  P_ANCHOR,                                   // anchor_k, the one launch of the anchor term (anchor.hip)
                  P_FRAMES,                                   // frames_k, the one launch of st_set_input_from_frame / st_anchor_from_frame (frames.hip)
                  P_FLOW_PREP, P_FLOW_LINEAR, P_FLOW_JACOBI, P_FLOW_JACOBI_WG,   // optical flow (flow.hip): pyramids, start and interleave; a warp's linearisation; one Jacobi iteration; all of a warp's in one workgroup
+                 P_MAT_FIT, P_MAT_APPLY, P_MAT_SET,           // the photorealism term (matting.hip): the two passes of an evaluation; the per-window data
                  P_COUNT };
 extern const char* const kProfNames[P_COUNT];
 struct ProfRec { int cls; hipEvent_t a, b; double flops, bytes; };
@@ -334,6 +335,20 @@ struct st_ctx {
         bool evaluated = false, have_grad = false; // extra holds the last evaluation's
         bool resized = false;                      // ... it did, until the input was resized
     } anchor;
+    // the photorealism term (st_set_matting; engine_matting.cpp, matting_plan.h)
+    struct Matting {
+        bool on = false;                           // off: every buffer below is empty
+        double weight = 0, eps = 0;
+        MatPlan plan{};                            // of the input's size when the buffers were made (H == 0: none yet)
+        DevBuf<float> I;                           // content_x / 255, (3, H, W)
+        DevBuf<float> win;                         // per-window planes: mu, M (MatPlan::off_*), then a_pb
+        DevBuf<float> extra;                       // prev + g_mat, or g_mat: what the image pass adds after p_w g_p
+        DevBuf<float> part;                        // kMatPartRows * kMaxPartials
+        int cnt_l = 0, cnt_g = 0;                  // partial counts of the last evaluation
+        bool windows_ok = false;                   // I, mu, M are those of the current content image at the plan's size
+        bool evaluated = false, have_grad = false; // a_pb (and extra) hold the last evaluation's
+        bool resized = false;                      // ... they did, until the input was resized
+    } mat;
     // jitter (st_set_jitter; engine_jitter.cpp, jitter_plan.h): the network terms are evaluated on a rolled copy of the iterate
     struct Jitter {
         bool on = false;                           // off: every buffer below is empty
@@ -533,6 +548,17 @@ int anchor_preflight(const st_ctx* c);
 int anchor_eval(st_ctx* c, const float* x, bool want_grad, const float* g_lap, const float** extra);
 int anchor_trace(st_ctx* c, bool want_grad, bool with_lap, float* image_out);
 void anchor_input_resized(st_ctx* c);             // the input has a new size: `extra` is that of an evaluation at the old one
+// ---------------------------------------------------------------------------------------- engine_matting.cpp
+// The photorealism term of an evaluation.  mat_preflight: the refusals (a tile-configured context, no content image, one of another size
+// than the input, an input under 3 x 3), ST_OK with the term off -- no HIP call, nothing changes: every evaluation asks before it enqueues
+// anything.  mat_eval: after the anchor term's launch -- buffers of the input's size, the per-window data where the content or the size
+// changed since they were taken, the first pass and, with a gradient, the second; prev: what `extra` was without this term or NULL;
+// *extra: what launch_image_pass takes as `lap` (left alone for an evaluation without a gradient).  mat_trace: m_loss and m_grad into the
+// image part of the trace at image_out, which holds `others` (0 .. 2) optional terms already
+int mat_preflight(const st_ctx* c);
+int mat_eval(st_ctx* c, const float* x, bool want_grad, const float* prev, const float** extra);
+int mat_trace(st_ctx* c, bool want_grad, int others, float* image_out);
+void mat_input_resized(st_ctx* c);
 // ---------------------------------------------------------------------------------------- engine_jitter.cpp
 // Jitter inside an evaluation; with the mode off each returns at once and launches nothing.  jitter_preflight: the refusal (a
 // tile-configured context) -- no HIP call, nothing changes.  jitter_content: content_feat made those of the shift this evaluation uses

@@ -57,6 +57,7 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
     if (!c->x[0]) return fail(ST_ERR_STATE, "no input image");
     ST_TRY(lap_preflight(c));
     ST_TRY(anchor_preflight(c));
+    ST_TRY(mat_preflight(c));
     ST_TRY(jitter_preflight(c));
     ST_TRY(act_ensure(c, c->act, c->H, c->W));
     ActSet& a = c->act;
@@ -159,6 +160,10 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
     const bool anchor = c->anchor.on;
     if (anchor) ST_TRY(anchor_eval(c, x, want_grad, extra, &extra));
 
+    // the photorealism term (st_set_matting): two window passes; with a gradient the second leaves extra = prev + g_mat (or g_mat)
+    const bool mat = c->mat.on;
+    if (mat) ST_TRY(mat_eval(c, x, want_grad, extra, &extra));
+
     {
         const ImagePassArgs ip = image_pass_args(c, x, scd, want_grad ? grad_out : nullptr, adam, x_next);
         const double n3 = 3.0 * c->H * c->W;
@@ -186,7 +191,7 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
         t.tv_w = c->tv_w; t.p_w = c->p_w; t.p_pow = c->p_pow; t.have_grad = want_grad;
         t.out = c->trace_dev;
         t.sums = c->trace_sums;
-        c->trace_len_last = t.n_layers * 6 + 8 + (lap ? 2 : 0) + (anchor ? 2 : 0);
+        c->trace_len_last = t.n_layers * 6 + 8 + (lap ? 2 : 0) + (anchor ? 2 : 0) + (mat ? 2 : 0);
         ProfScope ps(c, P_FINALIZE, 0, 0);
         HIP_TRY(launch_finalize_trace(t, c->stream));
         if (lap) {                // l_loss and l_grad join the image part of the trace
@@ -197,6 +202,7 @@ int eval_objective(st_ctx* c, const float* x, bool want_grad, float* grad_out, b
             HIP_TRY(launch_trace_lap(tl, c->stream));
         }
         if (anchor) ST_TRY(anchor_trace(c, want_grad, lap, c->trace_dev + t.n_layers * 6));      // a_loss and a_grad, after the Laplacian term's
+        if (mat) ST_TRY(mat_trace(c, want_grad, (lap ? 1 : 0) + (anchor ? 1 : 0), c->trace_dev + t.n_layers * 6));      // m_loss and m_grad, last
     }
     c->lt.any = true;
     return ST_OK;
@@ -325,7 +331,7 @@ int st_get_tapped_diff(st_ctx* c, float* out32, uint16_t* out16, int* have32, in
     return ST_OK;
 }
 
-int st_trace_len(st_ctx* c) { return c ? (int)c->active.size() * 6 + 8 + (c->lap.n ? 2 : 0) + (c->anchor.on ? 2 : 0) : 0; }
+int st_trace_len(st_ctx* c) { return c ? (int)c->active.size() * 6 + 8 + (c->lap.n ? 2 : 0) + (c->anchor.on ? 2 : 0) + (c->mat.on ? 2 : 0) : 0; }
 
 int st_opfunc(st_ctx* c, float* out_loss, float* out_grad, double* trace)
 {
@@ -334,6 +340,7 @@ int st_opfunc(st_ctx* c, float* out_loss, float* out_grad, double* trace)
     if (!c->x[0]) return fail(ST_ERR_STATE, "no input image");
     ST_TRY(lap_preflight(c));                                 // refused before anything is enqueued
     ST_TRY(anchor_preflight(c));
+    ST_TRY(mat_preflight(c));
     ST_TRY(jitter_preflight(c));
     HIP_TRY(hipSetDevice(c->device));
     if (c->tap.blob >= 0 && out_grad) {                       // st_tap_diff: this evaluation's backward copies the tapped diff

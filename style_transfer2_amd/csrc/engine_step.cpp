@@ -281,6 +281,7 @@ int st_step(st_ctx* c, float* out_hwc, double* trace, float* out_loss)
     ST_TRY(emit_preflight(c, EMIT_STEP, out_hwc != nullptr, &emit));       // refused before anything is enqueued
     ST_TRY(lap_preflight(c));
     ST_TRY(anchor_preflight(c));
+    ST_TRY(mat_preflight(c));
     ST_TRY(jitter_preflight(c));
     HIP_TRY(hipSetDevice(c->device));
     ST_TRY(step_enqueue(c));
@@ -307,6 +308,7 @@ int st_step_begin(st_ctx* c)
     ST_TRY(emit_preflight(c, EMIT_STEP_BEGIN, true, &emit));
     ST_TRY(lap_preflight(c));
     ST_TRY(anchor_preflight(c));
+    ST_TRY(mat_preflight(c));
     ST_TRY(jitter_preflight(c));
     HIP_TRY(hipSetDevice(c->device));
     const size_t n3 = (size_t)3 * c->H * c->W;
@@ -315,7 +317,7 @@ int st_step_begin(st_ctx* c)
         for (int i = 0; i < st_ctx::Pipe::kSlots; ++i) {
             HIP_TRY(hipEventCreateWithFlags(&p.ready[i], hipEventDisableTiming));
             HIP_TRY(hipEventCreateWithFlags(&p.done[i], hipEventDisableTiming));
-            ST_TRY(p.trace_pin[i].alloc(kMaxTraceLayers * 6 + 8 + 4));
+            ST_TRY(p.trace_pin[i].alloc(kMaxTraceLayers * 6 + 8 + 6));
         }
     }
     p.begins += 1;

@@ -123,6 +123,7 @@ int st_tile_configure(st_ctx* c, int gH, int gW, int wy0, int wx0, int ty0, int 
     if (!c || !c->x[0]) return fail(ST_ERR_STATE, "set the window image first (st_set_input)");
     if (c->lap.n) return fail(ST_ERR_STATE, "tile-sharded mode does not run the Laplacian term: st_set_laplacian(ctx, 0, NULL, NULL) first, or use a single-context job");
     if (c->anchor.on) return fail(ST_ERR_STATE, "tile-sharded mode does not run the anchor term: st_set_anchor(ctx, NULL, ...) first, or use a single-context job");
+    if (c->mat.on) return fail(ST_ERR_STATE, "tile-sharded mode does not run the photorealism term: st_set_matting(ctx, 0, ...) first, or use a single-context job");
     if (c->jit.on) return fail(ST_ERR_STATE, "tile-sharded mode does not run jitter: st_set_jitter(ctx, 0, 0) first, or use a single-context job");
     if (c->tap.blob >= 0) return fail(ST_ERR_STATE, "tile-sharded mode does not run the diff tap: st_tap_diff(ctx, -1) first");
     if (wy0 < 0 || wx0 < 0 || wy0 + c->H > gH || wx0 + c->W > gW || ty0 < wy0 || tx0 < wx0 ||

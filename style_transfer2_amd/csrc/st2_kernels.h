@@ -8,6 +8,7 @@
 #include "emit_plan.h"
 #include "laplacian_plan.h"
 #include "anchor_plan.h"
+#include "matting_plan.h"
 #include "frames_plan.h"
 #include "jitter_plan.h"
 #include "flow_plan.h"
@@ -17,6 +18,7 @@ namespace st2 {
 constexpr int kMaxPartials = 1024;   // grid cap (= partial-sum slots) of every reducing kernel
 static_assert(kLapMaxBlocks == kMaxPartials, "laplacian_plan.h sizes its partial-sum rows like every reducing kernel");
 static_assert(kAnchorMaxBlocks == kMaxPartials, "anchor_plan.h sizes its partial-sum rows like every reducing kernel");
+static_assert(kMatMaxBlocks == kMaxPartials, "matting_plan.h sizes its partial-sum rows like every reducing kernel");
 constexpr int kConvCC = 4;           // K granularity of the packed conv weights (staged chunk = 4 or 8)
 constexpr int kCoutQuantum = 64;     // conv weights are zero-padded to a multiple of this many outputs
 
@@ -381,6 +383,21 @@ struct AnchorArgs { const float* x; const float* ax; const float* m; const float
 hipError_t launch_anchor(const AnchorArgs& a, int grid, int grid_vec, int* n_partial, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
+// The photorealism term (matting.hip; matting_plan.h has the validation, the buffer layout, the tiles and the grids): planes x, I, extra
+// and the optional prev of (3, H, W); per-window planes of Hw * Ww = (H - 2) * (W - 2) floats in `win` (mu at off_mu, M at off_M) and `ab`
+// (3 channels x a0 a1 a2 pb).
+// ------------------------------------------------------------------------------------------
+// I = cx / 255 (`pixels` floats), then per window mu and M, the float64 cofactor inverse of st2.h, each rounded once to fp32
+struct MatWindowsArgs { const float* I; float* win; int H, W, Ww; size_t windows, off_mu, off_M; double eps; };
+hipError_t launch_mat_windows(const float* cx, float* I, size_t pixels, const MatWindowsArgs& a, hipStream_t s);
+// first pass: ab per window and channel; part[block] = the workgroup's sum of J (`grid` slots)
+struct MatFitArgs { const float* x; const float* I; const float* win; float* ab; float* part; int H, W, Hw, Ww, tiles_x; size_t tiles, windows, off_mu, off_M; double eps; };
+hipError_t launch_mat_fit(const MatFitArgs& a, int grid, hipStream_t s);
+// second pass: extra = prev + w (2 Lu) (prev == NULL: w (2 Lu)); part[block] = the workgroup's sum of (w (2 Lu))^2 (`grid` slots)
+struct MatApplyArgs { const float* x; const float* I; const float* win; const float* ab; const float* prev; float* extra; float* part; int H, W, Hw, Ww, tiles_x; size_t tiles, windows, off_mu; float w; };
+hipError_t launch_mat_apply(const MatApplyArgs& a, int grid, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------
 // Jitter (jitter.hip; jitter_plan.h has the shift sequence, the source index and the grids): dst = roll(src, (p.dy, p.dx)) over the three
 // planes of (3, H, W), dst[c][y][x] = src[c][(y - dy) mod H][(x - dx) mod W].  A pure move: every element is read once and written once.
 // Aligned 16-byte stores of four destination pixels (their sources are dword loads: a shifted row start is not aligned, a group may
@@ -461,6 +478,12 @@ hipError_t launch_trace_lap(const TraceLapArgs& a, hipStream_t s);
 // or from 10 to 12.  part: two rows of kAnchorMaxBlocks partials -- sum e d (count_l), then sum g_anc^2 (count_g)
 struct TraceAnchorArgs { const float* part; int count_l, count_g; float w; double image_n; int have_grad, with_lap; float* image_out; };
 hipError_t launch_trace_anchor(const TraceAnchorArgs& a, hipStream_t s);
+// The photorealism term's part of the trace (matting.hip), after the Laplacian and the anchor term's on the same `out` (others: how many
+// of those two are on): m_loss = w * float(sum J) follows the last loss term, m_grad = sqrt(float(sum g_mat^2 / image_n)) (0 without a
+// gradient) the last gradient norm, and loss becomes loss + m_loss: the image part grows by two scalars.  part: two rows of
+// kMatMaxBlocks partials -- sum J (count_l), then sum g_mat^2 (count_g)
+struct TraceMatArgs { const float* part; int count_l, count_g; float w; double image_n; int have_grad, others; float* image_out; };
+hipError_t launch_trace_mat(const TraceMatArgs& a, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
 // Fixed-step L-BFGS as a device-resident state machine (lbfgs.hip), optimizers.py:49-125, utils.py:29-46

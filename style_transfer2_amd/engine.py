@@ -614,6 +614,40 @@ class Engine:
         check(self.lib.st_get_anchor_terms(self._ctx, _ptr(ax), _ptr(mask), _ptr(extra)))
         return ax, mask, extra
 
+    # -- the photorealism term (st2.h: st_set_matting) ------------------------------------------------------------------------------
+    def set_matting(self, weight, eps=1e-7):
+        """The matting-Laplacian regulariser of Luan et al.: every evaluation adds weight * sum_c u_c' L u_c (u = x / 255, L the matting
+        Laplacian of the content image with regularisation eps in [1e-9, 1]) to the loss and its gradient to the image gradient, and the
+        trace has two more scalars (m_loss, m_grad).  The term is zero where the result is locally an affine function of the content's
+        colours.  weight 0, None or False turns it off (the default).  It follows the content image; evaluations are refused without
+        one of the input's size and under 3 x 3.  Refused while a pipelined iteration is in flight and on a tile-configured context."""
+        check(self.lib.st_set_matting(self._ctx, float(weight or 0.0), float(eps)))
+
+    def matting(self):
+        """The term in force: None while it is off, else a dict with 'weight' and 'eps'."""
+        on, weight, eps = c_int(), c_double(), c_double()
+        check(self.lib.st_get_matting(self._ctx, byref(on), byref(weight), byref(eps)))
+        if not on.value:
+            return None
+        return {'weight': weight.value, 'eps': eps.value}
+
+    def matting_terms(self, want_extra=True):
+        """Test hook: (mu, M, a_pb, extra) of the last evaluation -- the window means (3, H - 2, W - 2), the inverse covariances
+        (6, H - 2, W - 2) in the order 00 01 02 11 12 22, the fits (3, 4, H - 2, W - 2) (a0 a1 a2 pb per channel of the iterate) and the
+        plane the image pass added after the p-norm term (1, 3, H, W); None for it when want_extra is False."""
+        h, w = self.input_shape()
+        hw, ww = max(h - 2, 1), max(w - 2, 1)
+        mu, m, ab = np.empty((3, hw, ww), F32), np.empty((6, hw, ww), F32), np.empty((3, 4, hw, ww), F32)
+        extra = np.empty((1, 3, h, w), F32) if want_extra else None
+        check(self.lib.st_get_matting_terms(self._ctx, _ptr(mu), _ptr(m), _ptr(ab), _ptr(extra)))
+        return mu, m, ab, extra
+
+    def trace_terms(self):
+        """Which optional image-space terms are on, as the trace orders them: (laplacian, anchor, matting)."""
+        lap, anchor, mat = c_int(), c_int(), c_int()
+        check(self.lib.st_get_trace_terms(self._ctx, byref(lap), byref(anchor), byref(mat)))
+        return bool(lap.value), bool(anchor.value), bool(mat.value)
+
     # -- jitter (st2.h: st_set_jitter) ------------------------------------------------------------------------------------------------
     def set_jitter(self, radius, seed=0):
         """Evaluate the network terms on the iterate rolled by a random shift of up to `radius` pixels per axis (1 .. 4096), one shift per

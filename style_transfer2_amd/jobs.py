@@ -51,7 +51,7 @@ def load_mask(path, hw):
 def run_job(transfer, content, style, iterations, size=None, style_size=None, optimizer='adam', step_size=None,
             weights=None, params=None, init=None, seed=0, callback=None, iterate_average=None, original_colors=None,
             match_style_colors=None, laplacian=None, anchor=None, init_nchw=None, init_frame=None, anchor_frames=None, jitter=None,
-            jitter_seed=0):
+            jitter_seed=0, matting=None):
     """One whole stylisation: content/style are PIL images or HxWx3 arrays.  Returns the final HxWx3 float32
     image.  Mirrors app.init_arrays + 'start': SetImages(reset) -> SetWeights -> SetOptimizer -> iterate.
     iterate_average: a decay in (0, 1) makes every image handed out (the callback's, the result) the bias-corrected running mean of
@@ -72,8 +72,14 @@ def run_job(transfer, content, style, iterations, size=None, style_size=None, op
     anchor_from_frame): the first entry sets the anchor, the others accumulate into it; not together with anchor.
     jitter: a radius R in 1 .. 4096 makes every iteration show the network the iterate rolled by a random shift of up to R pixels per
     axis, drawn from jitter_seed (Engine.set_jitter: the grid artefacts of pools and strides go; the iterate itself never moves); 0
-    turns it off; None leaves the engine as it is."""
+    turns it off; None leaves the engine as it is.
+    matting: (weight, eps) or a weight alone (eps 1e-7) turns the photorealism term on (StyleTransfer.set_matting: the matting Laplacian
+    of the content image keeps the result locally affine in the content's colours, so straight edges stay straight); False or 0 turns
+    it off; None leaves the engine as it is."""
     from .device_optimizers import AdamOptimizer, LBFGSOptimizer
+    from .matting import matting_arg
+    if matting is not None:
+        matting = matting_arg(matting)                      # (a ValueError before anything is set)
     if init_frame is not None and init_nchw is not None:
         raise ValueError('init_frame and init_nchw are two ways to start: give one')
     if anchor_frames is not None and anchor is not None:
@@ -117,6 +123,8 @@ def run_job(transfer, content, style, iterations, size=None, style_size=None, op
         else:
             image, mask, weight = anchor
             transfer.set_anchor(image, mask, weight)
+    if matting is not None:
+        transfer.set_matting(*matting)
     if jitter is not None:
         transfer.engine.set_jitter(jitter, jitter_seed)     # (after the resets: the shift sequence starts at step 0 of this job)
     if anchor_frames is not None:
@@ -139,7 +147,7 @@ def run_job(transfer, content, style, iterations, size=None, style_size=None, op
 
 def run_tiled_job(net_params, content, style, iterations, grid, size=None, style_size=None, weights=None, params=None, init=None,
                   seed=0, device=0, precision='fp32', topology=None, callback=None, optimizer='adam', step_size=None, shard_style=False,
-                  iterate_average=None, original_colors=None, match_style_colors=None, laplacian=None, anchor=None):
+                  iterate_average=None, original_colors=None, match_style_colors=None, laplacian=None, anchor=None, matting=None):
     """The same job for an image no single engine holds (an 8192 x 8192 image has conv1 blobs of 17 GB each): the image is cut into
     grid = (rows, cols) tiles, every tile + apron is an engine context of THIS process on the one GPU (tiled.InProcessFabric: one
     thread per rank, the all-reduces and strip exchanges are device-to-device copies); one st_tile_step per rank and iteration, Adam or
@@ -155,7 +163,10 @@ def run_tiled_job(net_params, content, style, iterations, grid, size=None, style
     laplacian: the Laplacian term does not run tile-sharded (st_set_laplacian refuses a tile-configured context): any levels, here or
     in params['laplacian'], are a ValueError before anything is built.
     anchor: the anchor term does not run tile-sharded either (st_set_anchor refuses a tile-configured context): a ValueError as well.
+    matting: nor does the photorealism term (st_set_matting refuses a tile-configured context): a ValueError as well.
     Returns the stitched HxWx3 float32 image; callback(i, trace values) after every iteration."""
+    if matting:
+        raise ValueError('the photorealism term does not run tile-sharded: use run_job, or drop matting')
     if anchor:
         raise ValueError('the anchor term does not run tile-sharded: use run_job, or drop the anchor')
     if laplacian or (params and params.get('laplacian')):

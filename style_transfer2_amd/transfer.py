@@ -196,6 +196,11 @@ class StyleTransfer:
         self._anchor_on = image is not None
         self.objective_changed()
 
+    def set_matting(self, weight, eps=1e-7):
+        """The photorealism term (Engine.set_matting): the matting Laplacian of the content image; weight 0, None or False turns it off."""
+        self.engine.set_matting(weight, eps)
+        self.objective_changed()
+
     def anchor_from_frame(self, j, flow=None, forward_flow=None, mask=None, weight=1.0, accumulate=False):
         """The anchor term from a kept frame, warped and weighted on the device (Engine.anchor_from_frame)."""
         self.engine.anchor_from_frame(j, flow, forward_flow, mask, weight, accumulate)
@@ -224,11 +229,17 @@ class StyleTransfer:
                     t('%s_%s_loss' % (layer, tag), v[off])
                     t('%s_%s_grad' % (layer, tag), v[off + 1])
         g = list(values[6 * len(active):])
-        # the image part is 8 long, plus 2 with the Laplacian term on, plus 2 with the anchor term: a 10-long one is the anchor's only
-        # when this object turned that term on (set_anchor)
-        anchor = len(g) == 12 or (len(g) == 10 and self._anchor_on)
-        lap = len(g) - (2 if anchor else 0) == 10           # the Laplacian term is on: l_loss follows p_loss, l_grad follows p_grad
-        extra = [name for name, on in (('l', lap), ('a', anchor)) if on]
+        # the image part is 8 long, plus 2 for each optional term that is on (Laplacian, anchor, photorealism): the engine says which.
+        # A backend that cannot say has no photorealism term; there a 10-long part is the anchor's only when this object turned that
+        # term on (set_anchor)
+        ask = getattr(self.engine, 'trace_terms', None)
+        if callable(ask):
+            lap, anchor, mat = ask()
+        else:
+            anchor = len(g) == 12 or (len(g) == 10 and self._anchor_on)
+            lap = len(g) - (2 if anchor else 0) == 10       # the Laplacian term is on: l_loss follows p_loss, l_grad follows p_grad
+            mat = False
+        extra = [name for name, on in (('l', lap), ('a', anchor), ('m', mat)) if on]
         n = 3 + len(extra)                                  # losses, then as many gradient norms, then loss and grad
         for name, v in zip(['scd', 't', 'p'] + extra, g[:n]):
             t(name + '_loss', v)

@@ -52,6 +52,8 @@ def parser():
     ap.add_argument('--jitter', type=int, default=None, metavar='R',
                     help='st_set_jitter: evaluate the network on the iterate rolled by a random shift of up to R pixels per axis in every iteration (1 .. 4096; removes the grid artefacts of pools and strides); not with --grid')
     ap.add_argument('--jitter-seed', type=int, default=None, metavar='S', help='with --jitter: the seed of the shift sequence, 0 .. 2**64 - 1 (default 0)')
+    ap.add_argument('--matting', default='', metavar='W[:EPS]',
+                    help='st_set_matting: the photorealism term, the matting Laplacian of the content image with the weight W such as 1e4 and the regularisation EPS in [1e-9, 1] (default 1e-7); not with --grid')
     return ap
 
 
@@ -62,6 +64,8 @@ def main(argv=None):
         ap.error('--laplacian with --grid: tile-sharded mode does not run the Laplacian term')
     if args.anchor and args.grid:
         ap.error('--anchor with --grid: tile-sharded mode does not run the anchor term')
+    if args.matting and args.grid:
+        ap.error('--matting with --grid: tile-sharded mode does not run the photorealism term')
     if args.jitter and args.grid:
         ap.error('--jitter with --grid: tile-sharded mode does not run jitter')
     if args.jitter_seed is not None and args.jitter is None:
@@ -73,11 +77,15 @@ def main(argv=None):
 
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import style_transfer2_amd as st2
-    from style_transfer2_amd import jitter as st2_jitter, jobs, laplacian, weights as st2_weights
+    from style_transfer2_amd import jitter as st2_jitter, jobs, laplacian, matting as st2_matting, weights as st2_weights
     try:
         jit = st2_jitter.check_jitter(args.jitter, args.jitter_seed or 0) if args.jitter is not None else None
     except ValueError as err:
         ap.error('--jitter %s: %s' % (args.jitter, err))
+    try:
+        mat = st2_matting.parse_matting(args.matting) if args.matting else None
+    except ValueError as err:
+        ap.error('--matting %s: %s' % (args.matting, err))
     try:
         levels = laplacian.parse_levels(args.laplacian) if args.laplacian else None
     except ValueError as err:
@@ -113,7 +121,7 @@ def main(argv=None):
         image = jobs.run_job(job, content, jobs.load_rgb(args.style), args.iters, size=args.size,
                              style_size=args.style_size or None, optimizer=args.optimizer, iterate_average=args.avg_decay,
                              original_colors=args.original_colors or None, match_style_colors=args.match_style_colors or None,
-                             laplacian=levels, anchor=anchor, jitter=jit[0] if jit else None, jitter_seed=jit[1] if jit else 0)
+                             laplacian=levels, anchor=anchor, jitter=jit[0] if jit else None, jitter_seed=jit[1] if jit else 0, matting=mat)
     Image.fromarray(np.uint8(np.clip(image, 0, 255))).save(args.out)
     print('wrote', args.out, image.shape)
 

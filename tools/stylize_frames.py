@@ -36,6 +36,7 @@ def parser():
     ap.add_argument('--forward-flows', default='', metavar='DIR', help='<stem>.npy: the flow from the frame before; derives the reliability on the device')
     ap.add_argument('--long-term', type=long_term_arg, default=[], metavar='J,J', help='earlier frames to anchor uncovered pixels to, e.g. 2,4 (each 2 .. 8)')
     ap.add_argument('--anchor-weight', type=float, default=1.0, metavar='W')
+    ap.add_argument('--matting', default='', metavar='W[:EPS]', help='st_set_matting for every frame: the photorealism term with the weight W and the regularisation EPS (default 1e-7)')
     ap.add_argument('--estimate-flow', action='store_true', help='estimate on the device every flow no file gives (st_flow_estimate)')
     ap.add_argument('--flow-alpha', type=float, default=None, metavar='A', help='smoothness weight of the estimator (default 0.06)')
     ap.add_argument('--flow-iters', type=int, default=None, metavar='N', help='Jacobi iterations per warp (default 40)')
@@ -136,7 +137,11 @@ def main(argv=None):
     estimate = flow_params(ap, args)
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import style_transfer2_amd as st2
-    from style_transfer2_amd import jobs, weights as st2_weights
+    from style_transfer2_amd import jobs, matting as st2_matting, weights as st2_weights
+    try:
+        mat = st2_matting.parse_matting(args.matting) if args.matting else None
+    except ValueError as err:
+        ap.error('--matting %s: %s' % (args.matting, err))
 
     frames = [np.uint8(jobs.resize_to_fit(jobs.load_rgb(path), args.size)) for path in args.frames]
     stems = [os.path.splitext(os.path.basename(path))[0] for path in args.frames]
@@ -177,7 +182,7 @@ def main(argv=None):
             for path in save_flows(args.save_flows, stems, flows, forward_flows, long_term):
                 print('wrote', path)
     results = jobs.run_frames(job, frames, style, args.iters, args.anchor_weight, flows=flows, masks=masks, forward_flows=forward_flows, long_term=long_term,
-                              first_iterations=args.first_iters or None, optimizer=args.optimizer)
+                              first_iterations=args.first_iters or None, optimizer=args.optimizer, matting=mat)
     os.makedirs(args.out_dir, exist_ok=True)
     for stem, image in zip(stems, results):
         out = os.path.join(args.out_dir, stem + '.png')

@@ -140,6 +140,21 @@ def read_jitter(config):
         raise ValueError('config key jitter = %r: %s (expected R or R:SEED such as 8 or 8:1234)' % (raw, err)) from None
 
 
+def read_matting(config):
+    """The optional config key ``matting = W`` or ``matting = W:EPS``: the photorealism term (Engine.set_matting), the matting Laplacian
+    of the content image with the weight W (finite; ``0`` or ``off`` is off) and the regularisation EPS in [1e-9, 1] (default 1e-7).
+    Returns (W, EPS), or None when the key is absent or empty (no call is made: the engine's default, off, stays); a malformed value is
+    a ValueError that names the key.  Pure: any mapping with ``get`` will do."""
+    raw = config.get('matting', None)
+    if raw is None or str(raw).strip() == '':
+        return None
+    from style_transfer2_amd.matting import parse_matting
+    try:
+        return parse_matting(raw)
+    except ValueError as err:
+        raise ValueError('config key matting = %r: %s (expected W or W:EPS such as 10000 or 10000:1e-7)' % (raw, err)) from None
+
+
 COLOR_KEYS = ('original_colors', 'style_color_match')
 
 
@@ -380,6 +395,10 @@ class Worker:
             jitter = read_jitter(config)
             if jitter is not None:
                 self.transfer.engine.set_jitter(*jitter)
+            # the photorealism term (config key matting): two more trace scalars, m_loss and m_grad
+            matting = read_matting(config)
+            if matting is not None:
+                self.transfer.engine.set_matting(*matting)
             async_send = str(config.get('async_iterate', '1')).lower() not in ('0', 'false', 'no')
             if async_send:
                 self.sock_out = AsyncSender(sock_out)
